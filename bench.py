@@ -16,9 +16,18 @@ region.  ``value`` = audio samples pushed through a flow pass per second, whole 
 starts ``python -m torch.distributed.run --nproc-per-node N bench.py ...`` as a CHILD process (one rank per GPU over
 RCCL), relays rank 0's JSON line and exits non-zero if fewer than N GPUs exist or the line does not say ``n_gpus: N``.
 
-One JSON line on stdout (rank 0) with ``roofline`` and ``cpu_baseline`` objects as described in DESIGN.md
-"Measurement", plus ``rtf_10s`` (BASELINE configs[3]: 10 s clip inverse, one clip per GPU) and ``train``
-(configs[2]: the data-parallel training step, B=8 x 6400 samples per GPU, RCCL gradient all-reduce).
+A plain run sets up, warms up, times exactly ``--steps`` steps once and prints one JSON line on stdout (rank 0):
+``metric``, ``value``, ``unit``, ``higher_is_better``, ``dtype``, ``ms_per_step`` and the configuration.
+
+``--full`` adds everything else, as described in DESIGN.md "Measurement": the timed region repeated (``--repeats``,
+median reported), the check that the overlapped last step is bit-identical to a one-stream pass, per-direction
+timings, ``roofline``, ``path``, ``latency_b1`` and ``cpu_baseline`` objects, plus ``rtf_10s`` (BASELINE configs[3]:
+10 s clip inverse, one clip per GPU), ``fp8`` (configs[4]) and ``train`` (configs[2]: the data-parallel training step,
+B=8 x 6400 samples per GPU, RCCL gradient all-reduce).
+
+``--dump-outputs DIR`` writes what the last timed step returned, rank 0's arrays in float32: ``log_p.npy`` and
+``logdet.npy`` (the global-batch NLL terms, 0-dim) and ``wav.npy`` (the synthesised clips, [B, T, 1]).  The inputs
+and weights are seeded, so two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -576,7 +585,13 @@ def main():
     ap.add_argument("--chain-mode", type=int, default=0, help="fwn_model_desc.chain_mode (developer A/B: 1 = every flow on its own)")
     ap.add_argument("--persist-mode", type=int, default=0, help="fwn_model_desc.persist_mode (0 default, 1 no one-launch flows, 2 wherever they exist)")
     ap.add_argument("--serial", action="store_true", help="forward and inverse on one stream (no overlap)")
-    ap.add_argument("--repeats", type=int, default=3, help="how many times the K-step timed region is run (the line reports the median)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="how many times the K-step timed region is run (the line reports the median); default 1, 3 with --full")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the checks and secondary measurements (result check, per-direction timings, roofline, "
+                         "per-block table, B=1 latency, CPU baseline, 10 s clip, fp8 and training-step legs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (log_p, logdet, wav) as DIR/<name>.npy, float32")
     ap.add_argument("--lanes", type=int, default=7,
                     help="HIP streams per direction; successive (independent) steps rotate over them")
     ap.add_argument("--no-train", action="store_true", help="skip the configs[2] training-step leg")
@@ -588,6 +603,8 @@ def main():
     ap.add_argument("--force-collectives", action="store_true",
                     help="issue the gradient all-reduces even with one rank (exercises the RCCL path on one GPU)")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 3 if args.full else 1
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -702,17 +719,19 @@ def main():
             cur.wait_stream(st)
         return nll, wav
 
-    # reference for the result check below: one pass of each direction alone on the current stream
-    ref_nll = torch.stack(model.forward(x, c)).clone()
-    ref_wav = model.reverse(z, c).clone()
+    if args.full:
+        # reference for the result check below: one pass of each direction alone on the current stream
+        ref_nll = torch.stack(model.forward(x, c)).clone()
+        ref_wav = model.reverse(z, c).clone()
     run_steps(args.warmup)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
     # The timed region - EXACTLY args.steps steps between barrier + synchronize brackets, MAX over the ranks - is run
-    # args.repeats times (default 3); the line reports the MEDIAN region and lists all of them (at 0.1 - 0.2 s a single
-    # region moves by about as much from run to run as a round's gain; the dominant kernel's own launch groups spread 52 - 63 us).
+    # args.repeats times (default 1, 3 with --full); the line reports the MEDIAN region and lists all of them (at
+    # 0.1 - 0.2 s a single region moves by about as much from run to run as a round's gain; the dominant kernel's own launch
+    # groups spread 52 - 63 us).
     regions = []
     for _ in range(max(1, args.repeats)):
         t0 = time.perf_counter()
@@ -728,11 +747,17 @@ def main():
             el = float(tmax.item())
         regions.append(el)
     elapsed = sorted(regions)[len(regions) // 2]
-    assert bool(torch.isfinite(nll).all()) and bool(torch.isfinite(wav).all())
-    # the overlapped passes of the timed region must reproduce the single-stream result bit for bit
-    same = bool(torch.equal(wav, ref_wav)) and (world > 1 or bool(torch.equal(nll, ref_nll)))
-    if not same:
-        raise SystemExit("bench.py: the overlapped passes differ from the single-stream result")
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its last step (the NLL terms all-reduced over the ranks)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, arr in (("log_p", nll[0]), ("logdet", nll[1]), ("wav", wav)):
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), arr.detach().cpu().numpy().astype(np.float32))
+    if args.full:
+        assert bool(torch.isfinite(nll).all()) and bool(torch.isfinite(wav).all())
+        # the overlapped passes of the timed region must reproduce the single-stream result bit for bit
+        same = bool(torch.equal(wav, ref_wav)) and (world > 1 or bool(torch.equal(nll, ref_nll)))
+        if not same:
+            raise SystemExit("bench.py: the overlapped passes differ from the single-stream result")
 
     # per-direction timings (HIP events on the launch stream), rank 0, for the breakdown fields
     def timed(fn, n=5):
@@ -746,8 +771,6 @@ def main():
 
     out = {}
     if rank == 0:
-        fwd_s = timed(lambda: model.forward(x, c))
-        inv_s = timed(lambda: model.reverse(z, c))
         fps = flop_per_sample(hp)
         ms = elapsed / args.steps * 1e3
         value = 2.0 * b * t * world / (elapsed / args.steps)
@@ -762,25 +785,30 @@ def main():
                        "weights": "synthetic seed 1234, ActNorm DDI on the first (global) batch",
                        "parallelism": "batch shard x%d, no data-path collective (2-scalar NLL all-reduce)" % world,
                        "streams": "serial" if args.serial else "%d per direction" % args.lanes,
-                       "results": "last step bit-identical to the single-stream pass",
+                       "results": ("last step bit-identical to the single-stream pass" if args.full
+                                   else "not checked (--full checks them)"),
                        "timed_regions": {"repeats": len(regions), "steps_each": args.steps, "reported": "median",
                                          "ms_per_step_each": [r / args.steps * 1e3 for r in regions],
                                          "ms_per_step_min": min(regions) / args.steps * 1e3,
                                          "ms_per_step_max": max(regions) / args.steps * 1e3}},
-            "fwd_samples_per_s": b * t / fwd_s, "inv_samples_per_s": b * t / inv_s,
-            "fwd_ms": fwd_s * 1e3, "inv_ms": inv_s * 1e3,
             "model_tflops": value / world * fps / 1e12,
             "model_mfma_frac": value / world * fps / 1e12 / MFMA_PEAK_TFLOPS,
-            "realtime_factor_inverse": b * t / inv_s / hp.sample_rate,
         }
-        out["roofline"] = gate_roofline(model, hp, b, t)
-        out["path"] = path_roofline(hp, b, t, fwd_s, inv_s, block_table(model, hp, b, t, x, c, z))
-        out["latency_b1"] = None if args.no_latency else latency_b1(model, hp, t, dev, params=params)
-        if args.no_cpu_baseline or world > 1:
-            out["cpu_baseline"] = None
-        else:
-            out["cpu_baseline"] = cpu_baseline(hp, params, t)
-    out["rtf_10s"] = out["train"] = out["fp8"] = None
+        if args.full:
+            fwd_s = timed(lambda: model.forward(x, c))
+            inv_s = timed(lambda: model.reverse(z, c))
+            out.update({"fwd_samples_per_s": b * t / fwd_s, "inv_samples_per_s": b * t / inv_s,
+                        "fwd_ms": fwd_s * 1e3, "inv_ms": inv_s * 1e3,
+                        "realtime_factor_inverse": b * t / inv_s / hp.sample_rate})
+            out["roofline"] = gate_roofline(model, hp, b, t)
+            out["path"] = path_roofline(hp, b, t, fwd_s, inv_s, block_table(model, hp, b, t, x, c, z))
+            out["latency_b1"] = None if args.no_latency else latency_b1(model, hp, t, dev, params=params)
+            if args.no_cpu_baseline or world > 1:
+                out["cpu_baseline"] = None
+            else:
+                out["cpu_baseline"] = cpu_baseline(hp, params, t)
+    if args.full:
+        out["rtf_10s"] = out["train"] = out["fp8"] = None
 
     def emit(note=None):
         if rank == 0:
@@ -793,23 +821,23 @@ def main():
         out[name] = {"error": "%s: %s" % (type(e).__name__, e)}
         print("bench.py rank %d: the %s leg failed:\n%s" % (rank, name, traceback.format_exc()), file=sys.stderr, flush=True)
 
-    # optional legs (all ranks take part; a failure or a stall is reported inside the line, never instead of it)
+    # optional legs, --full only (all ranks take part; a failure or a stall is reported inside the line, never instead of it)
     deadline = Deadline(emit)
-    if not args.no_rtf:
+    if args.full and not args.no_rtf:
         deadline.arm(args.leg_timeout, "the configs[3] 10 s clip leg")
         try:
             out["rtf_10s"] = rtf_10s(model, hp, dev, world)
         except Exception as e:
             leg_failed("rtf_10s", e)
         deadline.disarm()
-    if not args.no_fp8 and rank == 0:
+    if args.full and not args.no_fp8 and rank == 0:
         deadline.arm(args.leg_timeout, "the configs[4] fp8 leg")
         try:
             out["fp8"] = fp8_leg(hp, params, model, x, c, z, b, t)
         except Exception as e:
             leg_failed("fp8", e)
         deadline.disarm()
-    if not args.no_train:
+    if args.full and not args.no_train:
         del model
         torch.cuda.empty_cache()
         deadline.arm(args.leg_timeout, "the configs[2] training-step leg")

@@ -1,8 +1,11 @@
 """CPU checks of bench.py's contract pieces that need no GPU: the algorithmic FLOP figure the roofline is computed
-from, and the loud failure without a GPU (the HIP path has no CPU fallback)."""
+from, and the loud failure without a GPU (the HIP path has no CPU fallback); plus one GPU check of the
+plain run's line and its --dump-outputs arrays."""
 import os
 import subprocess
 import sys
+
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -103,3 +106,28 @@ def test_path_roofline_quotes_committed_profiles_only_for_the_current_kernel_sou
     assert "no profile of the current kernel sources" in r["blocks_launch_counts_source"] and "no profile" in r["hbm_source"]
     assert bench.path_roofline(hp, 8, 16128, 4.0e-3, 4.1e-3)["blocks"] is None
     assert bench.path_roofline(hp, 3, 999 * 256, 1e-3, 1e-3)["survey_bound_us"] is None      # no SURVEY bound for other shapes
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_given_steps_and_dumps_the_last_steps_outputs(tmp_path):
+    """A plain run prints the headline only, with `steps` timed once, and --dump-outputs writes what the last timed step
+    returned (float32, the bench workload's shapes); the seeded inputs make two runs' dumps equal."""
+    import json
+    import numpy as np
+    dumps = []
+    for k, steps in enumerate((2, 3)):
+        d = tmp_path / ("run%d" % k)
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", "1",
+                              "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-3000:]
+        rec = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
+        assert rec["steps"] == steps and rec["config"]["timed_regions"]["repeats"] == 1 and rec["ms_per_step"] > 0
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype"):
+            assert key in rec
+        assert "roofline" not in rec and "train" not in rec and "cpu_baseline" not in rec
+        arrs = {n: np.load(d / (n + ".npy")) for n in ("log_p", "logdet", "wav")}
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrs.values())
+        assert arrs["log_p"].shape == () and arrs["wav"].shape == (rec["config"]["clips_per_gpu"], rec["config"]["samples_per_clip"], 1)
+        dumps.append(arrs)
+    for n in dumps[0]:
+        assert np.array_equal(dumps[0][n], dumps[1][n]), n

@@ -4,7 +4,7 @@ O=gpurun_out/${1:-check}
 mkdir -p $O
 timeout 2400 python3 -m pytest tests -m gpu -x -q > $O/pytest.txt 2>&1
 tail -5 $O/pytest.txt
-python3 bench.py --no-cpu-baseline > $O/bench.json 2> $O/bench.err
+python3 bench.py --full --no-cpu-baseline > $O/bench.json 2> $O/bench.err
 python3 -c "
 import json,sys
 d=json.load(open('$O/bench.json'))

@@ -7,12 +7,12 @@ TAG=${1:-q}
 O=$R/gpurun_out/quick
 mkdir -p $O
 export TMPDIR=/tmp
-(cd /tmp && rocprofv3 --kernel-trace --output-format csv -d $O/rocprof_$TAG -o $TAG -- python3 $R/bench.py --no-cpu-baseline --serial --no-train --no-rtf --no-fp8 --no-latency --steps 12 --warmup 3 > $O/${TAG}_rocprof.log 2>&1)
+(cd /tmp && rocprofv3 --kernel-trace --output-format csv -d $O/rocprof_$TAG -o $TAG -- python3 $R/bench.py --full --no-cpu-baseline --serial --no-train --no-rtf --no-fp8 --no-latency --steps 12 --warmup 3 > $O/${TAG}_rocprof.log 2>&1)
 T=$(ls $O/rocprof_$TAG/*/*kernel_trace.csv $O/rocprof_$TAG/*kernel_trace.csv 2>/dev/null | head -1)
 python3 tools/pass_table.py $T > $O/${TAG}_pass_table.txt
 python3 tools/prof_summary.py $T 40 > $O/${TAG}_kernel_summary.txt
 rm -rf $O/rocprof_$TAG
-python3 bench.py --no-cpu-baseline --no-train --no-rtf --no-fp8 --no-latency > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
+python3 bench.py --full --no-cpu-baseline --no-train --no-rtf --no-fp8 --no-latency > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
 cat $O/${TAG}_pass_table.txt
 python3 - <<PY
 import json
