@@ -1380,3 +1380,46 @@ def test_random_small_configurations_match_oracle():
             xr = m.reverse(dev(inp["z"]), dev(inp["c"])).cpu().numpy()
             assert np.abs(xr - x0).max() < ABS_WAV * max(1.0, np.abs(x0).max()), (n_block, n_flow, n_layer, b, t)
         done += 1
+
+
+@pytest.mark.parametrize("full", [False, True])
+def test_which_streams_a_pack_sets(full):
+    """The fragment-order streams select the kernels: an inference pack sets the gate stream Wgs[l] where
+    the register-streamed gate has a form for cin, the tail stream Wts where the flow has one ZeroConv pair tile and the
+    hoisted conditioning's stream where K >= 640; a refreshed (training) pack sets only Wts; tail_stream=False none."""
+    hp = default_hparams() if full else small_hparams(n_block=3, n_flow=2, n_layer=2, num_mels=16)
+    lib = _lib.load()
+    params = W.synthetic_params(hp, 3)
+    half = hp.num_mels // 2
+    for refresh, tail_stream in ((False, True), (True, True), (False, False)):
+        pm = packing.pack_model(params, hp, "cuda", refresh=refresh, tail_stream=tail_stream)
+        assert (getattr(pm, "plan", None) is not None) == refresh
+        for i in range(hp.n_block):
+            ch, cin = 1 << i, half * (2 << i)
+            kcpad, npt = packing.roundup(cin, 64), max(1, (ch + 31) // 32)
+            assert bool(pm.model_desc.cond_stream[i]) == (not refresh and kcpad >= 640), (refresh, i)
+            for j in range(hp.n_flow):
+                d = pm.flow_descs[i * hp.n_flow + j]
+                assert bool(d.Wts) == (tail_stream and npt == 1), (refresh, tail_stream, i, j)
+                for l in range(hp.n_layer):
+                    assert bool(d.Wgs[l]) == (not refresh and int(lib.fwn_gate_stream_bytes(cin)) > 0), (refresh, i, j, l)
+        del pm
+
+
+def test_an_inference_pack_keeps_no_fp32_copy_of_the_parameters():
+    """A model loaded from NumPy holds its packed buffers and its table buffer only: the flat fp32 vector the packing
+    ran over is freed (the fp32 parameters of this model take 26.6 MB, the slack is 1 MB)."""
+    import gc
+    hp = small_hparams(n_block=3, n_flow=2, n_layer=2, num_mels=16)
+    FloWaveNet(hp).init_synthetic()             # the index tables cached per device are allocated once, here
+    gc.collect()
+    torch.cuda.synchronize()
+    before = torch.cuda.memory_allocated()
+    model = FloWaveNet(hp).init_synthetic()
+    gc.collect()
+    torch.cuda.synchronize()
+    grown = torch.cuda.memory_allocated() - before
+    pm = model._packed
+    tables = sum(t.numel() * t.element_size() for t in pm.tensors if t.dtype == torch.float32)
+    assert W.count_params(hp) * 4 > 2 ** 20
+    assert grown <= pm.weight_bytes + tables + 2 ** 20, (grown, pm.weight_bytes, tables)

@@ -668,12 +668,12 @@ def test_two_rank_data_parallel_step_matches_one_process_on_the_whole_batch(tmp_
 
 
 @pytest.mark.parametrize("t", [256, 4096])
-def test_recorded_packing_matches_immediate_packing(t):
-    """Device-resident parameters take the PackPlan path (grouped, transposed packing, refreshed in
-    place every step); NumPy parameters the immediate one: same gradients, also after the
-    parameters changed in place.  t = 4096: 4 096 / 2 048 / 1 024 rows per block - the forward half runs the register-streamed
-    tail (csrc/tail_rs.h, SAVE form), whose fragment-order weights the plan re-packs behind the grouped packing of every
-    refresh (fwn_pack_tail_stream_jobs: all flows in one launch) - a stale or mis-ordered stream would show after the change."""
+def test_reused_engine_matches_fresh_engine(t):
+    """An engine that re-uses its packing plan (device parameters copied into its own flat vector, the plan refreshed in
+    place) gives the gradients of a fresh engine fed NumPy, also after the parameters changed in place.  t = 4096:
+    4 096 / 2 048 / 1 024 rows per block - the forward half runs the register-streamed tail (csrc/tail_rs.h, SAVE form),
+    whose fragment-order weights the plan re-packs behind the grouped packing of every refresh
+    (fwn_pack_tail_stream_jobs: all flows in one launch) - a stale or mis-ordered stream would show after the change."""
     import sys, os
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
     from conftest import small_hparams
@@ -685,9 +685,11 @@ def test_recorded_packing_matches_immediate_packing(t):
     x, c = torch.from_numpy(inp["x"]).reshape(2, t), torch.from_numpy(inp["c"])
     pd = {k: torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)).cuda() for k, v in p.items()}
     eng = GradEngine(hp)
+    plans = []
     for step in range(2):
         l_d, _, _, g_d = eng.loss_and_grads(pd, x, c)
-        assert eng._tp.plan is not None and len(eng._tp.plan.tail_jobs) == hp.n_block * hp.n_flow
+        plans.append(eng._tp.plan)
+        assert len(eng._tp.plan.tail_jobs) == hp.n_block * hp.n_flow
         assert all(d.Wts for d in eng._tp.pm.flow_descs)
         l_n, _, _, g_n = GradEngine(hp).loss_and_grads({k: v.cpu().numpy() for k, v in pd.items()}, x, c)
         assert float(l_d) == float(l_n)
@@ -695,6 +697,78 @@ def test_recorded_packing_matches_immediate_packing(t):
             assert torch.equal(g_d[k].reshape(-1), g_n[k].reshape(-1)), k
         for k, v in pd.items():          # "an optimiser step": every parameter moves, in place
             v.mul_(1.01)
+    assert plans[0] is plans[1]
+
+
+def test_device_side_table_refresh_equals_numpy_tables():
+    """PackPlan.refresh_tables_device (one gather over the flat masters + the up-sampling kernels) reproduces the
+    biases / ActNorm / ZeroConv / up-sampling tables computed here in NumPy after the parameters changed, and the
+    training step's own fp32 tables (bskip, bz, ez) those of the framework expressions they replace."""
+    import sys, os
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    from conftest import small_hparams
+    from tf_flowavenet_amd import packing as PK, weights as W
+    from tf_flowavenet_amd.optim import DataParallelAdam
+    hp = small_hparams(n_block=3, n_flow=2, n_layer=2, hop_size=16, upsample_scales=[4, 4], num_mels=16)
+    L = hp.n_layer
+    opt = DataParallelAdam(hp, W.synthetic_params(hp, 11))
+    tp = TR._TrainPack(opt.master_views(), hp, "cuda")
+    opt.w.add_(torch.randn_like(opt.w) * 0.05)            # "an optimiser step"
+    tp.plan.refresh_tables_device()
+    tbuf = tp.plan._tbuf.clone()
+    P = {k: v.cpu().numpy() for k, v in opt.master_views().items()}
+    f64 = lambda name: np.asarray(P[name], np.float64).reshape(-1)
+    fg, gch = PK.gate_row_channel()
+    acc = PK.acc_k_perm(256).astype(np.int64)
+    got, want = [], []
+
+    def check(ptr, table):
+        off = (ptr - tp.plan._tbuf.data_ptr()) // 4
+        assert 0 <= off and off + table.size <= tbuf.numel()
+        got.append(tbuf[off:off + table.size])
+        want.append(torch.from_numpy(np.ascontiguousarray(table, dtype=np.float32).reshape(-1)).cuda())
+
+    md = tp.pm.model_desc
+    for i in range(hp.n_block):
+        zsn = PK.zero_src_n(i)
+        for j in range(hp.n_flow):
+            d = tp.pm.flow_descs[i * hp.n_flow + j]
+            fp = W.flow_prefix(i, j)
+            wp = fp + "/WaveNet"
+            check(d.bfront, f64(wp + "/Conv_front/bias"))
+            for l in range(L):
+                rp = "%s/ResBlock_%d" % (wp, l)
+                filt = PK.GATE_MUL[0] * (f64(rp + "/Conv_filter/bias") + f64(rp + "/filter_conv_c/bias"))
+                gate = PK.GATE_MUL[1] * (f64(rp + "/Conv_gate/bias") + f64(rp + "/gate_conv_c/bias"))
+                check(d.bgate[l], np.where(fg == 0, filt[gch], gate[gch]))
+                if l + 1 < L:
+                    check(d.bres[l], f64(rp + "/res_conv/bias"))
+            check(d.bskip, sum(f64("%s/ResBlock_%d/skip_conv/bias" % (wp, l)) for l in range(L))[acc])
+            check(d.bfinal, f64(wp + "/Conv_final/bias")[acc])
+            valid = zsn >= 0
+            bzero, ezero = np.zeros(zsn.size), np.ones(zsn.size)
+            bzero[valid] = f64(wp + "/ZeroConv1d/bias")[zsn[valid]]
+            ezero[valid] = np.exp(3.0 * f64(wp + "/ZeroConv1d/scale")[zsn[valid]])
+            check(d.bzero, bzero)
+            check(d.ezero, ezero)
+            check(d.an, PK.actnorm_table(P[fp + "/ActNorm/b"], P[fp + "/ActNorm/logs"], i))
+    for n in range(len(hp.upsample_scales)):
+        check(md.up_w[n], PK.upsample_kernel(P, n)[0])
+    got, want = torch.cat(got), torch.cat(want)
+    diff = (got != want).nonzero().reshape(-1)
+    # float64 exp on the device vs numpy may differ in the last float64 bit: at most a handful of fp32 roundings flip
+    assert diff.numel() <= 4, diff[:10]
+    assert torch.allclose(got, want, rtol=2e-7, atol=0)
+    # the training step's tables: fp32, terms in order (bit-compatible with the framework expressions)
+    mv = opt.master_views()
+    for (i, j), t in tp.flows.items():
+        wp = W.flow_prefix(i, j) + "/WaveNet"
+        bskip = mv["%s/ResBlock_0/skip_conv/bias" % wp].clone()
+        for l in range(1, L):
+            bskip = bskip + mv["%s/ResBlock_%d/skip_conv/bias" % (wp, l)]
+        assert torch.equal(t["bskip"], bskip)
+        assert torch.equal(t["bz"], mv[wp + "/ZeroConv1d/bias"].reshape(-1)[t["zcol"]])
+        assert torch.allclose(t["ez"], torch.exp(3.0 * mv[wp + "/ZeroConv1d/scale"].reshape(-1))[t["zcol"]], rtol=2e-7, atol=0)
 
 
 @pytest.mark.parametrize("m,ti,kx,n,shifts", [(333, 111, 256, 512, (0,)), (6000, 1000, 256, 512, (-1, 0, 1)),
@@ -767,30 +841,6 @@ def test_grouped_weight_gradients_and_weight_norm_backward():
         dv = gg / nrm * (dw - vv * dg / nrm)
         np.testing.assert_allclose(out["dg"].cpu().numpy(), dg, rtol=1e-4, atol=1e-4 * np.abs(dg).max())
         np.testing.assert_allclose(out["dv"].cpu().numpy(), dv, rtol=1e-4, atol=1e-4 * np.abs(dv).max())
-
-
-def test_device_side_table_refresh_equals_the_host_tables():
-    """PackPlan.refresh_tables_device (batched float64 gathers from the flat masters) reproduces the host-computed
-    biases / ActNorm / ZeroConv / up-sampling tables after the parameters changed."""
-    import sys, os
-    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-    from conftest import small_hparams
-    from tf_flowavenet_amd import weights as W
-    from tf_flowavenet_amd.optim import DataParallelAdam
-    hp = small_hparams(n_block=3, n_flow=2, n_layer=2, hop_size=16, upsample_scales=[4, 4], num_mels=16)
-    opt = DataParallelAdam(hp, W.synthetic_params(hp, 11))
-    tp = TR._TrainPack(opt.master_views(), hp, "cuda")
-    assert tp.plan._dev_ready
-    opt.w.add_(torch.randn_like(opt.w) * 0.05)            # "an optimiser step"
-    tp.plan.refresh_tables_device()
-    dev_tables = tp.plan._tbuf.clone()
-    tp.plan.hostview.reset()
-    tp.plan.upload_tables()
-    host_tables = tp.plan._tbuf.clone()
-    diff = (dev_tables != host_tables).nonzero().reshape(-1)
-    # float64 exp on the device vs numpy may differ in the last float64 bit: at most a handful of fp32 roundings flip
-    assert diff.numel() <= 4, diff[:10]
-    assert torch.allclose(dev_tables, host_tables, rtol=2e-7, atol=0)
 
 
 def test_full_size_model_recorded_step_equals_eager_step():

@@ -15,9 +15,8 @@ Replaces, for one process per GPU:
 """
 from __future__ import annotations
 
-import numpy as np
-
-from . import _lib, weights
+from . import _lib
+from .weights import FlatLayout
 
 
 def learning_rate(step: int) -> float:
@@ -29,30 +28,6 @@ def learning_rate(step: int) -> float:
     if step >= 200000:
         return 0.001 / 2
     return 0.001
-
-
-class FlatLayout:
-    """name -> (offset, shape) of every trainable tensor inside one flat fp32 vector, in
-    ``weights.param_shapes`` order, each tensor start aligned to 4 elements (16 bytes)."""
-
-    def __init__(self, hp):
-        self.slots = {}
-        off = 0
-        for name, shape in weights.param_shapes(hp).items():
-            n = int(np.prod(shape))
-            self.slots[name] = (off, tuple(shape), n)
-            off += (n + 3) // 4 * 4
-        self.size = off
-
-    def flatten(self, params):
-        out = np.zeros(self.size, dtype=np.float32)
-        for name, (off, shape, n) in self.slots.items():
-            out[off:off + n] = np.asarray(params[name], dtype=np.float32).reshape(-1)
-        return out
-
-    def views(self, flat):
-        """dict name -> view (torch or numpy) into ``flat`` with the reference's shapes."""
-        return {name: flat[off:off + n].reshape(shape) for name, (off, shape, n) in self.slots.items()}
 
 
 def bucket_bounds(n: int, bucket_elems: int):

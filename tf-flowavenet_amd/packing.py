@@ -10,17 +10,15 @@ Plane algebra (DESIGN.md "Data layout in HBM"):
   * the conditioning half ``c_a`` is a mel-bin half at all phases: natural K index
     ``tau*half + m'`` is logical channel ``m'*2^n + bitrev_n(tau)``.
 
-Everything in this file except ``pack_model`` is pure NumPy and runs without a GPU.
+Everything in this file except ``PackPlan`` and ``pack_model`` is pure NumPy and runs without a GPU.
 """
 from __future__ import annotations
 
 import ctypes as C
-import os
-import math
 
 import numpy as np
 
-from . import _lib
+from . import _lib, weights
 from .weights import FILTER, flow_prefix
 
 GATE_N = 2 * FILTER  # filter + gate output channels
@@ -191,17 +189,19 @@ _IDX_CACHE = {}
 
 
 class PackPlan:
-    """Recorded packing work for parameters that live in device memory at stable addresses (the fp32
-    masters of a training run): ``refresh()`` re-packs every weight with two grouped launches
-    (``fwn_pack_jobs``) and re-uploads the small host-computed tables in one copy, into the same
-    device buffers - the descriptors built at record time stay valid."""
+    """Recorded packing work over parameters that are contiguous views of ONE flat fp32 device vector
+    (``weights.flat_views``): ``refresh()`` re-packs every weight with two grouped launches (``fwn_pack_jobs``) and
+    recomputes every small table with one gather (``fwn_gather_tables``), into device buffers allocated at the first
+    run - the descriptors built at record time stay valid."""
 
-    def __init__(self, dev):
-        self.dev = dev
+    def __init__(self, dev, params):
+        if not weights.is_flat(params, dev):
+            raise ValueError("a PackPlan needs the parameters as contiguous fp32 views of one flat device vector")
+        self.dev, self.params = dev, params
+        self._flat = next(iter(params.values()))._base
         self.sjobs, self.slot, self.jobs = [], {}, []
-        self.tables, self.recipes, self.host_cbs, self.keep = [], [], [], []
-        self._dev_ready = False
-        self.hostview = None
+        self.tables, self.keep = [], []
+        self._tbuf = None
         self._built = False
         self.tail_jobs, self._tail_L = [], 0       # (Wskip, Wfinal, out) of the flows whose tail stream follows the weights
 
@@ -215,7 +215,7 @@ class PackPlan:
             slot = self.slot[key]
         self.jobs.append((v.data_ptr(), src_k.data_ptr(), src_n.data_ptr(), int(out_ptr), int(ld_dst), int(v.shape[2]),
                           int(k_dst), int(n_dst), slot, int(bool(transposed)), float(mul)))
-        self.keep += [v, g, src_k, src_n]
+        self.keep += [src_k, src_n]
         self._built = False
 
     def add_tail_stream(self, wskip_ptr, wfinal_ptr, out_ptr, L):
@@ -225,122 +225,94 @@ class PackPlan:
         self._tail_L = int(L)
         self._built = False
 
-    def table(self, setter, fn, recipe=None):
-        """recipe (optional): how the table follows from the parameters, for the on-device refresh -
-        ``dict(terms=[(param name, index array or -1 per element), ..], post=scalar or array, exp=bool or array)``:
-        table = F(post * sum_t param_t[index_t]) with F = exp where flagged; or ``dict(upsample=n)``."""
-        self.tables.append((setter, fn))
-        self.recipes.append(recipe)
-
-    def enable_device_tables(self, params):
-        """Build the gather tables of the on-device refresh (``refresh_tables_device``).  Needs every table to carry
-        a recipe and every parameter to be a view of ONE flat fp32 device vector (the optimiser's masters)."""
-        import torch
-        self._dev_ready = False
-        if getattr(self, "_tbuf", None) is None or any(r is None for r in self.recipes):
-            return False
-        vals = list(params.values())
-        base = vals[0]._base if isinstance(vals[0], torch.Tensor) else None
-        if base is None or base.dim() != 1 or base.dtype != torch.float32 or any(
-                not isinstance(v, torch.Tensor) or v._base is not base or not v.is_contiguous() for v in vals):
-            return False
-        total = int(self._tbuf.numel())
-        nterm = max(len(r.get("terms", ())) for r in self.recipes)
-        idx = np.full((nterm, total), -1, dtype=np.int64)
-        post = np.ones(total, dtype=np.float64)
-        mode = np.zeros(total, dtype=np.uint8)
-        self._up_jobs = []
-        for (off, size), r in zip(self._toffs, self.recipes):
-            if "upsample" in r:
-                self._up_jobs.append((r["upsample"], off, size))
-                continue
-            for t, (name, ix) in enumerate(r["terms"]):
-                ix = np.broadcast_to(np.asarray(ix, dtype=np.int64).reshape(-1), (size,))
-                idx[t, off:off + size] = np.where(ix >= 0, int(params[name].storage_offset()) + ix, -1)
-            post[off:off + size] = np.broadcast_to(np.asarray(r.get("post", 1.0), dtype=np.float64).reshape(-1), (size,))
-            mode[off:off + size] = np.broadcast_to(np.asarray(r.get("exp", False), dtype=bool).reshape(-1), (size,))
-        dev = self.dev
-        self._flat = base
-        self._didx = torch.from_numpy(np.ascontiguousarray(idx)).to(dev)
-        self._dpost = torch.from_numpy(post).to(dev)
-        self._dmode = torch.from_numpy(mode).to(dev)
-        self._nterm, self._ttotal = nterm, total
-        self._up_params = params
-        self._dev_ready = True
-        return True
-
-    def refresh_tables_device(self):
-        """The small tables recomputed from the masters ON the device: one ``fwn_gather_tables`` launch (fp64 like the
-        host path) + one ``fwn_upsample_wn`` per up-sampling stage, straight into the table buffer the descriptors
-        point at - no device -> host -> device round trip, and the whole refresh can sit in a hipGraph."""
-        import torch
-        lib = _lib.load()
-        st = torch.cuda.current_stream(self.dev).cuda_stream
-        _lib.check(lib.fwn_gather_tables(self._flat.data_ptr(), self._didx.data_ptr(), self._nterm, self._ttotal,
-                                         self._dpost.data_ptr(), self._dmode.data_ptr(), self._tbuf.data_ptr(), st), "fwn_gather_tables")
-        P = self._up_params
-        for n, off, size in self._up_jobs:          # weight-normed up-sampling kernels: v / ||v||_(k) * g per kw column
-            v, g = P["upsample_%d/kernel" % n], P["upsample_%d/g" % n]
-            _lib.check(lib.fwn_upsample_wn(v.data_ptr(), g.data_ptr(), size // 6, self._tbuf[off:].data_ptr(), st), "fwn_upsample_wn")
+    def table(self, setter, shape, recipe):
+        """A small fp32 table of ``shape``; setter(view) is called with its device view at the first run.  recipe: how
+        the table follows from the parameters - ``dict(terms=[(param name, index array or -1 per element), ..],
+        post=scalar or array, exp=bool or array, fp32=bool)``: table = F(post * sum_t param_t[index_t]) with F = exp where
+        flagged, in fp64 rounded once (fp32=True: in fp32, terms added in order); or ``dict(upsample=n)``."""
+        self.tables.append((setter, tuple(shape), recipe))
+        self._built = False
 
     def _build(self):
         import torch
+        dev = self.dev
         sj = (_lib.ScaleJob * max(1, len(self.sjobs)))()
         for i, (v, g, k, n) in enumerate(self.sjobs):
             sj[i].v, sj[i].g, sj[i].k_src, sj[i].n_src = v, g, k, n
         pj = (_lib.PackJob * max(1, len(self.jobs)))()
         # jobs that read the same master back to back (stable sort: the jobs are independent of one another), so that the
         # second reader finds it in the Infinity Cache (pack_jobs_kernel dispatches the jobs in table order)
-        order = sorted(range(len(self.jobs)), key=lambda i: self.jobs[i][0]) if os.environ.get("FWN_PACK_SORT", "1") != "0" else range(len(self.jobs))
+        order = sorted(range(len(self.jobs)), key=lambda i: self.jobs[i][0])
         for i, (v, sk, sn, out, ld, n_src, kd, nd, slot, tr, mul) in enumerate(self.jobs[k] for k in order):
             j = pj[i]
             j.v, j.src_k, j.src_n, j.out, j.ld_dst = v, sk, sn, out, ld
             j.n_src, j.k_dst, j.n_dst, j.scale_slot, j.transposed, j.mul = n_src, kd, nd, slot, tr, mul
-        self._sj = torch.frombuffer(bytearray(bytes(sj)), dtype=torch.uint8).to(self.dev)
-        self._pj = torch.frombuffer(bytearray(bytes(pj)), dtype=torch.uint8).to(self.dev)
-        self._scales = torch.empty(max(1, len(self.sjobs)), 512, dtype=torch.float32, device=self.dev)
+        self._sj = torch.frombuffer(bytearray(bytes(sj)), dtype=torch.uint8).to(dev)
+        self._pj = torch.frombuffer(bytearray(bytes(pj)), dtype=torch.uint8).to(dev)
+        self._scales = torch.empty(max(1, len(self.sjobs)), 512, dtype=torch.float32, device=dev)
         if self.tail_jobs:
             tj = np.asarray(self.tail_jobs, dtype=np.uint64).reshape(-1)
-            self._tj = torch.from_numpy(tj.view(np.int64).copy()).to(self.dev)
+            self._tj = torch.from_numpy(tj.view(np.int64).copy()).to(dev)
+        # the table buffer: every table starts on a 16-byte boundary (float4 loads in the kernels)
+        offs, total = [], 0
+        for _, shape, _ in self.tables:
+            size = int(np.prod(shape))
+            offs.append((total, size))
+            total += (size + 3) // 4 * 4
+        total = max(total, 4)
+        self._tbuf = torch.zeros(total, dtype=torch.float32, device=dev)
+        for (setter, shape, _), (off, size) in zip(self.tables, offs):
+            setter(self._tbuf[off:off + size].view(shape))
+        # the gather: one term row per summand, element i of the buffer reads flat[idx[t][i]]
+        base = int(self._flat.storage_offset())
+        nterm = max([len(r.get("terms", ())) for _, _, r in self.tables] + [1])
+        idx = np.full((nterm, total), -1, dtype=np.int64)
+        post = np.ones(total, dtype=np.float64)
+        mode = np.zeros(total, dtype=np.uint8)
+        self._up_jobs = []
+        for (_, _, r), (off, size) in zip(self.tables, offs):
+            if "upsample" in r:
+                self._up_jobs.append((r["upsample"], off, size))
+                continue
+            for t, (name, ix) in enumerate(r["terms"]):
+                ix = np.broadcast_to(np.asarray(ix, dtype=np.int64).reshape(-1), (size,))
+                idx[t, off:off + size] = np.where(ix >= 0, int(self.params[name].storage_offset()) - base + ix, -1)
+            post[off:off + size] = np.broadcast_to(np.asarray(r.get("post", 1.0), dtype=np.float64).reshape(-1), (size,))
+            mode[off:off + size] = np.broadcast_to(np.asarray(r.get("exp", False), dtype=bool).reshape(-1), (size,)) \
+                + (2 if r.get("fp32") else 0)
+        self._didx = torch.from_numpy(idx).to(dev)
+        self._dpost = torch.from_numpy(post).to(dev)
+        self._dmode = torch.from_numpy(mode).to(dev)
+        self._nterm, self._ttotal = nterm, total
         self._built = True
+
+    def refresh_tables_device(self):
+        """The small tables recomputed from the parameters ON the device: one ``fwn_gather_tables`` launch + one
+        ``fwn_upsample_wn`` per up-sampling stage, straight into the table buffer the descriptors point at - no device
+        -> host -> device round trip, and the whole refresh can sit in a hipGraph."""
+        import torch
+        lib = _lib.load()
+        st = torch.cuda.current_stream(self.dev).cuda_stream
+        _lib.check(lib.fwn_gather_tables(self._flat.data_ptr(), self._didx.data_ptr(), self._nterm, self._ttotal,
+                                         self._dpost.data_ptr(), self._dmode.data_ptr(), self._tbuf.data_ptr(), st), "fwn_gather_tables")
+        P = self.params
+        for n, off, size in self._up_jobs:          # weight-normed up-sampling kernels: v / ||v||_(k) * g per kw column
+            v, g = P["upsample_%d/kernel" % n], P["upsample_%d/g" % n]
+            _lib.check(lib.fwn_upsample_wn(v.data_ptr(), g.data_ptr(), size // 6, self._tbuf[off:].data_ptr(), st), "fwn_upsample_wn")
 
     def run_kernels(self):
         import torch
-        if not self._built:
-            self._build()
         st = torch.cuda.current_stream(self.dev).cuda_stream
         _lib.check(_lib.load().fwn_pack_jobs(self._sj.data_ptr(), len(self.sjobs), self._pj.data_ptr(), len(self.jobs),
                                              self._scales.data_ptr(), 512, st), "fwn_pack_jobs")
         if self.tail_jobs:
             _lib.check(_lib.load().fwn_pack_tail_stream_jobs(self._tj.data_ptr(), len(self.tail_jobs), self._tail_L, st), "fwn_pack_tail_stream_jobs")
 
-    def upload_tables(self):
-        import torch
-        arrs = [np.ascontiguousarray(fn(), dtype=np.float32) for _, fn in self.tables]
-        offs, total = [], 0
-        for a in arrs:
-            offs.append(total)
-            total += (a.size + 3) // 4 * 4
-        host = np.zeros(max(total, 4), dtype=np.float32)
-        for a, off in zip(arrs, offs):
-            host[off:off + a.size] = a.reshape(-1)
-        self._toffs = [(off, a.size) for a, off in zip(arrs, offs)]
-        if getattr(self, "_tbuf", None) is None:
-            self._tbuf = torch.from_numpy(host).to(self.dev)
-            for (setter, _), a, off in zip(self.tables, arrs, offs):
-                setter(self._tbuf[off:off + a.size].view(a.shape))
-        else:
-            self._tbuf.copy_(torch.from_numpy(host))
-        for cb in self.host_cbs:
-            cb()
-
     def refresh(self):
-        """The masters changed: recompute everything that was recorded."""
-        if self._dev_ready:
-            self.refresh_tables_device()
-        else:
-            self.hostview.reset()
-            self.upload_tables()
+        """The parameters changed (or work was recorded since the last run): recompute every table and every packed copy."""
+        if not self._built:
+            self._build()
+        self.refresh_tables_device()
         self.run_kernels()
 
 
@@ -362,12 +334,16 @@ class PackedModel:
         return t
 
 
-def pack_model(params, hp, device="cuda", cond_mode: int = 0, plan: "PackPlan | None" = None,
+def pack_model(params, hp, device="cuda", cond_mode: int = 0, refresh: bool = False,
                gate_fp8: bool = False, persist_mode: int = 0, chain_mode: int = 0, tail_stream: bool = True,
                cond_stream: bool = True) -> PackedModel:
-    """Upload ``params`` (reference layouts, fp32) and run the packing kernels (K10).
-    With ``plan`` (params must then be device tensors at stable addresses) the work is recorded into it
-    and executed once; ``plan.refresh()`` repeats it after the parameters changed."""
+    """Pack ``params`` (reference layouts, fp32; NumPy or device tensors) for the kernels (K10): the work is recorded
+    into a ``PackPlan`` over the parameters as views of one flat fp32 device vector (``weights.flat_views``: the
+    optimiser's masters as they are, anything else copied once) and run once.
+    refresh=False (inference): the fragment-order streams derived from the packed weights - gate (``Wgs``), hoisted
+    conditioning (``cond_stream``) and the fp8 gate - are packed once more and the plan is dropped: the model keeps only
+    its own buffers.  refresh=True (training): none of those streams, and ``pm.plan`` is kept - ``pm.plan.refresh()``
+    repeats the work after the parameters changed in place (their descriptors keep ``tail_kernel`` and the ring gates)."""
     import torch
 
     lib = _lib.load()
@@ -375,6 +351,8 @@ def pack_model(params, hp, device="cuda", cond_mode: int = 0, plan: "PackPlan | 
         raise ValueError("n_layer=%d exceeds FWN_MAX_LAYERS" % hp.n_layer)
     if hp.num_mels % 8:
         raise ValueError("num_mels must be a multiple of 8 (16-byte rows of the mel half planes)")
+    if gate_fp8 and refresh:
+        raise ValueError("the fp8 gate path is inference-only (refresh=False)")
     half = hp.num_mels // 2
     pm = PackedModel(hp, device)
     dev = torch.device(device)
@@ -382,74 +360,15 @@ def pack_model(params, hp, device="cuda", cond_mode: int = 0, plan: "PackPlan | 
         dev = torch.device("cuda", torch.cuda.current_device())
     stream = torch.cuda.current_stream(dev).cuda_stream
     L = hp.n_layer
+    params = weights.flat_views(params, hp, dev)
+    plan = PackPlan(dev, params)
 
     def dev_i32(key, fn):
-        # index tables depend only on (block, num_mels): kept across calls (a training step re-packs
-        # the weights every step)
+        # index tables depend only on (block, num_mels): kept across calls
         gk = (str(dev), hp.num_mels, key)
         if gk not in _IDX_CACHE:
             _IDX_CACHE[gk] = torch.from_numpy(np.ascontiguousarray(fn(), dtype=np.int32)).to(dev)
         return _IDX_CACHE[gk]
-
-    # Small fp32 tables (biases, ActNorm / ZeroConv tables, up-sampling kernels) are gathered on the
-    # host and uploaded in ONE copy at the end; `put(setter, array)` calls setter(view) once the
-    # device copy exists.  Every table starts on a 16-byte boundary (float4 loads in the kernels).
-    pending = []
-
-    def put(setter, fn, recipe=None):
-        """fn() -> the table's current value (re-evaluated by plan.refresh()); recipe: see PackPlan.table."""
-        if plan is not None:
-            plan.table(setter, fn, recipe)
-        else:
-            a = fn()
-            pending.append((setter, np.ascontiguousarray(a, dtype=np.float32).reshape(-1), np.shape(a)))
-
-    def flush_tables():
-        if plan is not None:
-            plan.upload_tables()
-            return
-        offs, total = [], 0
-        for _, a, _ in pending:
-            offs.append(total)
-            total += (a.size + 3) // 4 * 4
-        host = np.zeros(max(total, 4), dtype=np.float32)
-        for (_, a, _), off in zip(pending, offs):
-            host[off:off + a.size] = a
-        buf = pm.keep(torch.from_numpy(host).to(dev))
-        for (setter, a, shape), off in zip(pending, offs):
-            setter(buf[off:off + a.size].view(shape))
-
-    class _HostView(dict):
-        """params may hold device tensors (fp32 masters of optim.DataParallelAdam): the few
-        host-side reductions (bias sums, ActNorm / ZeroConv scale tables) read them through here.
-        All small device tensors come over in ONE copy (a per-tensor .cpu() is a sync each)."""
-        _cache = None
-
-        def reset(self):
-            self._cache = None
-
-        def _fill(self):
-            small = [(k, v) for k, v in params.items() if isinstance(v, torch.Tensor) and v.numel() <= 4096]
-            self._cache = {}
-            if small:
-                flat = torch.cat([v.detach().reshape(-1).to(torch.float32) for _, v in small]).cpu().numpy()
-                off = 0
-                for k, v in small:
-                    n = v.numel()
-                    self._cache[k] = flat[off:off + n].reshape(tuple(v.shape))
-                    off += n
-
-        def __getitem__(self, k):
-            v = params[k]
-            if not isinstance(v, torch.Tensor):
-                return v
-            if self._cache is None:
-                self._fill()
-            return self._cache[k] if k in self._cache else v.detach().cpu().numpy()
-
-    hostp = _HostView()
-    if plan is not None:
-        plan.hostview = hostp
 
     ident256 = dev_i32("id256", lambda: np.arange(FILTER))
     ident768 = dev_i32("id768", lambda: np.arange(3 * FILTER))
@@ -457,9 +376,6 @@ def pack_model(params, hp, device="cuda", cond_mode: int = 0, plan: "PackPlan | 
     accperm_host = acc_k_perm(FILTER).astype(np.int64)
     fg, gch = gate_row_channel()
     gate_rows = [dev_i32("gate_rows%d" % s, lambda s=s: np.where(fg == s, gch, -1)) for s in (0, 1)]
-    scale_buf = torch.empty(FILTER, dtype=torch.float32, device=dev)
-    if gate_fp8 and plan is not None:
-        raise ValueError("the fp8 gate path is inference-only (no PackPlan)")
     # fp8 gate path: per (flow, layer) one e4m3 copy of the gate-packed dilated conv weights + its power-of-two exponent
     fp8_exp = torch.zeros(max(1, hp.n_block * hp.n_flow * L), dtype=torch.int32, device=dev) if gate_fp8 else None
     fp8_amax = torch.zeros_like(fp8_exp, dtype=torch.float32) if gate_fp8 else None
@@ -472,8 +388,7 @@ def pack_model(params, hp, device="cuda", cond_mode: int = 0, plan: "PackPlan | 
         pm.weight_bytes += wd8.numel()
         srcs = []
         for s_, nm in enumerate(("/Conv_filter", "/Conv_gate")):
-            v = torch.as_tensor(params[rp + nm + "/kernel"]).to(device=dev, dtype=torch.float32).contiguous()
-            g = torch.as_tensor(params[rp + nm + "/g"]).to(device=dev, dtype=torch.float32).contiguous()
+            v, g = params[rp + nm + "/kernel"], params[rp + nm + "/g"]
             _lib.check(lib.fwn_wn_scale(v.data_ptr(), g.data_ptr(), 3 * FILTER, FILTER, fp8_scales[s_].data_ptr(), stream), "fwn_wn_scale")
             _lib.check(lib.fwn_wn_absmax(v.data_ptr(), fp8_scales[s_].data_ptr(), 3 * FILTER, FILTER, GATE_MUL[s_],
                                          fp8_amax[slot:].data_ptr(), stream), "fwn_wn_absmax")
@@ -482,53 +397,26 @@ def pack_model(params, hp, device="cuda", cond_mode: int = 0, plan: "PackPlan | 
             _lib.check(lib.fwn_pack_e4m3(v.data_ptr(), fp8_scales[s_].data_ptr(), ident768.data_ptr(), gate_rows[s_].data_ptr(), FILTER,
                                          3 * FILTER, GATE_N, 3 * FILTER, GATE_MUL[s_], fp8_amax[slot:].data_ptr(), wd8.data_ptr(),
                                          fp8_exp[slot:].data_ptr(), stream), "fwn_pack_e4m3")
-            v.record_stream(torch.cuda.current_stream(dev))
         d.Wd8[l] = wd8.data_ptr()
         pm.wd8[slot] = wd8
         fp8_slots.append((d, l, slot))
 
-    def pack(name, src_k, src_n, k_dst, n_dst, out, ld_dst, col_off=0, weight_norm=True, mul=None):
+    def pack(name, src_k, src_n, k_dst, n_dst, out, ld_dst, col_off=0, weight_norm=True, mul=1.0):
         """Pack params[name + '/kernel'] into out[:, col_off: col_off + k_dst]; ``mul`` scales every
         output channel (folded into the weight-norm scale before the bf16 rounding)."""
-        def up(x):
-            if isinstance(x, torch.Tensor):
-                if x.device == dev and x.dtype == torch.float32 and x.is_contiguous():
-                    return x
-                return x.to(device=dev, dtype=torch.float32).contiguous()
-            return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(dev)
-
-        v = up(params[name + "/kernel"])
-        if plan is not None:
-            if v is not params[name + "/kernel"]:
-                raise ValueError("a PackPlan needs contiguous fp32 device parameters (%s)" % name)
-            if mul is not None and not weight_norm:
-                raise ValueError("mul needs weight_norm")
-            plan.add(v, up(params[name + "/g"]) if weight_norm else None, src_k, src_n, k_dst, n_dst,
-                     out.data_ptr() + 2 * col_off, ld_dst, 1.0 if mul is None else mul)
-            return
-        k_src = v.shape[0] * v.shape[1]
-        n_src = v.shape[2]
-        sc = None
-        if weight_norm:
-            g = up(params[name + "/g"])
-            _lib.check(lib.fwn_wn_scale(v.data_ptr(), g.data_ptr(), k_src, n_src, scale_buf.data_ptr(), stream),
-                       "fwn_wn_scale")
-            if mul is not None:
-                scale_buf.mul_(mul)
-            sc = scale_buf.data_ptr()
-        elif mul is not None:
+        if mul != 1.0 and not weight_norm:
             raise ValueError("mul needs weight_norm")
-        _lib.check(lib.fwn_pack_bf16(v.data_ptr(), sc, src_k.data_ptr(), src_n.data_ptr(), n_src, k_dst, n_dst,
-                                     ld_dst, out.data_ptr() + 2 * col_off, stream), "fwn_pack_bf16")
-        # v / g are freed by the caching allocator only after the stream passes this point
-        v.record_stream(torch.cuda.current_stream(dev))
+        plan.add(params[name + "/kernel"], params[name + "/g"] if weight_norm else None, src_k, src_n, k_dst, n_dst,
+                 out.data_ptr() + 2 * col_off, ld_dst, mul)
 
     def bf16_zeros(*shape):
         t = pm.keep(torch.zeros(*shape, dtype=torch.bfloat16, device=dev))
         pm.weight_bytes += t.numel() * 2
         return t
 
-    cond_blocks = []
+    # Small fp32 tables (biases, ActNorm / ZeroConv tables, up-sampling kernels): each one a gather recipe over the
+    # parameters (PackPlan.table), evaluated on the device into one buffer.
+    cond_blocks, gate_streams = [], []
     for i in range(hp.n_block):
         ch = 1 << i
         cin = half * (2 << i)
@@ -540,7 +428,7 @@ def pack_model(params, hp, device="cuda", cond_mode: int = 0, plan: "PackPlan | 
         z_src_n = dev_i32(("zero", i), lambda: zero_src_n(i))
         zsn_host = zero_src_n(i)
         wc_blk = bf16_zeros(hp.n_flow, L, GATE_N, kcpad)     # contiguous: hoisted conditioning
-        cond_blocks.append((i, wc_blk, cin, kcpad))
+        cond_blocks.append((i, wc_blk, kcpad))
         for j in range(hp.n_flow):
             fp = flow_prefix(i, j)
             wp = fp + "/WaveNet"
@@ -566,8 +454,8 @@ def pack_model(params, hp, device="cuda", cond_mode: int = 0, plan: "PackPlan | 
                 wfront3 = bf16_zeros(FILTER, kf3)
                 pack(wp + "/Conv_front", f3, ident256, kf3, FILTER, wfront3, kf3)
                 d.Wfront3, d.kf3 = wfront3.data_ptr(), kf3
-            put(lambda v, d=d: setattr(d, "bfront", v.data_ptr()), lambda wp=wp: hostp[wp + "/Conv_front/bias"],
-                dict(terms=[(wp + "/Conv_front/bias", np.arange(FILTER))]))
+            plan.table(lambda v, d=d: setattr(d, "bfront", v.data_ptr()), (FILTER,),
+                       dict(terms=[(wp + "/Conv_front/bias", np.arange(FILTER))]))
 
             wskip = bf16_zeros(FILTER, L * FILTER)
             for l in range(L):
@@ -580,115 +468,94 @@ def pack_model(params, hp, device="cuda", cond_mode: int = 0, plan: "PackPlan | 
                 wc = wc_blk[j, l]
                 pack(rp + "/filter_conv_c", c_src_k, gate_rows[0], kcpad, GATE_N, wc, kcpad, mul=GATE_MUL[0])
                 pack(rp + "/gate_conv_c", c_src_k, gate_rows[1], kcpad, GATE_N, wc, kcpad, mul=GATE_MUL[1])
-                def gate_bias(rp=rp):
-                    bsum = [GATE_MUL[0] * (np.asarray(hostp[rp + "/Conv_filter/bias"], np.float64)
-                                           + np.asarray(hostp[rp + "/filter_conv_c/bias"], np.float64)),
-                            GATE_MUL[1] * (np.asarray(hostp[rp + "/Conv_gate/bias"], np.float64)
-                                           + np.asarray(hostp[rp + "/gate_conv_c/bias"], np.float64))]
-                    return np.where(fg == 0, bsum[0][gch], bsum[1][gch])
                 d.Wd[l] = wd.data_ptr()
                 d.Wc[l] = wc.data_ptr()
-                # the same operands in MFMA-fragment order for the register-streamed gate kernel (csrc/gate_rs.h): packed
-                # once, so only without a PackPlan (a plan re-packs Wd / Wc every training step, whose forward pass keeps
-                # the training gate kernel anyway)
-                gs_bytes = int(lib.fwn_gate_stream_bytes(cin)) if plan is None else 0
-                if gs_bytes:
-                    wgs = pm.keep(torch.empty(gs_bytes, dtype=torch.uint8, device=dev))
-                    pm.weight_bytes += gs_bytes
-                    _lib.check(lib.fwn_pack_gate_stream(wd.data_ptr(), wc.data_ptr(), cin, kcpad, wgs.data_ptr(), stream),
-                               "fwn_pack_gate_stream")
-                    d.Wgs[l] = wgs.data_ptr()
+                gate_streams.append((d, l, wd, wc, cin, kcpad))
                 if gate_fp8:
                     pack_gate_fp8(rp, d, l, (i * hp.n_flow + j) * L + l)
-                put(lambda v, d=d, l=l: d.bgate.__setitem__(l, v.data_ptr()), gate_bias,
-                    dict(terms=[(rp + "/Conv_filter/bias", np.where(fg == 0, gch, -1)), (rp + "/filter_conv_c/bias", np.where(fg == 0, gch, -1)),
-                                (rp + "/Conv_gate/bias", np.where(fg == 0, -1, gch)), (rp + "/gate_conv_c/bias", np.where(fg == 0, -1, gch))],
-                         post=np.where(fg == 0, GATE_MUL[0], GATE_MUL[1])))
+                plan.table(lambda v, d=d, l=l: d.bgate.__setitem__(l, v.data_ptr()), (GATE_N,),
+                           dict(terms=[(rp + "/Conv_filter/bias", np.where(fg == 0, gch, -1)), (rp + "/filter_conv_c/bias", np.where(fg == 0, gch, -1)),
+                                       (rp + "/Conv_gate/bias", np.where(fg == 0, -1, gch)), (rp + "/gate_conv_c/bias", np.where(fg == 0, -1, gch))],
+                                post=np.where(fg == 0, GATE_MUL[0], GATE_MUL[1])))
                 if l + 1 < L:   # the last layer's res_conv is dead (modules.py:126-128,175-176)
                     wr = bf16_zeros(FILTER, FILTER)
                     pack(rp + "/res_conv", ident256, ident256, FILTER, FILTER, wr, FILTER)
                     d.Wres[l] = wr.data_ptr()
-                    put(lambda v, d=d, l=l: d.bres.__setitem__(l, v.data_ptr()), lambda rp=rp: hostp[rp + "/res_conv/bias"],
-                        dict(terms=[(rp + "/res_conv/bias", np.arange(FILTER))]))
+                    plan.table(lambda v, d=d, l=l: d.bres.__setitem__(l, v.data_ptr()), (FILTER,),
+                               dict(terms=[(rp + "/res_conv/bias", np.arange(FILTER))]))
                 # rows (output channels) in accumulator order: S leaves the tail's MFMA chain in natural channel order
                 pack(rp + "/skip_conv", ident256, accperm, FILTER, FILTER, wskip, L * FILTER, col_off=l * FILTER)
             d.Wskip = wskip.data_ptr()
-            put(lambda v, d=d: setattr(d, "bskip", v.data_ptr()),
-                lambda wp=wp: sum(np.asarray(hostp["%s/ResBlock_%d/skip_conv/bias" % (wp, l)], np.float64).reshape(-1) for l in range(L))[accperm_host],
-                dict(terms=[("%s/ResBlock_%d/skip_conv/bias" % (wp, l), accperm_host) for l in range(L)]))
+            plan.table(lambda v, d=d: setattr(d, "bskip", v.data_ptr()), (FILTER,),
+                       dict(terms=[("%s/ResBlock_%d/skip_conv/bias" % (wp, l), accperm_host) for l in range(L)]))
 
             wfin = bf16_zeros(FILTER, FILTER)
             pack(wp + "/Conv_final", ident256, accperm, FILTER, FILTER, wfin, FILTER)
             d.Wfinal = wfin.data_ptr()
             # Wskip | Wfinal once more in MFMA-fragment order for the register-streamed tail (csrc/tail_rs.h): one ZeroConv pair
-            # tile only.  Under a PackPlan (training: the weights are re-packed every step) the streams are re-packed too, all in one launch
+            # tile only; re-packed behind the grouped weight packing of every run, all flows in one launch
             ts_bytes = int(lib.fwn_tail_stream_bytes(L)) if (npt == 1 and tail_stream) else 0
             if ts_bytes:
                 wts = pm.keep(torch.empty(ts_bytes, dtype=torch.uint8, device=dev))
                 pm.weight_bytes += ts_bytes
-                if plan is None:
-                    _lib.check(lib.fwn_pack_tail_stream(wskip.data_ptr(), wfin.data_ptr(), L, wts.data_ptr(), stream), "fwn_pack_tail_stream")
-                else:       # re-packed behind every grouped weight packing, all flows in one launch (PackPlan.run_kernels)
-                    plan.add_tail_stream(wskip.data_ptr(), wfin.data_ptr(), wts.data_ptr(), L)
+                plan.add_tail_stream(wskip.data_ptr(), wfin.data_ptr(), wts.data_ptr(), L)
                 d.Wts = wts.data_ptr()
-            put(lambda v, d=d: setattr(d, "bfinal", v.data_ptr()), lambda wp=wp: np.asarray(hostp[wp + "/Conv_final/bias"]).reshape(-1)[accperm_host],
-                dict(terms=[(wp + "/Conv_final/bias", accperm_host)]))
+            plan.table(lambda v, d=d: setattr(d, "bfinal", v.data_ptr()), (FILTER,),
+                       dict(terms=[(wp + "/Conv_final/bias", accperm_host)]))
 
             wz = bf16_zeros(npt * 64, FILTER)
             pack(wp + "/ZeroConv1d", ident256, z_src_n, FILTER, npt * 64, wz, FILTER, weight_norm=False)
-            def zero_tables(which, wp=wp, zsn_host=zsn_host, npt=npt):
-                valid = zsn_host >= 0
-                if which == 0:
-                    zb = np.asarray(hostp[wp + "/ZeroConv1d/bias"], np.float64).reshape(-1)
-                    out = np.zeros(npt * 64)
-                    out[valid] = zb[zsn_host[valid]]
-                else:
-                    zs = np.asarray(hostp[wp + "/ZeroConv1d/scale"], np.float64).reshape(-1)
-                    out = np.ones(npt * 64)
-                    out[valid] = np.exp(3.0 * zs[zsn_host[valid]])
-                return out
             d.Wzero = wz.data_ptr()
-            zidx = np.where(zsn_host >= 0, zsn_host, -1)
-            put(lambda v, d=d: setattr(d, "bzero", v.data_ptr()), lambda f=zero_tables: f(0),
-                dict(terms=[(wp + "/ZeroConv1d/bias", zidx)]))
-            put(lambda v, d=d: setattr(d, "ezero", v.data_ptr()), lambda f=zero_tables: f(1),
-                dict(terms=[(wp + "/ZeroConv1d/scale", zidx)], post=3.0, exp=True))
+            # pad rows: bias 0, scale exp(0) = 1
+            plan.table(lambda v, d=d: setattr(d, "bzero", v.data_ptr()), (npt * 64,),
+                       dict(terms=[(wp + "/ZeroConv1d/bias", zsn_host)]))
+            plan.table(lambda v, d=d: setattr(d, "ezero", v.data_ptr()), (npt * 64,),
+                       dict(terms=[(wp + "/ZeroConv1d/scale", zsn_host)], post=3.0, exp=True))
 
             def set_an(v, d=d, key=(i, j)):
                 pm.an[key] = v
                 d.an = v.data_ptr()
+            # actnorm_table: rows (shift, scale, 1/scale, 3*logs)
             an_idx = np.concatenate([r * ch + bitrev_table(i).astype(np.int64) for r in range(2)]).reshape(2, 1, ch)
             rows = np.arange(4).reshape(1, 4, 1)
-            put(set_an, lambda fp=fp, i=i: actnorm_table(hostp[fp + "/ActNorm/b"], hostp[fp + "/ActNorm/logs"], i),
-                dict(terms=[(fp + "/ActNorm/b", np.where(rows == 0, an_idx, -1)), (fp + "/ActNorm/logs", np.where(rows == 0, -1, an_idx))],
-                     post=np.broadcast_to(np.array([1.0, 3.0, -3.0, 3.0]).reshape(1, 4, 1), (2, 4, ch)),
-                     exp=np.broadcast_to((rows == 1) | (rows == 2), (2, 4, ch))))
+            plan.table(set_an, (2, 4, ch),
+                       dict(terms=[(fp + "/ActNorm/b", np.where(rows == 0, an_idx, -1)), (fp + "/ActNorm/logs", np.where(rows == 0, -1, an_idx))],
+                            post=np.broadcast_to(np.array([1.0, 3.0, -3.0, 3.0]).reshape(1, 4, 1), (2, 4, ch)),
+                            exp=np.broadcast_to((rows == 1) | (rows == 2), (2, 4, ch))))
 
     md = pm.model_desc
-    # the hoisted conditioning's weights once more in MFMA-fragment order (csrc/cond_rs.h): blocks whose conditioning can be
-    # hoisted and the streamed kernel is the faster form (K >= 640), packed once - so only without a PackPlan, like the gate's and the tail's streams
-    for i, wc_blk, cin, kcpad in cond_blocks:
-        cs_bytes = int(lib.fwn_cond_stream_bytes(kcpad)) if (plan is None and cond_stream and kcpad >= 640 and i < 16) else 0
-        if cs_bytes:
-            nz = hp.n_flow * L
-            wcs = pm.keep(torch.empty(nz * cs_bytes, dtype=torch.uint8, device=dev))
-            pm.weight_bytes += nz * cs_bytes
-            _lib.check(lib.fwn_pack_cond_stream(wc_blk.data_ptr(), GATE_N * kcpad, kcpad, nz, wcs.data_ptr(), stream), "fwn_pack_cond_stream")
-            md.cond_stream[i] = wcs.data_ptr()
     md.n_block, md.n_flow, md.n_layer, md.num_mels = hp.n_block, hp.n_flow, L, hp.num_mels
     md.n_up = len(hp.upsample_scales)
     if md.n_up > _lib.FWN_MAX_UPSAMPLE:
         raise ValueError("too many upsample stages")
     for n, s in enumerate(hp.upsample_scales):
         md.up_scale[n] = int(s)
-        put(lambda v, n=n: md.up_w.__setitem__(n, v.data_ptr()), lambda n=n: upsample_kernel(hostp, n)[0], dict(upsample=n))
-        md.up_bias[n] = upsample_kernel(hostp, n)[1]
-        if plan is not None:
-            plan.host_cbs.append(lambda n=n: md.up_bias.__setitem__(n, upsample_kernel(hostp, n)[1]))
-    flush_tables()
-    if plan is not None:
-        plan.run_kernels()
+        plan.table(lambda v, n=n: md.up_w.__setitem__(n, v.data_ptr()), (2 * int(s), 3), dict(upsample=n))
+        md.up_bias[n] = float(params["upsample_%d/bias" % n].reshape(-1)[0])
+    plan.refresh()
+    if refresh:
         pm.plan = plan
+    else:
+        pm.keep(plan._tbuf)
+        # the same operands once more in MFMA-fragment order, from the packed copies: the register-streamed gate
+        # (csrc/gate_rs.h, where the kernel has a form for cin) and the hoisted conditioning (csrc/cond_rs.h, blocks whose
+        # conditioning can be hoisted and the streamed kernel is the faster form, K >= 640)
+        for d, l, wd, wc, cin, kcpad in gate_streams:
+            gs_bytes = int(lib.fwn_gate_stream_bytes(cin))
+            if gs_bytes:
+                wgs = pm.keep(torch.empty(gs_bytes, dtype=torch.uint8, device=dev))
+                pm.weight_bytes += gs_bytes
+                _lib.check(lib.fwn_pack_gate_stream(wd.data_ptr(), wc.data_ptr(), cin, kcpad, wgs.data_ptr(), stream),
+                           "fwn_pack_gate_stream")
+                d.Wgs[l] = wgs.data_ptr()
+        for i, wc_blk, kcpad in cond_blocks:
+            cs_bytes = int(lib.fwn_cond_stream_bytes(kcpad)) if (cond_stream and kcpad >= 640 and i < 16) else 0
+            if cs_bytes:
+                nz = hp.n_flow * L
+                wcs = pm.keep(torch.empty(nz * cs_bytes, dtype=torch.uint8, device=dev))
+                pm.weight_bytes += nz * cs_bytes
+                _lib.check(lib.fwn_pack_cond_stream(wc_blk.data_ptr(), GATE_N * kcpad, kcpad, nz, wcs.data_ptr(), stream), "fwn_pack_cond_stream")
+                md.cond_stream[i] = wcs.data_ptr()
     md.flows = C.cast(pm.flow_descs, C.POINTER(_lib.FlowDesc))
     md.cond_mode = int(cond_mode)
     # fwn.h chain_mode: 1 runs every flow on its own like round 2 (same-box A/B, tests); an argument, not a process variable

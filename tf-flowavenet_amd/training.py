@@ -224,7 +224,7 @@ def weight_grad(x, dy, m, kx, n, *, shifts=(0,), ti=0, nsplit=None):
 # Loss and gradients of the whole model (train.py:56-66: loss = -(log_p + logdet)): ONE C call per batch,
 # fwn_train_loss_and_grads (csrc/train_api.hip sequences the training forward and the backward over the stage
 # kernels).  What stays here is parameter-side: the packed bf16 copies the GEMMs read (_TrainPack, refreshed from the
-# fp32 masters every step by two grouped packing launches) and the descriptors that tell the C side where masters,
+# fp32 masters every step by one gather and the grouped packing launches) and the descriptors that tell the C side where masters,
 # copies and gradients live.
 # =============================================================================================
 import numpy as np
@@ -235,7 +235,8 @@ SQH = float(np.sqrt(0.5))
 
 
 class _TrainPack:
-    """Inference packing plus the natural-order / transposed bf16 copies the backward GEMMs read."""
+    """Inference packing plus the natural-order / transposed bf16 copies the backward GEMMs read, all recorded into
+    one ``packing.PackPlan`` over the flat fp32 masters and refreshed from them every step."""
 
     def __init__(self, params, hp, device):
         import torch
@@ -244,15 +245,9 @@ class _TrainPack:
             self.dev = torch.device("cuda", torch.cuda.current_device())
         self.lib = _lib.load()
         self.params = params
-        # parameters that are contiguous fp32 device tensors (the masters of a training run) have
-        # stable addresses: record the packing once (packing.PackPlan) and refresh() it every step
-        stable = all(isinstance(v, torch.Tensor) and v.device == self.dev and v.dtype == torch.float32 and v.is_contiguous()
-                     for v in params.values())
-        self.plan = packing.PackPlan(self.dev) if stable else None
-        self.pm = packing.pack_model(params, hp, device, cond_mode=1, plan=self.plan)
+        self.pm = packing.pack_model(params, hp, self.dev, cond_mode=1, refresh=True)
+        self.plan = self.pm.plan
         self.flows = {}
-        self._idx = {}
-        self._scale = torch.empty(512, dtype=torch.float32, device=self.dev)
         self.br = [self._i64(("br", i), packing.bitrev_table(i)) for i in range(hp.n_block)]
         half_ = hp.num_mels // 2
         # logical row of a weight gradient -> row of the GEMM that computed it in device channel order
@@ -265,93 +260,16 @@ class _TrainPack:
                        for i in range(hp.n_block)]
         for i in range(hp.n_block):
             for j in range(hp.n_flow):
-                self.flows[(i, j)] = self._pack_flow_plan(i, j) if stable else self._pack_flow(i, j)
-        if stable:
-            self.plan.run_kernels()
-            self.plan.enable_device_tables(params)      # masters in one flat vector: the small tables refresh on the device
-        self._small_tables()
+                self.flows[(i, j)] = self._pack_flow_plan(i, j)
+        self.plan.refresh()
 
     def refresh(self):
         """The masters changed (an optimiser step): re-pack everything into the same buffers."""
         self.plan.refresh()
-        self._small_tables()
-
-    def _small_tables(self):
-        """Per-flow bias / scale vectors in device channel order (parameter-sized; the backward reads ez).  With the
-        masters in one flat vector all flows are done by a handful of batched gathers (``_batched_tables``)."""
-        import torch
-        hp = self.hp
-        if self.plan is not None and self.plan._dev_ready:
-            return self._batched_tables()
-        for (i, j), t in self.flows.items():
-            wp = weights.flow_prefix(i, j) + "/WaveNet"
-            t["bskip"] = sum(self._f32("%s/ResBlock_%d/skip_conv/bias" % (wp, l)) for l in range(hp.n_layer))
-            t["bfin"] = self._f32(wp + "/Conv_final/bias")
-            t["bz"] = self._f32(wp + "/ZeroConv1d/bias").reshape(-1)[t["zcol"]].contiguous()
-            t["ez"] = torch.exp(3.0 * self._f32(wp + "/ZeroConv1d/scale").reshape(-1))[t["zcol"]].contiguous()
-        self.an_logdet = None
-
-    def _batched_tables(self):
-        """bskip (sum of the layers' skip biases), bz, ez = exp(3 scale) of every flow and the parameter-only part of
-        logdet, sum over flows of mean_C(3 logs) (model.py:86-94): ONE ``fwn_gather_tables`` launch over the flat
-        masters (fp32 arithmetic, the order of the framework expressions it replaced) + ``fwn_sum_f32``, into buffers
-        allocated once (the descriptors of the C step keep pointing at them)."""
-        import torch
-        hp, P = self.hp, self.params
-        flat = self.plan._flat
-        lib = self.lib
-        if getattr(self, "_bt", None) is None:          # gather tables into the flat master vector, built once
-            off = lambda name: int(P[name].storage_offset())
-            L = hp.n_layer
-            skip = [[] for _ in range(L)]
-            bz, ez, an3, anw, spans = [], [], [], [], {}
-            zpos = 0
-            for (i, j), t in self.flows.items():
-                wp = weights.flow_prefix(i, j) + "/WaveNet"
-                for l in range(L):
-                    skip[l].append(off("%s/ResBlock_%d/skip_conv/bias" % (wp, l)) + np.arange(256))
-                zc = t["zcol"].cpu().numpy()
-                bz.append(off(wp + "/ZeroConv1d/bias") + zc)
-                ez.append(off(wp + "/ZeroConv1d/scale") + zc)
-                an3.append(off(weights.flow_prefix(i, j) + "/ActNorm/logs") + np.arange(2 << i))
-                anw.append(np.full(2 << i, 3.0 / (2 << i)))          # sum over both planes of mean_C(3 logs)
-                spans[(i, j)] = (zpos, zpos + len(zc))
-                zpos += len(zc)
-            skip = [np.concatenate(a) for a in skip]
-            bz, ez, an3, anw = np.concatenate(bz), np.concatenate(ez), np.concatenate(an3), np.concatenate(anw)
-            n_s, n_z, n_a = len(skip[0]), len(bz), len(an3)
-            total = n_s + 2 * n_z + n_a
-            idx = np.full((L, total), -1, dtype=np.int64)
-            for l in range(L):
-                idx[l, :n_s] = skip[l]
-            idx[0, n_s:n_s + n_z] = bz
-            idx[0, n_s + n_z:n_s + 2 * n_z] = ez
-            idx[0, n_s + 2 * n_z:] = an3
-            post = np.ones(total)
-            post[n_s + n_z:n_s + 2 * n_z] = 3.0
-            post[n_s + 2 * n_z:] = anw
-            mode = np.full(total, 2, dtype=np.uint8)
-            mode[n_s + n_z:n_s + 2 * n_z] = 3
-            out = torch.empty(total, dtype=torch.float32, device=self.dev)
-            self._bt = dict(idx=torch.from_numpy(idx).to(self.dev), post=torch.from_numpy(post).to(self.dev),
-                            mode=torch.from_numpy(mode).to(self.dev), out=out, L=L, total=total, spans=spans,
-                            bskip=out[:n_s], bz=out[n_s:n_s + n_z], ez=out[n_s + n_z:n_s + 2 * n_z], anp=out[n_s + 2 * n_z:],
-                            an_logdet=torch.empty(1, dtype=torch.float32, device=self.dev))
-            for f, ((i, j), t) in enumerate(self.flows.items()):
-                wp = weights.flow_prefix(i, j) + "/WaveNet"
-                lo, hi = spans[(i, j)]
-                t["bskip"] = self._bt["bskip"][f * 256:(f + 1) * 256]
-                t["bfin"] = self._f32(wp + "/Conv_final/bias")
-                t["bz"], t["ez"] = self._bt["bz"][lo:hi], self._bt["ez"][lo:hi]
-        bt = self._bt
-        st = _stream(flat)
-        _lib.check(lib.fwn_gather_tables(flat.data_ptr(), bt["idx"].data_ptr(), bt["L"], bt["total"], bt["post"].data_ptr(),
-                                         bt["mode"].data_ptr(), bt["out"].data_ptr(), st), "fwn_gather_tables")
-        self.an_logdet = None       # (unused since the forward half runs the inference tail: its log-det partials carry the ActNorm terms)
 
     def _pack_flow_plan(self, i, j):
-        """The backward's transposed / natural-order copies as jobs of the plan (transposed packing:
-        no separate transposes)."""
+        """The backward's transposed copies as jobs of the plan (transposed packing: no separate transposes) and its
+        per-flow tables as gather recipes."""
         import torch
         hp, dev, plan = self.hp, self.dev, self.plan
         ch, half, L = 1 << i, hp.num_mels // 2, hp.n_layer
@@ -407,6 +325,12 @@ class _TrainPack:
         t["ldz"] = max(8, n2)
         t["WzT"] = bz(256, t["ldz"])
         job(wp + "/ZeroConv1d", id256, 256, zc32, n2, t["WzT"], 0, True, weight_norm=False)
+        # per-flow bias / scale vectors in device channel order (the backward reads ez), in fp32 with the terms in order
+        t["bfin"] = P[wp + "/Conv_final/bias"]
+        plan.table(lambda v: t.__setitem__("bskip", v), (256,),
+                   dict(terms=[("%s/ResBlock_%d/skip_conv/bias" % (wp, l), np.arange(256)) for l in range(L)], fp32=True))
+        plan.table(lambda v: t.__setitem__("bz", v), (n2,), dict(terms=[(wp + "/ZeroConv1d/bias", zcol)], fp32=True))
+        plan.table(lambda v: t.__setitem__("ez", v), (n2,), dict(terms=[(wp + "/ZeroConv1d/scale", zcol)], post=3.0, exp=True, fp32=True))
         return t
 
     def _i32(self, key, arr):
@@ -424,92 +348,16 @@ class _TrainPack:
         return packing._IDX_CACHE[gk]
 
     def _f32(self, name):
-        import torch
-        v = self.params[name]
-        if isinstance(v, torch.Tensor):
-            if v.device == self.dev and v.dtype == torch.float32 and v.is_contiguous():
-                return v
-            return v.to(device=self.dev, dtype=torch.float32).contiguous()
-        return torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)).to(self.dev)
-
-    def _pack(self, name, src_k, src_n, k_dst, n_dst, out, weight_norm=True):
-        import torch
-        v = self._f32(name + "/kernel")
-        k_src, n_src = v.shape[0] * v.shape[1], v.shape[2]
-        st = _stream(v)
-        sc = None
-        if weight_norm:
-            g = self._f32(name + "/g")
-            _lib.check(self.lib.fwn_wn_scale(v.data_ptr(), g.data_ptr(), k_src, n_src, self._scale.data_ptr(), st), "fwn_wn_scale")
-            sc = self._scale.data_ptr()
-        _lib.check(self.lib.fwn_pack_bf16(v.data_ptr(), sc, src_k.data_ptr(), src_n.data_ptr(), n_src, k_dst, n_dst,
-                                          int(out.stride(0)), out.data_ptr(), st), "fwn_pack_bf16")
-
-    def _pack_flow(self, i, j):
-        import torch
-        hp, dev = self.hp, self.dev
-        ch, half, L = 1 << i, hp.num_mels // 2, hp.n_layer
-        cin = half * (2 << i)
-        kcpad = packing.roundup(cin, 64)
-        wp = weights.flow_prefix(i, j) + "/WaveNet"
-        bz = lambda *s: torch.zeros(*s, dtype=torch.bfloat16, device=dev)
-        id256 = self._i32("id256", np.arange(256))
-        id768 = self._i32("id768", np.arange(768))
-        rows_f = self._i32("rows_f", np.concatenate([np.arange(256), np.full(256, -1)]))
-        rows_g = self._i32("rows_g", np.concatenate([np.full(256, -1), np.arange(256)]))
-        csrc = self._i32(("csrc", i), packing.cond_src_k(i, half))
-        br = packing.bitrev_table(i).astype(np.int64)
-        t = {}
-        # front: K = tap*Ch + tau (plane order)
-        fk = packing.front_src_k(i)[:3 * ch]
-        wf = bz(256, packing.roundup(3 * ch, 8))
-        self._pack(wp + "/Conv_front", self._i32(("fk", i), np.concatenate([fk, np.full(wf.shape[1] - 3 * ch, -1)])), id256,
-                   wf.shape[1], 256, wf)
-        wft = transpose_shift(wf, 256, 3 * ch, ld_dst=256)                      # [3Ch][256]
-        t["WfT"] = wft.view(3, ch, 256).permute(1, 0, 2).reshape(ch, 768).contiguous()       # [Ch][tap*256 + n]
-        t["Wd"], t["WdT"], t["Wc"], t["WcT"], t["WresT"], t["WskipT"] = [], [], [], [], [], []
-        for l in range(L):
-            rp = "%s/ResBlock_%d" % (wp, l)
-            wd = bz(512, 768)
-            self._pack(rp + "/Conv_filter", id768, rows_f, 768, 512, wd)
-            self._pack(rp + "/Conv_gate", id768, rows_g, 768, 512, wd)
-            wdt = transpose_shift(wd, 512, 768, ld_dst=512)                     # [768][512]
-            t["WdT"].append(wdt.view(3, 256, 512).permute(1, 0, 2).reshape(256, 1536).contiguous())
-            wc = bz(512, kcpad)
-            self._pack(rp + "/filter_conv_c", csrc, rows_f, kcpad, 512, wc)
-            self._pack(rp + "/gate_conv_c", csrc, rows_g, kcpad, 512, wc)
-            if l == 0:
-                t["WcT_all"] = bz(cin, L * 512)
-            t["WcT_all"][:, l * 512:(l + 1) * 512] = transpose_shift(wc, 512, cin, ld_dst=512)            # [cin][512] of layer l
-            t["WcT"].append(t["WcT_all"][:, l * 512:(l + 1) * 512])
-            if l + 1 < L:
-                wr = bz(256, 256)
-                self._pack(rp + "/res_conv", id256, id256, 256, 256, wr)
-                t["WresT"].append(transpose_shift(wr, 256, 256, ld_dst=256))
-            ws = bz(256, 256)
-            self._pack(rp + "/skip_conv", id256, id256, 256, 256, ws)
-            t["WskipT"].append(transpose_shift(ws, 256, 256, ld_dst=256))
-        t["WskipT_all"] = torch.cat(t["WskipT"], 0).contiguous()
-        wfin = bz(256, 256)
-        self._pack(wp + "/Conv_final", id256, id256, 256, 256, wfin)
-        t["WfinT"] = transpose_shift(wfin, 256, 256, ld_dst=256)
-        # ZeroConv rows in plane order: row fg*Ch + tau serves logical channel fg*Ch + bitrev(tau)
-        zcol = np.concatenate([br, ch + br])
-        t["zcol"] = self._i64(("zcol", i), zcol)
-        t["zinv32"] = self._i32(("zinv", i), np.argsort(zcol))
-        n2 = 2 * ch
-        ldz = max(8, n2)
-        wz = bz(n2, 256)
-        self._pack(wp + "/ZeroConv1d", id256, self._i32(("zcol", i), zcol), 256, n2, wz, weight_norm=False)
-        t["WzT"] = transpose_shift(wz, n2, 256, ld_dst=packing.roundup(n2, 64))[:, :ldz].contiguous()   # [256][ldz], zero padded
-        t["ldz"] = ldz
-        return t
+        """The fp32 device master of parameter ``name`` (a view of the flat vector the plan reads)."""
+        return self.params[name]
 
 
 class GradEngine:
     """``loss_and_grads(params, x, c)``: one training forward + backward on the current device.
 
-    params: dict name -> fp32 array / tensor in the reference's layouts (``weights.param_shapes``).
+    params: dict name -> fp32 array / tensor in the reference's layouts (``weights.param_shapes``); views of one flat
+    fp32 device vector (the optimiser's masters) are read in place, anything else is copied into a flat vector the
+    engine owns, on every call.
     Returns ``(loss, log_p, logdet, grads)`` with grads a dict name -> fp32 device tensor of the
     parameter's shape (``d loss / d param``, loss = -(log_p + logdet), train.py:60)."""
 
@@ -520,22 +368,9 @@ class GradEngine:
         self.lib = _lib.load()
         self._gout = None
         self._on_block = None
-        # True: the caller refreshes the host-computed tables itself (``refresh_host_tables``) - a recorded
-        # step keeps that device -> host -> device round trip outside its hipGraph
-        self.external_host_tables = False
+        self._own_flat = None
         # True: no consumer of a block's gradients before the end of the call (fwn_train_desc.defer_block_done; slower, see _run)
         self.defer_block_done = False
-
-    def refresh_host_tables(self):
-        """Host-computed small tables (only when the parameters are not views of one flat device vector: then
-        ``PackPlan.refresh_tables_device`` does it inside the step)."""
-        tp = getattr(self, "_tp", None)
-        if tp is None or tp.plan is None:
-            raise RuntimeError("no recorded packing plan: run one eager step on device-resident parameters first")
-        if tp.plan._dev_ready:
-            return
-        tp.plan.hostview.reset()
-        tp.plan.upload_tables()
 
     # ------------------------------------------------------------------ helpers
     def _side_stream(self, dev):
@@ -575,19 +410,17 @@ class GradEngine:
         _STREAMS.clear()
         _STREAMS[torch.zeros(0, device=dev).device] = st
         shp = self._shapes = weights.param_shapes(hp)
-        key = tuple(v.data_ptr() for v in list(params.values())[:4]) if all(hasattr(v, "data_ptr") for v in list(params.values())[:4]) else None
+        if not weights.is_flat(params, dev):
+            if self._own_flat is None:
+                self._own_flat = torch.zeros(weights.FlatLayout(hp).size, dtype=torch.float32, device=dev)
+            params = weights.flat_views(params, hp, dev, out=self._own_flat)
+        key = next(iter(params.values())).data_ptr()
         tp = getattr(self, "_tp", None)
-        if tp is not None and tp.plan is not None and key is not None and getattr(self, "_tp_key", None) == key:
-            tp.params = params
-            if tp.plan._dev_ready:
-                tp.plan.refresh_tables_device()
-            elif not self.external_host_tables:
-                self.refresh_host_tables()
-            tp.plan.run_kernels()
-            tp._small_tables()
+        if tp is not None and getattr(self, "_tp_key", None) == key:
+            tp.refresh()
         else:
             tp = self._tp = _TrainPack(params, hp, self.device)
-            self._tp_key = key if tp.plan is not None else None
+            self._tp_key = key
         x = torch.as_tensor(x).to(device=dev, dtype=torch.float32).contiguous()
         c = torch.as_tensor(c).to(device=dev, dtype=torch.float32).contiguous()
         B, T = int(x.shape[0]), int(x.shape[1])
@@ -607,7 +440,7 @@ class GradEngine:
             go = {k: torch.empty(v, dtype=torch.float32, device=dev) for k, v in shp.items()}
         elif not all(go[k].is_contiguous() for k in shp):
             raise ValueError("grad_out tensors must be contiguous")
-        masters = {k: tp._f32(k) for k in shp}                   # device fp32 copies (the masters themselves when they qualify)
+        masters = {k: tp._f32(k) for k in shp}
         ptr = lambda t_: t_.data_ptr() if t_ is not None else None
         key = (tuple(masters[k].data_ptr() for k in shp), tuple(go[k].data_ptr() for k in shp))
         if getattr(self, "_desc_key", None) != key:
@@ -767,7 +600,7 @@ class Trainer:
         """First call at a shape: eager (creates the packing plan, fills every cache).  Second: record.  The
         recording is a chain of hipGraphs cut where a block's gradients are final, so that with more than one
         rank each block's all-reduce still starts between two replays, under the rest of the backward pass;
-        the host-computed tables and the Adam rate are refreshed before the replay."""
+        the Adam rate is refreshed before the replay (the packing, tables included, is inside the recording)."""
         import torch
         import torch.distributed as dist
         dev = torch.device(self.device)
@@ -787,7 +620,6 @@ class Trainer:
             mprio = os.environ.get("FWN_TRAIN_MAIN_PRIO")     # developer switch (same-box A/B)
             side = torch.cuda.Stream(dev, priority=int(mprio)) if mprio else torch.cuda.Stream(dev)
             side.wait_stream(torch.cuda.current_stream(dev))
-            self.engine.external_host_tables = True
             cur = [None]
             try:
                 with torch.cuda.stream(side):
@@ -825,15 +657,11 @@ class Trainer:
                 torch.cuda.synchronize(dev)
                 warnings.warn("recording the training step failed (%s: %s); continuing with eager steps" % (type(e).__name__, e))
                 self.graph = False
-                self.engine.external_host_tables = False
                 return self._step_eager(x, c)
-            finally:
-                self.engine.external_host_tables = False
             torch.cuda.current_stream(dev).wait_stream(side)
             rec = self._recorded[key] = dict(xs=xs, cs=cs, segs=segs, out=(loss, log_p, logdet, gnorm))
         rec["xs"].copy_(x.reshape(rec["xs"].shape), non_blocking=True)
         rec["cs"].copy_(c, non_blocking=True)
-        self.engine.refresh_host_tables()
         self.opt.advance()
         ranges, works = self._ranges(), []
         for g, i in rec["segs"]:

@@ -198,6 +198,60 @@ def count_params(hp) -> int:
     return int(sum(int(np.prod(v)) for v in param_shapes(hp).values()))
 
 
+class FlatLayout:
+    """name -> (offset, shape) of every trainable tensor inside one flat fp32 vector, in
+    ``param_shapes`` order, each tensor start aligned to 4 elements (16 bytes)."""
+
+    def __init__(self, hp):
+        self.slots = {}
+        off = 0
+        for name, shape in param_shapes(hp).items():
+            n = int(np.prod(shape))
+            self.slots[name] = (off, tuple(shape), n)
+            off += (n + 3) // 4 * 4
+        self.size = off
+
+    def flatten(self, params):
+        out = np.zeros(self.size, dtype=np.float32)
+        for name, (off, shape, n) in self.slots.items():
+            out[off:off + n] = np.asarray(params[name], dtype=np.float32).reshape(-1)
+        return out
+
+    def views(self, flat):
+        """dict name -> view (torch or numpy) into ``flat`` with the reference's shapes."""
+        return {name: flat[off:off + n].reshape(shape) for name, (off, shape, n) in self.slots.items()}
+
+
+def is_flat(params, device) -> bool:
+    """True if every parameter is a contiguous fp32 view of one 1-D tensor on ``device`` (the optimiser's masters)."""
+    import torch
+    dev = torch.device(device)
+    if dev.type == "cuda" and dev.index is None:       # "cuda" != "cuda:0" for torch: make it concrete
+        dev = torch.device("cuda", torch.cuda.current_device())
+    vals = list(params.values())
+    base = getattr(vals[0], "_base", None)
+    return (base is not None and base.dim() == 1 and base.dtype == torch.float32 and base.device == dev
+            and all(isinstance(v, torch.Tensor) and v._base is base and v.is_contiguous() for v in vals))
+
+
+def flat_views(params, hp, device, out=None):
+    """``params`` as contiguous fp32 views of one flat device vector (``FlatLayout``): returned unchanged when they
+    already are (``is_flat``), else copied into ``out`` (a fresh vector when None) - NumPy input in one host-to-device copy."""
+    import torch
+    if out is None and is_flat(params, device):
+        return params
+    lay = FlatLayout(hp)
+    if out is None:
+        out = torch.zeros(lay.size, dtype=torch.float32, device=device)
+    views = lay.views(out)
+    if any(isinstance(v, torch.Tensor) for v in params.values()):
+        for name, v in views.items():
+            v.copy_(torch.as_tensor(params[name]).reshape(v.shape))
+    else:
+        out.copy_(torch.from_numpy(lay.flatten(params)))
+    return views
+
+
 def synthetic_params(hp, seed: int = 1234, zero_conv: str = "normal",
                      actnorm: str = "zeros") -> "OrderedDict[str, np.ndarray]":
     """Seeded fp32 parameter set (numpy PCG64), generated in ``param_shapes`` order.
