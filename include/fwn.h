@@ -31,7 +31,8 @@
 extern "C" {
 #endif
 
-#define FWN_VERSION 321            /* 0.3.21 (round 6): + fwn_model_desc.cond_stream (appended) and fwn_cond_stream* / fwn_pack_cond_stream (the register-streamed
+#define FWN_VERSION 322            /* 0.3.22: - fwn_train_desc.an_logdet and .defer_block_done (a host built against 0.3.21 must be rebuilt).
+                                    * 0.3.21 (round 6): + fwn_model_desc.cond_stream (appended) and fwn_cond_stream* / fwn_pack_cond_stream (the register-streamed
                                     * conditioning projection, csrc/cond_rs.h; additive); fwn_pack_tail_stream_jobs.  0.3.20 (round 6): + fwn_flow_desc.Wts and fwn_tail_stream_bytes / fwn_pack_tail_stream / fwn_tail_stream_rows (the
                                     * register-streamed tail, csrc/tail_rs.h; additive: a 0.3.10 host that zero-fills its descriptors keeps working);
                                     * fwn_tail_partials / fwn_tail_partials_chained are upper bounds now.  0.3.10 (round 5): + fwn_flow_run_persist / fwn_flow_persist_* (one launch per small-M flow), fwn_model_desc.persist_mode
@@ -546,20 +547,12 @@ typedef struct fwn_train_desc {
     const int64_t* br[16]; const int64_t* zcol[16];
     const float* up_bias_dev[FWN_MAX_UPSAMPLE]; /* the bias masters (device scalars)                            */
     fwn_conv_grad up[FWN_MAX_UPSAMPLE];         /* V [2s][3], scalar g; dV, dg, db (bias)                       */
-    const float* an_logdet;                     /* unused (the tail's log-det partials carry the ActNorm terms); any
-                                                   non-NULL device pointer */
     int32_t zero_dead_res;                      /* != 0: also zero the gradients of the dead last-layer res_conv */
-    /* != 0 (with side_stream): nothing consumes a block's gradients before the end of the call (one rank: no all-reduce),
-     * so the side stream is NOT joined into `stream` block by block - the data-gradient chain never waits for the weight
-     * gradients - but once, behind block 0; on_block_done(n_block - 1 .. 0) are then all called at that point, in order
-     * (each still fires only after its block's gradients are complete in `stream` order - but none of them early: a hook that
-     * starts collectives to overlap them with the backward pass wants 0 here).  On an error return every path first joins the
-     * side stream into `stream`: nothing of the call is left running on it. */
-    int32_t defer_block_done;
     /* Optional second hipStream_t (NULL: one stream).  The weight gradients of block i (grouped TN GEMMs + weight-norm
      * backward) and its conditioning-gradient GEMMs then run on it under the data-gradient chain of block i - 1 and are
      * joined into `stream` before on_block_done(i); the workspace grows by per-flow copies of the temporaries they
-     * read.  Same results. */
+     * read.  Same results.  On an error return every path first joins the side stream into `stream`: nothing of the
+     * call is left running on it. */
     void* side_stream;
 } fwn_train_desc;
 typedef int (*fwn_block_done_fn)(void* user, int block);

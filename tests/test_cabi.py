@@ -34,11 +34,11 @@ def test_every_declared_symbol_is_exported_and_bound(lib):
     assert sorted(_lib.SIGNATURES) == names
 
 
-def test_version(lib):
-    assert lib.fwn_version() == 321
+def test_version_322(lib):
+    assert lib.fwn_version() == 322
 
 
-def test_struct_layout_matches_header(tmp_path):
+def test_struct_layout_matches_header_v322(tmp_path):
     """The ctypes mirrors against the C compiler's view of include/fwn.h: sizes and the offsets of the last members."""
     import shutil
     import subprocess
@@ -50,7 +50,7 @@ def test_struct_layout_matches_header(tmp_path):
                    'offsetof(fwn_flow_desc, an), offsetof(fwn_flow_desc, Wd8), offsetof(fwn_flow_desc, wd8_exp), sizeof(fwn_model_desc), '
                    'offsetof(fwn_model_desc, up_w), offsetof(fwn_model_desc, flows), offsetof(fwn_model_desc, gate_fp8), '
                    'sizeof(fwn_conv_grad), sizeof(fwn_flow_train_desc), offsetof(fwn_flow_train_desc, d_zscale), sizeof(fwn_train_desc), '
-                   'offsetof(fwn_train_desc, an_logdet), offsetof(fwn_train_desc, side_stream), sizeof(fwn_gemm_desc), '
+                   'offsetof(fwn_train_desc, zero_dead_res), offsetof(fwn_train_desc, side_stream), sizeof(fwn_gemm_desc), '
                    'offsetof(fwn_gemm_desc, gate_out), offsetof(fwn_flow_desc, Wfront3), offsetof(fwn_flow_desc, kf3), '
                    'offsetof(fwn_model_desc, chain_mode)); return 0; }\n')
     exe = str(tmp_path / "layout")
@@ -58,7 +58,7 @@ def test_struct_layout_matches_header(tmp_path):
     got = [int(v) for v in subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split()]
     F, M, FT, T = _lib.FlowDesc, _lib.ModelDesc, _lib.FlowTrainDesc, _lib.TrainDesc
     assert got == [C.sizeof(F), F.an.offset, F.Wd8.offset, F.wd8_exp.offset, C.sizeof(M), M.up_w.offset, M.flows.offset,
-                   M.gate_fp8.offset, C.sizeof(_lib.ConvGrad), C.sizeof(FT), FT.d_zscale.offset, C.sizeof(T), T.an_logdet.offset,
+                   M.gate_fp8.offset, C.sizeof(_lib.ConvGrad), C.sizeof(FT), FT.d_zscale.offset, C.sizeof(T), T.zero_dead_res.offset,
                    T.side_stream.offset, C.sizeof(_lib.GemmDesc), _lib.GemmDesc.gate_out.offset, F.Wfront3.offset, F.kf3.offset,
                    M.chain_mode.offset]
 
@@ -96,13 +96,13 @@ def _build_c_consumer(tmp_path):
     return exe
 
 
-def test_plain_c_program_binds_the_abi(lib, tmp_path):
+def test_plain_c_program_binds_the_abi_v322(lib, tmp_path):
     """include/fwn.h compiles as C99 and a torch-free C program gets version, error codes and messages."""
     import subprocess
     exe = _build_c_consumer(tmp_path)
     out = subprocess.run([exe, _lib.LIB_PATH], capture_output=True, text=True, timeout=60)
     assert out.returncode == 0, out.stderr
-    assert "C ABI ok: version 321" in out.stdout
+    assert "C ABI ok: version 322" in out.stdout
 
 
 @pytest.mark.gpu

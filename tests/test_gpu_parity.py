@@ -517,7 +517,7 @@ def test_conditioning_split_k_equals_the_one_pass_projection(full_model, blk, m)
 @pytest.mark.parametrize("blk,m,forced", [(4, 4032, 0), (5, 2016, 0), (6, 1008, 0), (7, 504, 0), (7, 504, 1), (6, 1000, 3), (5, 390, 2), (4, 4000, 2),
                                           (7, 2016, 0), (3, 2016, 0)])
 def test_streamed_conditioning_equals_the_ring_projection_bit_for_bit(full_model, blk, m, forced):
-    """fwn_cond_stream (csrc/cond_rs.h: weights from their fragment streams to registers, 128- / 96- / 64-row tiles, the K range
+    """fwn_cond_stream (csrc/cond_rs.h: weights from their fragment streams to registers, 128- / 96-row tiles, the K range
     dealt over workgroups) against fwn_cond_split on the same operands with the same split count: the same MFMAs on the same
     fragments in the same order, so `==` - whole tiles and ragged row counts, every tile height the plan picks, split counts the
     plan picks and forced ones, both conditioning planes (flows with an odd index read the other one), NaN-filled outputs (every

@@ -246,7 +246,7 @@ def test_the_c_sequenced_step_reproduces_the_python_sequenced_reference_bit_for_
     (dict(n_block=4, n_flow=2, n_layer=3, hop_size=32, upsample_scales=[4, 8], num_mels=16), 2, 512),
     ("full6", 2, 1024),
 ])
-def test_side_stream_weight_gradients_equal_the_one_stream_call_bit_for_bit(cfg, b, t, monkeypatch):
+def test_side_stream_weight_gradients_equal_the_one_stream_call_bit_for_bit(cfg, b, t):
     """fwn_train_desc.side_stream moves each block's weight-gradient GEMMs and weight-norm backward to a second stream
     under the next block's data-gradient chain: same kernels on per-flow copies of the temporaries - same bits; and the
     block callbacks still arrive last block first, each after its gradients are enqueued on the caller's stream."""
@@ -260,8 +260,7 @@ def test_side_stream_weight_gradients_equal_the_one_stream_call_bit_for_bit(cfg,
     x, c = torch.from_numpy(inp["x"]).reshape(b, t).cuda(), torch.from_numpy(inp["c"]).cuda()
     res = {}
     for side in ("0", "1"):
-        monkeypatch.setenv("FWN_TRAIN_SIDE", side)
-        eng = GradEngine(hp)
+        eng = GradEngine(hp, side_stream=side == "1")
         order = []
         for rep in range(2):        # the second call reuses the workspace and the event pool
             order.clear()
@@ -330,24 +329,20 @@ def test_side_stream_training_steps_soak_against_the_one_stream_call():
 
     ref = {}
     for side, steps in (("0", 2), ("1", 50)):
-        os.environ["FWN_TRAIN_SIDE"] = side
-        try:
-            eng = GradEngine(hp)
-            flat = torch.zeros(total, dtype=torch.float32, device="cuda")
-            go = views(flat)
-            bad = 0
-            for _ in range(steps):
-                flat.zero_()                         # (the dead res_conv gradients are written once per engine: zeros either way)
-                loss, lp, ld, _ = eng.loss_and_grads(p, x, c, grad_out=go)
-                torch.cuda.synchronize()
-                if side == "0":
-                    ref = dict(loss=float(loss), lp=float(lp), ld=float(ld), flat=flat.clone())
-                else:
-                    bad += int(not ((float(loss), float(lp), float(ld)) == (ref["loss"], ref["lp"], ref["ld"])
-                                    and torch.equal(flat, ref["flat"])))
-            assert bad == 0, "%d of %d side-stream calls differ from the one-stream call" % (bad, steps)
-        finally:
-            os.environ.pop("FWN_TRAIN_SIDE", None)
+        eng = GradEngine(hp, side_stream=side == "1")
+        flat = torch.zeros(total, dtype=torch.float32, device="cuda")
+        go = views(flat)
+        bad = 0
+        for _ in range(steps):
+            flat.zero_()                         # (the dead res_conv gradients are written once per engine: zeros either way)
+            loss, lp, ld, _ = eng.loss_and_grads(p, x, c, grad_out=go)
+            torch.cuda.synchronize()
+            if side == "0":
+                ref = dict(loss=float(loss), lp=float(lp), ld=float(ld), flat=flat.clone())
+            else:
+                bad += int(not ((float(loss), float(lp), float(ld)) == (ref["loss"], ref["lp"], ref["ld"])
+                                and torch.equal(flat, ref["flat"])))
+        assert bad == 0, "%d of %d side-stream calls differ from the one-stream call" % (bad, steps)
     assert bool(torch.isfinite(ref["flat"]).all())
 
 
@@ -362,27 +357,23 @@ def test_an_exception_in_the_block_callback_stops_the_call_and_reaches_the_calle
     inp = W.synthetic_inputs(hp, 2, 128)
     x, c = torch.from_numpy(inp["x"]).reshape(2, 128).cuda(), torch.from_numpy(inp["c"]).cuda()
     for side in ("0", "1"):
-        os.environ["FWN_TRAIN_SIDE"] = side
-        try:
-            eng = GradEngine(hp)
-            seen = []
+        eng = GradEngine(hp, side_stream=side == "1")
+        seen = []
 
-            def hook(blk):
-                seen.append(blk)
-                if blk == 1:
-                    raise RuntimeError("all-reduce of block 1 failed")
+        def hook(blk):
+            seen.append(blk)
+            if blk == 1:
+                raise RuntimeError("all-reduce of block 1 failed")
 
-            with pytest.raises(RuntimeError, match="all-reduce of block 1 failed"):
-                eng.loss_and_grads(p, x, c, on_block_done=hook)
-            torch.cuda.synchronize()
-            assert seen == [2, 1]                      # nothing is reported (or enqueued) after the failure
-            # the raw C-ABI: a non-zero return from the callback -> FWN_ERR_CALLBACK with a message
-            good = eng.loss_and_grads(p, x, c)
-            torch.cuda.synchronize()
-            again = eng.loss_and_grads(p, x, c, on_block_done=lambda blk: None)
-            assert float(good[0]) == float(again[0])   # and the engine is usable afterwards
-        finally:
-            os.environ.pop("FWN_TRAIN_SIDE", None)
+        with pytest.raises(RuntimeError, match="all-reduce of block 1 failed"):
+            eng.loss_and_grads(p, x, c, on_block_done=hook)
+        torch.cuda.synchronize()
+        assert seen == [2, 1]                      # nothing is reported (or enqueued) after the failure
+        # the raw C-ABI: a non-zero return from the callback -> FWN_ERR_CALLBACK with a message
+        good = eng.loss_and_grads(p, x, c)
+        torch.cuda.synchronize()
+        again = eng.loss_and_grads(p, x, c, on_block_done=lambda blk: None)
+        assert float(good[0]) == float(again[0])   # and the engine is usable afterwards
 
 
 @pytest.mark.parametrize("m,ch", [(700, 1), (333, 8), (65, 128)])
@@ -570,7 +561,7 @@ def test_train_cli_loop_checkpoint_resume_and_synthesis(tmp_path):
 
 
 # ------------------------------------------------------------------ data-parallel step, 2 ranks on one GPU
-def _dp_worker(rank, world, port, out_dir, backend="gloo"):
+def _dp_worker(rank, world, port, out_dir, backend="gloo", graph=True):
     import os, sys
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
@@ -588,12 +579,12 @@ def _dp_worker(rank, world, port, out_dir, backend="gloo"):
     inp = W.synthetic_inputs(hp, 4, 256)
     x = torch.from_numpy(inp["x"]).reshape(4, 256)[2 * rank:2 * rank + 2].cuda()
     c = torch.from_numpy(inp["c"])[2 * rank:2 * rank + 2].cuda()
-    tr = Trainer(hp, W.synthetic_params(hp, 11))
+    tr = Trainer(hp, W.synthetic_params(hp, 11), graph=graph)
     tr.ddi(x, c)
     w0 = tr.opt.w.clone()
     tr.step(x, c)
     g1, w1 = tr.opt.g.cpu().numpy(), tr.opt.w.cpu().numpy()
-    tr.step(x, c)               # with FWN_TRAIN_GRAPH=1: recorded (a chain of hipGraphs cut at the all-reduces) ...
+    tr.step(x, c)               # with graph=True: recorded (a chain of hipGraphs cut at the all-reduces) ...
     tr.step(x, c)               # ... and replayed
     np.savez(os.path.join(out_dir, "rank%d.npz" % rank), w0=w0.cpu().numpy(), g=g1, w1=w1, w3=tr.opt.w.cpu().numpy())
     dist.barrier()
@@ -616,10 +607,10 @@ def test_two_rank_data_parallel_step_matches_one_process_on_the_whole_batch(tmp_
         pytest.skip("RCCL with one GPU per rank needs two GPUs (the one-rank RCCL path is covered by tests/test_rccl.py)")
     ctx = mp.get_context("spawn")
 
-    def run_pair(out):
+    def run_pair(out, graph):
         """Both ranks to completion -> exit codes (None = still running after the time limit, killed)."""
         s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()      # a fresh port per pair
-        procs = [ctx.Process(target=_dp_worker, args=(r, 2, port, str(out), backend), daemon=True) for r in range(2)]
+        procs = [ctx.Process(target=_dp_worker, args=(r, 2, port, str(out), backend, graph), daemon=True) for r in range(2)]
         for p in procs:
             p.start()
         try:
@@ -634,16 +625,12 @@ def test_two_rank_data_parallel_step_matches_one_process_on_the_whole_batch(tmp_
 
     w3 = {}
     for mode in ("1", "0"):     # recorded step, then the eager step: same bits after three steps
-        os.environ["FWN_TRAIN_GRAPH"] = mode
         out = tmp_path / ("graph" + mode)
         out.mkdir()
-        try:
-            codes = run_pair(out)
-            if None in codes:       # rendezvous of two fresh processes on one GPU stalled: one more try, then fail
-                codes = run_pair(out)
-            assert codes == [0, 0], codes
-        finally:
-            os.environ.pop("FWN_TRAIN_GRAPH")
+        codes = run_pair(out, mode == "1")
+        if None in codes:       # rendezvous of two fresh processes on one GPU stalled: one more try, then fail
+            codes = run_pair(out, mode == "1")
+        assert codes == [0, 0], codes
         r0, r1 = (np.load(out / ("rank%d.npz" % r)) for r in range(2))
         assert np.array_equal(r0["w0"], r1["w0"]) and np.array_equal(r0["g"], r1["g"]) and np.array_equal(r0["w1"], r1["w1"])
         assert np.array_equal(r0["w3"], r1["w3"])

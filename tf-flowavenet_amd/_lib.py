@@ -12,7 +12,7 @@ FWN_MAX_LAYERS = 8
 FWN_MAX_UPSAMPLE = 4
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# FWN_LIB: developer override (tools/tune.py loads the -DFWN_TUNABLE build); the product is csrc/libfwn.so
+# FWN_LIB: developer override (another build of the library, e.g. for a same-box A/B); the product is csrc/libfwn.so
 LIB_PATH = os.environ.get("FWN_LIB") or os.path.join(_HERE, "csrc", "libfwn.so")
 
 vp = C.c_void_p
@@ -79,7 +79,7 @@ class TrainDesc(C.Structure):
     _fields_ = [("model", C.POINTER(ModelDesc)), ("flows", C.POINTER(FlowTrainDesc)),
                 ("cond_rows", vp * 16), ("front_rows", vp * 16), ("zinv32", vp * 16), ("br", vp * 16), ("zcol", vp * 16),
                 ("up_bias_dev", vp * FWN_MAX_UPSAMPLE), ("up", ConvGrad * FWN_MAX_UPSAMPLE),
-                ("an_logdet", vp), ("zero_dead_res", i32), ("defer_block_done", i32), ("side_stream", vp)]
+                ("zero_dead_res", i32), ("side_stream", vp)]
 
 
 # name -> (restype, argtypes); every symbol include/fwn.h declares.
@@ -260,12 +260,6 @@ def load():
         fn = getattr(lib, name)   # AttributeError if the symbol is missing
         fn.restype = res
         fn.argtypes = args
-    # developer switches of the same-box A/B scripts (tools/diag): read ONCE here, handed to the library as options - the
-    # launch path itself reads no environment (round 4's did, on every gate launch)
-    for opt in ("rs_persist",):
-        v = os.environ.get("FWN_OPT_" + opt.upper())
-        if v is not None:
-            lib.fwn_set_option(opt.encode(), int(v))
     _lib = lib
     return lib
 

@@ -774,7 +774,8 @@ static bool hoist_cond(const fwn_model_desc* m, int64_t M, int cin) {
     if (m->cond_mode == 2) return true;
     // small-M blocks: batch the weight-streaming cond GEMMs of all flows - where the conditioning K is long enough to pay for
     // the extra launch and the P round trip
-    return M < FWN_TUNE(FWN_HOIST_M, 4096) && cin >= FWN_TUNE(FWN_HOIST_CIN, 256);
+    constexpr int FWN_HOIST_M = 4096, FWN_HOIST_CIN = 256;
+    return M < FWN_HOIST_M && cin >= FWN_HOIST_CIN;
 }
 // the register-streamed conditioning projection (csrc/cond_rs.h) serves this block at M rows: its stream is given
 static bool block_cond_rs(const fwn_model_desc* m, int blk, int64_t M) {
@@ -794,7 +795,8 @@ static bool persist_block(const fwn_model_desc* m, int64_t M, int blk) {
     // pass - there with one level's worth of workgroups, flow_persist.h's launcher), 1: nowhere,
     // 2: wherever the form exists.  Same results bit for bit either way.
     if (m->persist_mode == 1) return false;       // (gate_fp8 models too: fp8 taps need fused conditioning and >= 12288 rows - never these blocks)
-    if (m->persist_mode != 2 && M > FWN_TUNE(FWN_PERSIST_AUTO_ROWS, 512)) return false;
+    constexpr int FWN_PERSIST_AUTO_ROWS = 512;
+    if (m->persist_mode != 2 && M > FWN_PERSIST_AUTO_ROWS) return false;
     const fwn_flow_desc* d = &m->flows[blk * m->n_flow];
     return hoist_cond(m, M, d->cin) && fwn_flow_persist_ok((int)M, d->Ch, d->L, d->npt, d->Wfront2 != nullptr, true);
 }

@@ -798,32 +798,16 @@ struct TailLinProb {      // Y' = ReLU(sum_l A_l[M][256] . W[:, l*256 ..]^T + bi
 // ---------------------------------------------------------------------------
 // Host-side launchers (called from the C-ABI in api.hip)
 // ---------------------------------------------------------------------------
-// FWN_TAIL128_TWO = 1: from FWN_TAIL256_MIN rows on (block 0 of the 8-clip pass: two workgroups of 128 rows per CU exist)
-// the fused tail runs as 128-row workgroups with 32-wide phase-1 chunks in TWO 32 KB slots (72 KB of LDS: two per CU, one's
-// DMA latency and epilogue under the other's MFMA chains) instead of one 256-row workgroup per CU.  Measured below.
-#ifndef FWN_TAIL128_TWO
-#define FWN_TAIL128_TWO 0
-#endif
-#ifndef FWN_TAIL256_MIN
-#define FWN_TAIL256_MIN (192 * 256)
-#endif
-#ifndef FWN_TAIL_SPLIT_MAX
-#define FWN_TAIL_SPLIT_MAX 12288      // rows up to which the N-split tail (three ring GEMMs) replaces the fused tail
-#endif
-int fwn_tail_rows(int M) { return (M >= FWN_TAIL256_MIN && !FWN_TUNE(FWN_TAIL128_TWO, FWN_TAIL128_TWO)) ? 256 : 128; }   // rows per fused-tail workgroup
-int fwn_tail_is_split(int M) { return M <= FWN_TUNE(FWN_TAIL_SPLIT_MAX, FWN_TAIL_SPLIT_MAX); }
-// M <= FWN_TAIL_SPLIT_MAX: the skip sum as a ring GEMM that splits its weights over workgroups, then either (FWN_TAIL_SPLIT_CHAIN,
-// default) tail_kernel<.., HAS_P1 = false> = final conv + ZeroConv + coupling in one launch of 64-row workgroups, or the round-2
-// form (two more ring GEMMs).
-#ifndef FWN_TAIL_SPLIT_CHAIN
-#define FWN_TAIL_SPLIT_CHAIN 1
-#endif
-#ifndef FWN_TAIL_SPLIT_CHAIN_MIN
-#define FWN_TAIL_SPLIT_CHAIN_MIN 6144    // fewer rows: too few 64-row workgroups to stream the final / ZeroConv weights through (in situ:
-#endif                                   // block 4, 4032 rows, +2 us per flow; block 7, 504 rows, +17 us against the two ring GEMMs)
-static bool tail_split_chain(int M) {
-    return FWN_TUNE(FWN_TAIL_SPLIT_CHAIN, FWN_TAIL_SPLIT_CHAIN) != 0 && M >= FWN_TUNE(FWN_TAIL_SPLIT_CHAIN_MIN, FWN_TAIL_SPLIT_CHAIN_MIN);
-}
+constexpr int FWN_TAIL256_MIN = 192 * 256;       // rows from which the fused tail runs 256-row workgroups (they fill the chip)
+constexpr int FWN_TAIL_SPLIT_MAX = 12288;        // rows up to which the N-split tail (three ring GEMMs) replaces the fused tail
+int fwn_tail_rows(int M) { return M >= FWN_TAIL256_MIN ? 256 : 128; }   // rows per fused-tail workgroup
+int fwn_tail_is_split(int M) { return M <= FWN_TAIL_SPLIT_MAX; }
+// M <= FWN_TAIL_SPLIT_MAX: the skip sum as a ring GEMM that splits its weights over workgroups, then either
+// tail_kernel<.., HAS_P1 = false> = final conv + ZeroConv + coupling in one launch of 64-row workgroups, or (fewer rows than
+// FWN_TAIL_SPLIT_CHAIN_MIN) the round-2 form (two more ring GEMMs).
+constexpr int FWN_TAIL_SPLIT_CHAIN_MIN = 6144;   // fewer rows: too few 64-row workgroups to stream the final / ZeroConv weights through (in situ:
+                                                 // block 4, 4032 rows, +2 us per flow; block 7, 504 rows, +17 us against the two ring GEMMs)
+static bool tail_split_chain(int M) { return M >= FWN_TAIL_SPLIT_CHAIN_MIN; }
 static int tail_chain_rows(int M) { return fwn_tail_is_split(M) ? 64 : fwn_tail_rows(M); }
 // rs_mt != 0: the register-streamed tail runs the launch (tail_rs.h: it can always write out_b elsewhere)
 int fwn_tail_chain_xb_out(int M, int npt, int rs_mt) { return rs_mt != 0 || !fwn_tail_is_split(M) || tail_split_chain(M); }
@@ -877,9 +861,13 @@ static void launch_ring(const Prob& p, int M, int N, int ksteps, hipStream_t st)
     // 16-wave workgroups (4 waves per SIMD) hide the barrier / LDS latency of the K loop best
     // (tools/bench_gemm.hip): 256x256 reaches ~0.8 PF on the block-1 gate, 8-wave tiles ~0.7.
     const int FILL = 192;    // workgroups needed before a fatter tile pays (256 CUs)
-    if (Prob::ALLOW_256 && N % 256 == 0 && ((M + 255) / 256) * (N / 256) >= FILL) {
-        RING_LAUNCH(256, 256, 4, 4, 64, 2);
-    } else if (((M + 255) / 256) * (N / 128) >= FILL) {
+    if constexpr (Prob::ALLOW_256) {
+        if (N % 256 == 0 && ((M + 255) / 256) * (N / 256) >= FILL) {
+            RING_LAUNCH(256, 256, 4, 4, 64, 2);
+            return;
+        }
+    }
+    if (((M + 255) / 256) * (N / 128) >= FILL) {
         RING_LAUNCH(256, 128, 8, 2, 64, 3);
     } else if (((M + 127) / 128) * (N / 128) >= FILL) {
         RING_LAUNCH(128, 128, 4, 2, 64, 3);
@@ -890,16 +878,14 @@ static void launch_ring(const Prob& p, int M, int N, int ksteps, hipStream_t st)
         // barrier and an LDS round trip for a handful of MFMAs.  128-wide chunks halve the number of round trips and
         // intra-workgroup split-K (4 wave groups taking alternate k-steps) spreads the DMA issues over 8 waves
         // (tools/bench_gemm.hip, K = 768: 8.1 -> 6.7 us); K must be a multiple of 128 for the wide chunks.
-        const int mode = FWN_TUNE(FWN_SMALL_TILE, 2);
-        if (ksteps % 8 == 0 && mode == 2) RING_LAUNCHK(64, 64, 2, 1, 128, 4, 4);
-        else if (ksteps % 8 == 0 && mode == 1) RING_LAUNCHK(64, 64, 2, 1, 128, 4, 2);
+        if (ksteps % 8 == 0) RING_LAUNCHK(64, 64, 2, 1, 128, 4, 4);
         else RING_LAUNCHK(64, 64, 2, 1, 64, 4, 2);
     }
 }
 
 void fwn_launch_front(const float* xa, const float* an_a, const void* W, const void* W2, const float* bias,
                       void* hout, void* scratch, int M, int Ti, int Ch, int kpad, int apply_an, void* h8out, hipStream_t st) {
-    if (W2 && (Ch == 32 || Ch == 64 || Ch == 128 || (Ch == 16 && !h8out)) && ((uintptr_t)xa & 15) == 0 && FWN_TUNE(FWN_FRONT_FUSED, 1)) {
+    if (W2 && (Ch == 32 || Ch == 64 || Ch == 128 || (Ch == 16 && !h8out)) && ((uintptr_t)xa & 15) == 0) {
         const int grid = ((M + 63) / 64) * 4;
         if (Ch == 16) hipLaunchKernelGGL((front_mfma_kernel<32, 16>), dim3(grid), dim3(256), 0, st, xa, an_a, apply_an, (const bf16*)W2, bias, (bf16*)hout, M, Ti);
         else if (Ch == 32) hipLaunchKernelGGL((front_mfma_kernel<32>), dim3(grid), dim3(256), 0, st, xa, an_a, apply_an, (const bf16*)W2, bias, (bf16*)hout, M, Ti);
@@ -956,7 +942,7 @@ void fwn_launch_gate(const void* h, const void* ca, const float* P, const void* 
     // but 128-row tiles still fill the chip: block 3 of the 8-clip pass (8064 rows) - the ring tile there stages the
     // dilated taps three times (720 KB per workgroup against 593 KB) at one workgroup per CU
     const int t128 = (M + 127) / 128;
-    if (dil <= FWN_HALO_MAXDIL && t128 * 4 >= 192 && FWN_TUNE(FWN_HALO128, 1)) {
+    if (dil <= FWN_HALO_MAXDIL && t128 * 4 >= 192) {
         hipLaunchKernelGGL((gate_halo_kernel<128, 128, GateProb>), dim3(t128 * 4), dim3(512), 0, st, p, 4);
         return;
     }
@@ -988,7 +974,7 @@ void fwn_launch_res(const void* o, const void* hin, const void* W, const float* 
     // depth 3) left the memory pipe idle between phases: block 0 19.4 -> 17.6 us per launch, block 1 9.4 -> 9.3
     // (tools/probe/res_tiles.py, bit-identical; 128 x 128 at depth 3 / 4 x 32-wide chunks, 64 x 128 at depth 2 / 3 and
     // 256 x 128 at depth 2 are all slower than the old tile).
-    if (((M + 255) / 256) * 2 >= 192 && FWN_TUNE(FWN_RES_TWO_PER_CU, 1)) {
+    if (((M + 255) / 256) * 2 >= 192) {
         const int N = 256;
         typedef ResProb Prob;
         RING_LAUNCH(128, 128, 4, 2, 64, 2);
@@ -1006,10 +992,10 @@ void fwn_launch_res(const void* o, const void* hin, const void* W, const float* 
 static bool cond_wide_split(int M, int kcpad) { return M > 256 && M <= 512 && kcpad >= 8192; }
 int fwn_cond_nsplit(int M, int nz, int kcpad) {
     const int base = ((M + 63) / 64) * 4 * nz;
-    if (FWN_TUNE(FWN_COND_WIDE, 1) && cond_wide_split(M, kcpad)) return 2;
-    if (base >= FWN_TUNE(FWN_COND_BASE, 128)) return 1;
+    if (cond_wide_split(M, kcpad)) return 2;
+    if (base >= 128) return 1;
     int ns = 1;
-    while (ns < 8 && base * ns * 2 <= FWN_TUNE(FWN_COND_FILL, 256) && kcpad / 64 / (ns * 2) >= 8) ns *= 2;
+    while (ns < 8 && base * ns * 2 <= 256 && kcpad / 64 / (ns * 2) >= 8) ns *= 2;
     return ns;
 }
 __global__ __launch_bounds__(256) void cond_reduce_kernel(float* __restrict__ P, const float* __restrict__ part, long part_stride,
@@ -1063,8 +1049,7 @@ void fwn_launch_cond2(const void* ca, const void* ca_odd, const void* Wc_base, f
                  M, cin, kcpad, part_base, part_stride, nsplit > 1 ? nsplit : 1};
     const int nz = nflow * L;                                    // matrices of this launch
     // a split K range: the smallest tile (few rows), 256 x 128 for the wide split above
-    const int t = cb.nsplit > 1 ? (FWN_TUNE(FWN_COND_SPLIT_TILE, -1) >= 0 ? FWN_TUNE(FWN_COND_SPLIT_TILE, -1) : cond_wide_split(M, kcpad) ? 1 : 3)
-                                : FWN_TUNE(FWN_COND_TILE, -1) >= 0 ? FWN_TUNE(FWN_COND_TILE, -1) : fwn_cond_tile(M, nz, nullptr);
+    const int t = cb.nsplit > 1 ? (cond_wide_split(M, kcpad) ? 1 : 3) : fwn_cond_tile(M, nz, nullptr);
     const dim3 grid(((M + kCondBM[t] - 1) / kCondBM[t]) * (512 / kCondBN[t]), nz, cb.nsplit);
     if (t == 0) hipLaunchKernelGGL((cond_batch_kernel<256, 256, 4, 4, 64, 2>), grid, dim3(1024), 0, st, cb, 2);
     else if (t == 1) hipLaunchKernelGGL((cond_batch_kernel<256, 128, 8, 2, 64, 3>), grid, dim3(1024), 0, st, cb, 4);
@@ -1080,7 +1065,7 @@ void fwn_launch_cond(const void* ca, const void* Wc_base, float* P_base, long w_
 
 // ---- tail dispatch ----
 // M > FWN_TAIL_SPLIT_MAX: the fused register-chained tail (tail_chain.h, HAS_P1), 256-row workgroups while those fill the
-// chip, else 128-row ones; below: see FWN_TAIL_SPLIT_CHAIN above.
+// chip, else 128-row ones; below: see FWN_TAIL_SPLIT_CHAIN_MIN above.
 
 void fwn_launch_tail(const void* o, long o_stride, int L, const void* Ws, const float* bs, const void* Wf,
                      const float* bfin, const void* Wz, const float* bz, const float* ez, const float* an,
@@ -1135,7 +1120,6 @@ void fwn_launch_tail(const void* o, long o_stride, int L, const void* Ws, const 
         return;
     }
     if (fwn_tail_rows(M) == 256) TAIL_BY_NPT(8, 4, 32, false, true);
-    else if (M >= FWN_TAIL256_MIN) TAIL_BY_NPT(4, 2, 32, true, true);
     else TAIL_BY_NPT(4, 3, 64, true, true);
 #undef TAIL_BY_NPT
 #undef TAIL_LAUNCH

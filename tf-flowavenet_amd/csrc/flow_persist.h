@@ -36,9 +36,6 @@
 #include "../../include/fwn.h"
 
 #define FWN_PS_MAXL 2
-#ifndef FWN_PERSIST_MAX_ROWS
-#define FWN_PERSIST_MAX_ROWS 4096
-#endif
 #define FWN_PS_HDR 8
 
 struct PersistArgs {

@@ -18,8 +18,9 @@ int fwn_flow_persist_sync_words(int M, int L) {
 }
 // whether this flow at this shape runs as one launch: hoisted conditioning, few rows, the N-split tail's row range (so that
 // the log-det partial slots and the S / U buffers are the launch-per-stage path's), n_layer <= 2
+constexpr int FWN_PERSIST_MAX_ROWS = 4096;
 int fwn_flow_persist_ok(int M, int Ch, int L, int npt, bool has_w2, bool xa_aligned) {
-    if (M > FWN_TUNE(FWN_PERSIST_MAX_ROWS, FWN_PERSIST_MAX_ROWS) || L > FWN_PS_MAXL || L < 1) return 0;
+    if (M > FWN_PERSIST_MAX_ROWS || L > FWN_PS_MAXL || L < 1) return 0;
     if (fwn_tail_chain_xb_out(M, npt, 0)) return 0;   // only where the tail (without a fragment stream) is the three N-split ring GEMMs
     if (Ch > 128 || npt < 1 || npt > 4) return 0;
     if (Ch >= 16 && !(has_w2 && xa_aligned)) return 0;
@@ -56,7 +57,7 @@ static void fwn_launch_flow_persist(const PersistArgs& a, hipStream_t st) {
     // with the full grid, 45.7 with 64 workgroups, 45.3 with a launch per stage; one stream: no difference)
     const int RT = (a.M + 63) / 64;
     const int total = RT * ((a.has_front ? 4 : 0) + a.L * 8 + (a.L - 1) * 4 + 8 + a.npt);
-    const int cap = FWN_TUNE(FWN_PERSIST_GRID, 0) > 0 ? FWN_TUNE(FWN_PERSIST_GRID, 0) : RT >= 8 && 8 * RT < ncu ? 8 * RT : ncu;
+    const int cap = RT >= 8 && 8 * RT < ncu ? 8 * RT : ncu;
     const int grid = total < cap ? total : cap;
     hipLaunchKernelGGL(flow_persist_kernel, dim3(grid), dim3(512), 0, st, a);
 }

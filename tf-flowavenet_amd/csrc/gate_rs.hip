@@ -21,10 +21,10 @@ long fwn_gate_stream_size(int cin) {
 // tiles from 12 288 rows on (block 2 of the 8-clip pass, block 1 of a 4-clip pass: 256-row tiles would leave half the CUs empty);
 // 64-row tiles from 6 144 rows on (round 6: block 3 of the 8-clip pass, block 0 of one clip - 252 workgroups of 64 rows where
 // the 128 x 128 tap-sharing tile ran two 67 KB workgroups per CU at 0.22 of the MFMA peak)
-int fwn_gate_stream_min_rows() { return FWN_TUNE(FWN_RS_MIN_ROWS, 6144); }
+int fwn_gate_stream_min_rows() { return 6144; }
 static int gate_stream_mt(int M, int nkc) {
-    if (M >= FWN_TUNE(FWN_RS_MIN_ROWS256, 24576) && rs_has_mt8(nkc)) return 8;
-    return M >= FWN_TUNE(FWN_RS_MIN_ROWS128, 12288) ? 4 : 2;
+    if (M >= 24576 && rs_has_mt8(nkc)) return 8;
+    return M >= 12288 ? 4 : 2;
 }
 int fwn_gate_stream_ok(int M, int Ti, int dil, int cin, bool fused_cond, bool aux) {
     // a tile may cross one clip edge only; dilations whose halo fits the slot

@@ -52,12 +52,10 @@ __global__ void up_finish_kernel(const float* __restrict__ dg3, const float* __r
         dbias[0] = dwb[6 * s];
     }
 }
-__global__ void finish_loss_kernel(const float* __restrict__ out2, const float* __restrict__ an_logdet, float* __restrict__ out3) {
+__global__ void finish_loss_kernel(const float* __restrict__ out2, float* __restrict__ out3) {
     if (threadIdx.x == 0) {
-        // (the tail's log-det partials carry the ActNorm terms: an_logdet, the parameter-only scalar of the un-fused tail of
-        // round 2, is no longer added)
+        // (the tail's log-det partials carry the ActNorm terms)
         const float log_p = out2[0], logdet = out2[1];
-        (void)an_logdet;
         out3[0] = -(log_p + logdet);
         out3[1] = log_p;
         out3[2] = logdet;
@@ -114,7 +112,6 @@ inline int tn_group_splits(const TnSpec* sp, int n, int m) {          // trainin
 // Round 4: the split count of a flow's weight-gradient GEMMs is planned for its BLOCK - with a side stream the groups of all
 // n_flow flows of a block run as one launch (fwn_tn_multi_launch), and the one-stream path uses the same count so that both
 // sum the same partials in the same order (bit-identical results).  `sp`: the jobs of ONE flow.
-inline int tn_plan_flows(int n_flow) { return FWN_TUNE(FWN_TN_BLOCK, 1) ? n_flow : 1; }     // developer switch (tunable build): 0 = every flow on its own, as before
 inline int tn_block_splits(const TnSpec* sp, int n, int n_flow, int m) {
     const int e = fwn_tn_tile(m);
     long tiles = 0;
@@ -172,7 +169,7 @@ long tn_partial_floats(const fwn_model_desc* md, int i, long m) {
     }
     sp[n++] = {ch < 8 ? 8 : ch, 256, 3};
     long tot = 0;
-    const int ns = tn_block_splits(sp, n, tn_plan_flows(md->n_flow), (int)m);
+    const int ns = tn_block_splits(sp, n, md->n_flow, (int)m);
     for (int j = 0; j < n; ++j) tot += (long)ns * ((long)sp[j].ntap * sp[j].kx + 1) * sp[j].n;
     return tot * md->n_flow;
 }
@@ -345,7 +342,6 @@ int fwn_train_loss_and_grads(const fwn_train_desc* t, int64_t B_, int64_t T_, co
              "fwn_train_loss_and_grads: bad n_block / n_flow / n_layer");
     TREQUIRE(B > 0 && T > 0 && T % hop_of(md) == 0 && T % (1L << md->n_block) == 0, "fwn_train_loss_and_grads: T must be a multiple of hop_size and 2^n_block");
     TREQUIRE((int64_t)L * (B * T / 2) * 512 < ((int64_t)1 << 31), "fwn_train_loss_and_grads: B*T too large (2 GiB per activation buffer)");
-    TREQUIRE(t->an_logdet, "fwn_train_loss_and_grads: an_logdet (device scalar) required");
     for (int i = 0; i < md->n_block; ++i)
         TREQUIRE(t->cond_rows[i] && t->front_rows[i] && t->zinv32[i] && t->br[i] && t->zcol[i], "fwn_train_loss_and_grads: missing index table (block %d)", i);
     FlowSaved saved[256];
@@ -424,7 +420,7 @@ int fwn_train_loss_and_grads(const fwn_train_desc* t, int64_t B_, int64_t T_, co
         }
     }
     fwn_launch_prior(pl.planes, B * T, pl.partial_all, pl.npart, 1.0 / (double)(B * T), pl.out2, st);
-    hipLaunchKernelGGL(finish_loss_kernel, dim3(1), dim3(64), 0, st, pl.out2, t->an_logdet, out3);
+    hipLaunchKernelGGL(finish_loss_kernel, dim3(1), dim3(64), 0, st, pl.out2, out3);
 
     // ---------------- backward ----------------
     // The data gradients of a flow are one dependent chain of small launches; its weight gradients (grouped TN GEMM,
@@ -450,9 +446,9 @@ int fwn_train_loss_and_grads(const fwn_train_desc* t, int64_t B_, int64_t T_, co
     };
     std::vector<Deferred> pending;        // the flows of the block whose weight gradients are still to be enqueued
     // Error exits: once anything has been handed to the side stream, EVERY return path joins it into `st` first -
-    // otherwise weight-gradient kernels of up to n_block blocks (defer_block_done: all of them) would keep reading and
-    // writing the caller's workspace and gradient buffers after the call has returned an error.  Event-based, so it is also
-    // legal while the stream is being captured.
+    // otherwise weight-gradient kernels of the block handed over last would keep reading and writing the caller's workspace
+    // and gradient buffers after the call has returned an error.  Event-based, so it is also legal while the stream is being
+    // captured.
     struct SideJoinGuard {
         hipStream_t st, side; EventPool* evp; bool armed;
         ~SideJoinGuard() {
@@ -480,7 +476,7 @@ int fwn_train_loss_and_grads(const fwn_train_desc* t, int64_t B_, int64_t T_, co
         TnList& tn = D.tn;
         TnSpec sp[4 + 5 * FWN_MAX_LAYERS];
         for (int k = 0; k < tn.n; ++k) sp[k] = {tn.job[k].Kx, tn.job[k].N, tn.job[k].ntap};
-        const int ns = tn_block_splits(sp, tn.n, tn_plan_flows(NF), (int)D.m);
+        const int ns = tn_block_splits(sp, tn.n, NF, (int)D.m);
         for (int k = 0; k < tn.n; ++k) {
             fwn_tn_job& q = tn.job[k];
             const long size = ((long)q.ntap * q.Kx + 1) * q.N;
@@ -528,7 +524,7 @@ int fwn_train_loss_and_grads(const fwn_train_desc* t, int64_t B_, int64_t T_, co
         int gn[FWN_MAX_GROUP * 2], ng = 0;
         bool fits = true;
         for (size_t k = 0; k < flows.size(); ++k) ng += (flows[k].tn.n + FWN_MAX_GROUP - 1) / FWN_MAX_GROUP;
-        if (ng > fwn_tn_multi_max() || ng > (int)(sizeof(gn) / sizeof(gn[0])) || !FWN_TUNE(FWN_TN_BLOCK, 1)) fits = false;
+        if (ng > fwn_tn_multi_max() || ng > (int)(sizeof(gn) / sizeof(gn[0]))) fits = false;
         float* part = pl.tn_part;
         for (size_t k = 0; k < flows.size(); ++k) {
             wg_small(flows[k], s_);
@@ -569,32 +565,22 @@ int fwn_train_loss_and_grads(const fwn_train_desc* t, int64_t B_, int64_t T_, co
         hipEvent_t e = evp->get();
         return e && hipEventRecord(e, side) == hipSuccess && hipStreamWaitEvent(st, e, 0) == hipSuccess;
     };
-    // fwn_train_desc.defer_block_done: no consumer of a block's gradients before the end of the call - the chain never
-    // waits for the side stream; ONE join behind block 0, then every block is reported (same order)
-    const bool defer = side && t->defer_block_done != 0;
     auto join_pending = [&]() -> bool {      // the block handed over last: join it into `st`, then report it
         if (pending_block < 0) return true;
-        if (defer && pending_block > 0) { pending_block = -1; return true; }
         if (!join_side()) return false;
-        if (defer) {
-            for (int b_ = md->n_block - 1; b_ >= 0 && !hook_failed; --b_)
-                if (on_block_done && on_block_done(user, b_) != 0) hook_failed = true;
-        } else if (on_block_done && on_block_done(user, pending_block) != 0) hook_failed = true;
+        if (on_block_done && on_block_done(user, pending_block) != 0) hook_failed = true;
         pending_block = -1;
         return true;
     };
     hipEvent_t dca_done = nullptr;          // side stream, block 0: behind the last conditioning-gradient GEMM of the call
     auto hand_over = [&](bool last_block) -> int {          // fork, then everything in `pending` to the side stream
         if (!fork_side()) return fwn_set_error(FWN_ERR_HIP, "fwn_train_loss_and_grads: forking the side stream failed");
-        // (FWN_SKIP_WG: developer builds only - times the data-gradient chain alone; the gradients are then wrong)
-        if (!FWN_TUNE(FWN_SKIP_WG, 0)) {
-            if (last_block) {
-                dca_done = evp->get();
-                if (!dca_done) return fwn_set_error(FWN_ERR_HIP, "fwn_train_loss_and_grads: hipEventCreate failed");
-            }
-            const int rc = weight_grads_block(pending, side, dca_done);
-            if (rc != FWN_OK) return rc;
+        if (last_block) {
+            dca_done = evp->get();
+            if (!dca_done) return fwn_set_error(FWN_ERR_HIP, "fwn_train_loss_and_grads: hipEventCreate failed");
         }
+        const int rc = weight_grads_block(pending, side, dca_done);
+        if (rc != FWN_OK) return rc;
         pending.clear();
         return FWN_OK;
     };

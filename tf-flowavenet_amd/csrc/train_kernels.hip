@@ -292,7 +292,8 @@ int fwn_gemm_launch(const fwn_gemm_desc* g, hipStream_t st) {
         // A workgroup streams (BM + BN) K 2 bytes through ONE CU at ~50 GB/s: a launch of a few dozen 64 x 128 tiles is
         // bound by that, not by the chip.  Below FWN_LIN_TINY such workgroups, 32 x 64 tiles (4-way split-K inside the
         // workgroup): four times the CUs, half the bytes each.
-        if (((M + 63) / 64) * n128 * ns < FWN_TUNE(FWN_LIN_TINY, 40)) {
+        constexpr int FWN_LIN_TINY = 40;
+        if (((M + 63) / 64) * n128 * ns < FWN_LIN_TINY) {
             const int n64 = (g->N + 63) / 64;
             hipLaunchKernelGGL((lin_kernel<32, 64, 1, 1, 6, 4, 128>), dim3(((M + 31) / 32) * n64, 1, ns), dim3(256), 0, st, p, n64, nq128);
         } else
@@ -1131,13 +1132,11 @@ __global__ __launch_bounds__(256) void colsum_bf16_kernel(const bf16* __restrict
     if (part == 0 && c < C)
         partial[(size_t)blockIdx.y * C + c] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
 }
-#ifndef FWN_TN256_MIN
 // 256 x 256 output tiles from 128 rows on (2048 until round 2): the weight-gradient GEMMs of the late blocks - K = a few
 // hundred rows against cin up to 10240 output rows - are bound by writing their output; a quarter of the workgroups does
 // that in fewer rounds (training step -0.18 ms).
-#define FWN_TN256_MIN 128
-#endif
-int fwn_tn_tile(int M) { return M >= FWN_TUNE(FWN_TN256_MIN, FWN_TN256_MIN) ? 256 : 128; }     // output tile edge of the weight-gradient GEMM
+constexpr int FWN_TN256_MIN = 128;
+int fwn_tn_tile(int M) { return M >= FWN_TN256_MIN ? 256 : 128; }     // output tile edge of the weight-gradient GEMM
 static int tn_fill_group(TnGroup& g, const fwn_tn_job* jobs, int njobs, int M, int Ti) {       // -> workgroups of the group
     memset(&g, 0, sizeof(g));
     g.njobs = njobs;

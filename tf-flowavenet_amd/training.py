@@ -11,7 +11,6 @@ arithmetic step runs in ``libfwn.so`` and there is no fallback path (DESIGN.md s
 from __future__ import annotations
 
 import ctypes as C
-import os
 
 from . import _lib
 
@@ -361,7 +360,9 @@ class GradEngine:
     Returns ``(loss, log_p, logdet, grads)`` with grads a dict name -> fp32 device tensor of the
     parameter's shape (``d loss / d param``, loss = -(log_p + logdet), train.py:60)."""
 
-    def __init__(self, hparams, device="cuda"):
+    def __init__(self, hparams, device="cuda", side_stream=True):
+        """side_stream: each block's weight gradients run on a second stream under the next block's backward chain
+        (fwn_train_desc.side_stream); False keeps the one-stream sequence, the bit-for-bit reference of the tests."""
         if not hparams.affine or hparams.causality:
             raise NotImplementedError("affine=True, causality=False only")
         self.hp, self.device = hparams, device
@@ -369,19 +370,17 @@ class GradEngine:
         self._gout = None
         self._on_block = None
         self._own_flat = None
-        # True: no consumer of a block's gradients before the end of the call (fwn_train_desc.defer_block_done; slower, see _run)
-        self.defer_block_done = False
+        self.side_stream = bool(side_stream)
+        self._side = None
 
     # ------------------------------------------------------------------ helpers
     def _side_stream(self, dev):
-        """The second stream of a step (FWN_TRAIN_SIDE=0: none): each block's weight gradients run on it under the next
-        block's backward chain."""
+        """The second stream of a step, or None without one."""
         import torch
-        if os.environ.get("FWN_TRAIN_SIDE", "1") == "0":
+        if not self.side_stream:
             return None
-        if getattr(self, "_side", None) is None:            # an engine serves one device
-            prio = os.environ.get("FWN_TRAIN_SIDE_PRIO")       # developer switch (same-box A/B): HIP stream priority
-            self._side = torch.cuda.Stream(torch.device(dev), priority=int(prio)) if prio else torch.cuda.Stream(torch.device(dev))
+        if self._side is None:            # an engine serves one device
+            self._side = torch.cuda.Stream(torch.device(dev))
         return self._side
 
     def _call(self, name, *args):
@@ -488,26 +487,15 @@ class GradEngine:
         else:
             td, flows = self._desc, self._desc_flows
         # per-step tables (recomputed from the masters before every step: their addresses may move)
-        # fwn_train_desc.an_logdet: unused by the library since round 3 (any device pointer)
-        an_ld = getattr(self, "_an_ld0", None)
-        if an_ld is None or an_ld.device != dev:
-            an_ld = self._an_ld0 = torch.zeros(1, dtype=torch.float32, device=dev)
         for i in range(hp.n_block):
             for j in range(hp.n_flow):
                 f, t = flows[i * hp.n_flow + j], tp.flows[(i, j)]
                 tabs = [t[k] if t[k].is_contiguous() else t[k].contiguous() for k in ("bskip", "bfin", "bz", "ez")]
                 f.bskip, f.bfin, f.bz, f.ez = (x_.data_ptr() for x_ in tabs)
                 t["_tabs_alive"] = tabs
-        td.an_logdet = an_ld.data_ptr()
         # the weight gradients of a block run on a second stream under the next block's chain (fwn.h fwn_train_desc.side_stream)
         side = self._side_stream(dev)
         td.side_stream = side.cuda_stream if side is not None else None
-        # fwn_train_desc.defer_block_done: with nothing to exchange the data-gradient chain need not wait for the side
-        # stream block by block.  Measured (round 4, same box, recorded step at 8 x 6400): 14.30 ms against 13.48 with
-        # the per-block joins - without them the chain's small launches queue behind ever more chip-filling weight-gradient
-        # GEMMs - so it stays off; FWN_TRAIN_DEFER=1 turns it on (same-box A/B)
-        defer = os.environ.get("FWN_TRAIN_DEFER")
-        td.defer_block_done = int(defer) if defer in ("0", "1") else int(bool(self.defer_block_done))
         wkey = (B, T, str(dev), bool(td.side_stream))
         if getattr(self, "_ws_key", None) != wkey:
             need = int(lib.fwn_train_workspace_bytes(C.byref(td), B, T))
@@ -539,7 +527,7 @@ class GradEngine:
             raise failure[0]
         _lib.check(rc, "fwn_train_loss_and_grads")
         td.zero_dead_res = 0
-        self._alive = (masters, an_ld, x, c)           # until the stream has consumed them
+        self._alive = (masters, x, c)           # until the stream has consumed them
         return out3[0], out3[1], out3[2], {k: go[k] for k in shp}
 
 
@@ -550,18 +538,14 @@ class Trainer:
     fp32 masters.  ``ddi`` performs the ActNorm data-dependent init of the first step
     (train.py:221,229 with init=True)."""
 
-    def __init__(self, hparams, params, device="cuda", group=None, graph=None):
+    def __init__(self, hparams, params, device="cuda", group=None, graph=True):
         """graph: record the step into hipGraphs after one eager step per input shape and replay it from then on
-        (the step is ~5700 launches; replaying removes their host cost).  Default: on for GPU devices, off if
-        FWN_TRAIN_GRAPH=0."""
-        import os
+        (the step is ~5700 launches; replaying removes their host cost)."""
         from .optim import DataParallelAdam
         self.hp, self.device = hparams, device
         self.opt = DataParallelAdam(hparams, params, device, group=group, grad_reduce_dtype=getattr(hparams, "grad_reduce_dtype", "fp32"),
                                     exchange=getattr(hparams, "grad_exchange", "allreduce"))
         self.engine = GradEngine(hparams, device)
-        if graph is None:
-            graph = os.environ.get("FWN_TRAIN_GRAPH", "1") != "0"
         self.graph = bool(graph)
         self._recorded = {}
         # False: skip the gradient exchange (bench.py's compute-only step time, to price the overlap)
@@ -613,12 +597,15 @@ class Trainer:
             return self._step_eager(x, c)
         world = dist.get_world_size(self.opt.group) if dist.is_available() and dist.is_initialized() else 1
         if rec == "warm":
+            # cut(-1) below holds for the side-stream sequence only: one stream enqueues the up-sampling backward between
+            # the hooks of block 0 and -1
+            if not self.engine.side_stream:
+                raise RuntimeError("Trainer: the recorded step needs a GradEngine with side_stream=True")
             xs = torch.empty(tuple(x.shape), dtype=torch.float32, device=dev)
             cs = torch.empty(tuple(c.shape), dtype=torch.float32, device=dev)
             params, gv = self.opt.master_views(), self.opt.grad_views()
             segs, pool = [], torch.cuda.graph_pool_handle()
-            mprio = os.environ.get("FWN_TRAIN_MAIN_PRIO")     # developer switch (same-box A/B)
-            side = torch.cuda.Stream(dev, priority=int(mprio)) if mprio else torch.cuda.Stream(dev)
+            side = torch.cuda.Stream(dev)
             side.wait_stream(torch.cuda.current_stream(dev))
             cur = [None]
             try:
@@ -632,8 +619,8 @@ class Trainer:
                         if world == 1 and i >= 0 and not self.opt.force_collectives:
                             return
                         if i == -1 and segs and segs[-1][1] == 0:
-                            # fwn_train_loss_and_grads reports block 0 and then the up-sampling convs (-1) back to back - block 0 is
-                            # joined behind the up-sampling backward since round 5, nothing is enqueued between the two hooks
+                            # fwn_train_loss_and_grads reports block 0 and then the up-sampling convs (-1) back to back - with the
+                            # side stream block 0 is joined behind the up-sampling backward, nothing is enqueued between the two hooks
                             # (csrc/train_api.hip: join_pending, then the -1 hook) - so there is nothing to cut: no empty
                             # hipGraph segment, only the exchange of the up-sampling range to start
                             segs.append((None, -1))

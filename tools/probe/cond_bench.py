@@ -1,8 +1,6 @@
 """Per-launch time of the hoisted conditioning projection (csrc/flow_kernels.hip cond_batch_kernel) at the shapes of the blocks that hoist
 it (B clips x 16 128 samples: blocks 4 - 7 at B = 8, 2 - 7 at B = 1), through the C ABI's fwn_cond_split + fwn_cond_reduce: all 12 (flow, layer) matrices of a
-block in one launch, nsplit K ranges per tile.  Tile shapes are picked inside the library; with the tuning build
-(`make -C tf-flowavenet_amd/csrc tune`, FWN_LIB=.../libfwn_tune.so) FWN_COND_TILE / FWN_COND_SPLIT_TILE override them
-(0 = 256 x 256, 1 = 256 x 128, 2 = 128 x 128, 3 = 64 x 128).
+block in one launch, nsplit K ranges per tile.  Tile shapes are picked inside the library (fwn_cond_tile).
 
     python tools/probe/cond_bench.py [B] [nsplit per block 4..7, comma separated, 0 = the library's choice] [rounds] [nsplit of the streamed form]
 """
@@ -26,7 +24,7 @@ def main():
     st = torch.cuda.current_stream().cuda_stream
     T, nflow, L = 16128, 6, 2
     nz = nflow * L
-    print("B = %d; tiles: FWN_COND_TILE=%s FWN_COND_SPLIT_TILE=%s" % (nb, os.environ.get("FWN_COND_TILE"), os.environ.get("FWN_COND_SPLIT_TILE")))
+    print("B = %d" % nb)
     blocks = [b for b in range(8) if nb * (T // (2 << b)) < 4096 and 40 * (2 << b) >= 256]      # the blocks whose conditioning is hoisted
     splits = (splits + [0] * 8)[:len(blocks)]
     if splits2:

@@ -1,8 +1,8 @@
 """GPU box: device time per launch of the residual layer (fwn_res) at blocks 0 / 1 of the 8-clip pass.
 Round 4 sweep: two 64 KB workgroups per CU (128 x 128 tiles, ring depth 2; the product from
 24 576 rows on) against one 147 KB workgroup (256 x 128, depth 3): 17.6 vs 19.4 us at block 0, 9.3 vs 9.4 at block 1.
-With the tunable build the old tile is one switch away:
-   FWN_LIB=tf-flowavenet_amd/csrc/libfwn_tune.so FWN_RES_TWO_PER_CU=0 python tools/probe/res_tiles.py"""
+To time another tile, change the rule in fwn_launch_res (csrc/flow_kernels.hip) in a second build and run this script on each
+(FWN_LIB selects the build)."""
 import ctypes as C, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch
