@@ -1423,3 +1423,24 @@ def test_an_inference_pack_keeps_no_fp32_copy_of_the_parameters():
     tables = sum(t.numel() * t.element_size() for t in pm.tensors if t.dtype == torch.float32)
     assert W.count_params(hp) * 4 > 2 ** 20
     assert grown <= pm.weight_bytes + tables + 2 ** 20, (grown, pm.weight_bytes, tables)
+
+
+def test_persist_status_is_zero_for_a_fresh_shape_and_after_the_init_pass():
+    """FloWaveNet.persist_status reads the sync words of the last pass.  A (b, t) no pass has run at yet has no workspace: 0,
+    and none is allocated.  The data-dependent init pass runs no flow as one launch, but it zeroes their words like every pass
+    (it used to leave them as the workspace came: a status read after it returned garbage) - the workspace is filled with ones
+    first so that a skipped memset shows."""
+    hp = default_hparams().replace(n_flow=2)          # one clip: blocks 4 - 7 run one launch per flow
+    model = FloWaveNet(hp, init=True).load_params(W.synthetic_params(hp, 1234))
+    T = 16128
+    inp = W.synthetic_inputs(hp, 1, T)
+    x, c = dev(inp["x"]), dev(inp["c"])
+    assert model.persist_status(1, T) == 0 and model.persist_status(2, T) == 0
+    assert not model._ws
+    model._workspace(1, T)
+    model._ws[(1, T, model._stream())].fill_(255)
+    lp, ld = model.forward(x, c)                      # the init pass
+    assert np.isfinite(float(lp)) and np.isfinite(float(ld))
+    assert model.persist_status(1, T) == 0
+    lp, ld = model.forward(x, c)
+    assert np.isfinite(float(lp)) and model.persist_status(1, T) == 0

@@ -477,3 +477,55 @@ def test_dataset_keeps_a_bounded_number_of_file_descriptors_open(tmp_path):
         assert len(ds._cache) <= 4 + 1
     finally:
         T.Dataset.MAX_OPEN = old
+
+
+def _tail_desc(ch, L, npt, stream):
+    """A flow descriptor with dummy (aligned, never dereferenced) weight pointers: the tail queries read only its shape."""
+    import ctypes as C
+    from tf_flowavenet_amd import _lib
+    d = _lib.FlowDesc()
+    d.Ch, d.cin, d.kcpad, d.kfpad, d.npt, d.L = ch, 80 * ch, 80 * ch, 64, npt, L
+    fake = iter(range(1 << 40, 1 << 41, 1 << 12))
+    for name in ("Wfront", "bfront", "Wskip", "bskip", "Wfinal", "bfinal", "Wzero", "bzero", "ezero", "an"):
+        setattr(d, name, next(fake))
+    for l in range(L):
+        d.Wd[l], d.Wc[l], d.bgate[l], d.Wres[l], d.bres[l] = (next(fake) for _ in range(5))
+    if ch >= 16:
+        d.Wfront2 = next(fake)
+    if stream:
+        d.Wts = next(fake)
+    return C.byref(d), d
+
+
+def test_tail_slot_counts_stay_within_the_public_bounds_and_chaining_agrees():
+    """The workspace sizing reserves fwn_tail_partials / fwn_tail_partials_chained slots per flow: the exact count of every mode
+    of fwn_tail_partials_desc must fit under them, and fwn_tail_can_chain must name the form fwn_tail_partials_desc counts.
+    M from 1 to 2^17, with and without the tail's fragment stream."""
+    from tf_flowavenet_amd import _lib
+    lib = _lib.load()
+    ms = sorted({1, 2, 63, 64, 65, 1 << 17} | {int(round(2 ** (e / 8.0))) for e in range(8 * 17 + 1)} |
+                {b + o for b in (1008, 4096, 6144, 12288, 49152) for o in (-1, 0, 1)})
+    for ch in (1, 2, 4, 8, 16, 32, 64, 128):
+        npt = max(1, (ch + 31) // 32)
+        for L in (1, 2, 3):
+            for stream in (False, True):
+                if stream and (npt != 1 or L != 2):
+                    continue        # a fragment stream exists for L = 2, one ZeroConv tile only (check_desc)
+                dp, _ = _tail_desc(ch, L, npt, stream)
+                for m in ms:
+                    plain, chained, front = (lib.fwn_tail_partials_desc(dp, m, k) for k in (-1, 0, 1))
+                    assert 0 < plain <= lib.fwn_tail_partials(m), (ch, L, stream, m)
+                    assert chained <= lib.fwn_tail_partials_chained(m, ch, 0), (ch, L, stream, m)
+                    assert front <= lib.fwn_tail_partials_chained(m, ch, 1), (ch, L, stream, m)
+                    can, can_front = lib.fwn_tail_can_chain(dp, m, 0), lib.fwn_tail_can_chain(dp, m, 1)
+                    assert can or not can_front, (ch, L, stream, m)
+                    # the counts name the form: the three-launch N-split tail (8 slots per 64-row tile, never chained)
+                    # or one slot per workgroup of `rows` rows, rows - 2 with a chained front conv
+                    if not can:
+                        assert not can_front and plain == front == 8 * -(-m // 64), (ch, L, stream, m)
+                        continue
+                    rows = [r for r in (32, 64, 128, 256) if -(-m // r) == plain]
+                    assert rows, (ch, L, stream, m)
+                    if can_front:       # the front conv rides Ch <= 8 tails; its tiles overlap by one row on either side
+                        assert ch <= 8 and npt == 1, (ch, L, stream, m)
+                        assert front in {-(-m // (r - 2)) for r in rows}, (ch, L, stream, m)

@@ -34,6 +34,34 @@ static int check_launch(const char* what) {
 #define REQUIRE(cond, ...) do { if (!(cond)) return fail(FWN_ERR_ARG, __VA_ARGS__); } while (0)
 #define ALIGNED16(p) ((((uintptr_t)(p)) & 15) == 0)
 
+// ---- the hoisted conditioning of one block (inference and training; each has its own hoisting rule) ----
+fwn_cond_plan fwn_plan_cond(bool hoist, int M, int nflow, int L, int cin, int kcpad, const void* stream) {
+    fwn_cond_plan cp{hoist, nullptr, false, 1};
+    if (!hoist) return cp;
+    if (fwn_cond_rs_wanted(M, cin, kcpad, nflow * L, stream != nullptr)) {
+        cp.stream = stream;
+        cp.nsplit = fwn_cond_rs_nsplit(M, nflow * L, kcpad);
+    } else {
+        const int nzg = ((nflow + 1) / 2) * L;
+        cp.nsplit = fwn_cond_nsplit(M, nzg, kcpad);
+        cp.merged = nflow > 1 && fwn_cond_merge(M, nzg, cp.nsplit);
+    }
+    return cp;
+}
+void fwn_run_cond(const fwn_cond_plan& cp, const void* ca0, const void* ca1, const void* Wc0, float* P, float* Ppart, int M, int nflow,
+                  int L, int cin, int kcpad, hipStream_t st) {
+    const long pn = (long)nflow * L * M * 512;          // floats of the block's P matrices
+    if (cp.stream)          // the block's matrices from their fragment streams (csrc/cond_rs.h)
+        fwn_launch_cond_rs(ca0, nflow > 1 ? ca1 : nullptr, cp.stream, P, nflow * L, L, M, cin, kcpad, Ppart, pn, cp.nsplit, st);
+    else if (cp.merged)
+        fwn_launch_cond2(ca0, ca1, Wc0, P, (long)512 * kcpad, (long)M * 512, 0, 1, nflow, L, M, cin, kcpad, Ppart, pn, cp.nsplit, st);
+    else
+        for (int g = 0; g < 2 && g < nflow; ++g)
+            fwn_launch_cond(g ? ca1 : ca0, Wc0, P, (long)512 * kcpad, (long)M * 512, g, 2, (nflow - g + 1) / 2, L, M, cin, kcpad, Ppart,
+                            pn, cp.nsplit, st);
+    fwn_launch_cond_reduce(P, Ppart, pn, cp.nsplit, pn, st);
+}
+
 extern "C" {
 
 int fwn_version(void) { return FWN_VERSION; }
@@ -316,8 +344,8 @@ int fwn_cond_stream(const void* ca, const void* ca_odd, const void* Ws, float* P
     return check_launch("fwn_cond_stream");
 }
 
-// 32-row tiles per workgroup of the register-streamed tail when that kernel serves flow d at M rows, else 0
-static int desc_rs_mt(const fwn_flow_desc* d, int M) { return fwn_tail_rs_mt(M, d->L, d->Ch, d->npt, d->Wts != nullptr); }
+// the tail that serves flow d at M rows
+static TailForm desc_tail(const fwn_flow_desc* d, int M) { return fwn_tail_form(M, d->L, d->Ch, d->npt, d->Wts != nullptr); }
 
 int64_t fwn_tail_stream_bytes(int L) { return L > 0 ? (int64_t)fwn_tail_stream_size(L) : 0; }
 int fwn_tail_stream_rows(void) { return fwn_tail_stream_min_rows(); }
@@ -341,7 +369,7 @@ int fwn_tail(const fwn_flow_desc* d, const void* o, float* xa, float* xb, float*
     int rc = check_desc(d);
     if (rc) return rc;
     REQUIRE(o && xa && xb && M > 0, "fwn_tail: bad argument");
-    REQUIRE(!fwn_tail_is_split(M) || scratch || desc_rs_mt(d, M), "fwn_tail: M=%d runs the N-split tail: pass scratch [2][M][256] bf16", M);
+    REQUIRE(scratch || !desc_tail(d, M).scratch, "fwn_tail: M=%d runs the N-split tail: pass scratch [2][M][256] bf16", M);
     REQUIRE(!scratch || ALIGNED16(scratch), "fwn_tail: scratch must be 16-byte aligned");
     fwn_launch_tail(o, (long)M * 256, d->L, d->Wskip, d->bskip, d->Wfinal, d->bfinal, d->Wzero, d->bzero,
                     d->ezero, d->an, xa, xb, partial, M, d->Ch, d->npt, inverse, scratch,
@@ -350,25 +378,20 @@ int fwn_tail(const fwn_flow_desc* d, const void* o, float* xa, float* xb, float*
 }
 
 int fwn_tail_can_chain(const fwn_flow_desc* d, int M, int with_front) {
-    if (!d || M <= 0 || !fwn_tail_chain_xb_out(M, d->npt, desc_rs_mt(d, M))) return 0;
-    return with_front ? (fwn_tail_chain_front(M, d->Ch, d->npt, desc_rs_mt(d, M)) ? 1 : 0) : 1;
+    if (!d || M <= 0) return 0;
+    const TailForm f = desc_tail(d, M);
+    return with_front ? f.front : f.xb_out;
 }
-// the public counts are upper bounds over the kernels that may serve the shape (which one runs depends on the flow's packed
-// operands): callers zero the buffer, a launch writes its first n slots
-static int tail_partials_bound(int M, int Ch, int front) {
-    int n = fwn_tail_npartials_chain(M, Ch, front, 0);
-    const int mt = fwn_tail_rs_mt(M, 2, 1, 1, true);
-    if (mt) { const int b = fwn_tail_npartials_chain(M, Ch, front, mt); n = b > n ? b : n; }
-    return n;
+// the public counts are upper bounds over the forms that may serve the shape (which one runs depends on the flow's packed
+// operands: with or without the fragment stream): callers zero the buffer, a launch writes its first n slots
+static int tail_partials_bound(int M, bool front) {
+    const int a = fwn_tail_slots(fwn_tail_form(M, 2, 1, 1, false), M, front), b = fwn_tail_slots(fwn_tail_form(M, 2, 1, 1, true), M, front);
+    return a > b ? a : b;
 }
-int fwn_tail_partials_chained(int M, int Ch, int with_front) { return M > 0 ? tail_partials_bound(M, Ch, with_front != 0) : 0; }
+int fwn_tail_partials_chained(int M, int Ch, int with_front) { return M > 0 ? tail_partials_bound(M, with_front != 0) : 0; }
 // exact: the slots the tail of flow d writes at M rows - mode -1: fwn_tail / fwn_tail_train (in place), 0: fwn_tail_chained
 // without a next flow, 1: with one
-int fwn_tail_partials_desc(const fwn_flow_desc* d, int M, int mode) {
-    if (!d || M <= 0) return 0;
-    const int mt = desc_rs_mt(d, M);
-    return mode < 0 ? fwn_tail_npartials(M, mt) : fwn_tail_npartials_chain(M, d->Ch, mode != 0, mt);
-}
+int fwn_tail_partials_desc(const fwn_flow_desc* d, int M, int mode) { return d && M > 0 ? fwn_tail_slots(desc_tail(d, M), M, mode > 0) : 0; }
 int fwn_tail_chained(const fwn_flow_desc* d, const fwn_flow_desc* next, const void* o, float* xa, const float* xb, float* xb_out,
                      void* h0_next, float* partial, int M, int Ti, int inverse, void* scratch, void* stream) {
     int rc = check_desc(d);
@@ -378,7 +401,7 @@ int fwn_tail_chained(const fwn_flow_desc* d, const fwn_flow_desc* next, const vo
     REQUIRE(fwn_tail_can_chain(d, M, next != nullptr), "fwn_tail_chained: the tail at M=%d, Ch=%d cannot chain%s", M, d->Ch, next ? " a front conv" : "");
     REQUIRE(!next || (h0_next && ALIGNED16(h0_next) && next->Wfront3 && next->kf3 > 0 && next->Ch == d->Ch),
             "fwn_tail_chained: next needs Wfront3 / kf3, the same Ch, and h0_next");
-    REQUIRE(!fwn_tail_is_split(M) || scratch || desc_rs_mt(d, M), "fwn_tail_chained: M=%d runs the N-split tail: pass scratch [2][M][256] bf16", M);
+    REQUIRE(scratch || !desc_tail(d, M).scratch, "fwn_tail_chained: M=%d runs the N-split tail: pass scratch [2][M][256] bf16", M);
     fwn_tail_chain tc;
     memset(&tc, 0, sizeof(tc));
     tc.xb_out = xb_out;
@@ -410,7 +433,7 @@ int fwn_tail_train(const fwn_flow_desc* d, const void* o, int64_t o_stride, floa
     return check_launch("fwn_tail_train");
 }
 
-int fwn_tail_partials(int M) { return M > 0 ? tail_partials_bound(M, 0, 0) : 0; }
+int fwn_tail_partials(int M) { return M > 0 ? tail_partials_bound(M, false) : 0; }
 
 // ddi: 0 none, 1 local two-pass init, 2 moments -> reduce callback (may be NULL) -> tables
 // Chain context of one flow inside a whole-model call (NULL: a flow on its own, everything in place).
@@ -460,7 +483,7 @@ static int flow_run_impl(const fwn_flow_desc* d, int64_t B, int64_t T, float* xa
         if (!inside)
             fwn_launch_front(xa, d->an, d->Wfront, d->Wfront2, d->bfront, h0, h1, M, Ti, d->Ch, d->kfpad, inverse ? 0 : 1, nullptr, st);
         fwn_launch_flow_persist_desc(d, xa, xb, h0, h1, o, P, inverse ? nullptr : partial, sync, M, Ti, inverse, inside, st);
-        if (chain) { chain->h0_next = nullptr; chain->n_partial = fwn_tail_npartials_chain(M, d->Ch, false, 0); }
+        if (chain) { chain->h0_next = nullptr; chain->n_partial = fwn_tail_slots(fwn_tail_form(M, d->L, d->Ch, d->npt, false), M, false); }
         return check_launch("fwn_flow_run_persist");
     }
     void* h8c = h8a;
@@ -496,7 +519,7 @@ static int flow_run_impl(const fwn_flow_desc* d, int64_t B, int64_t T, float* xa
             tc.Wfn = nx->Wfront3; tc.bfn = nx->bfront; tc.an_next = inverse ? nullptr : nx->an; tc.kfn = nx->kf3; tc.Ti = Ti;
             chain->h0_next = hc;
         }
-        chain->n_partial = fwn_tail_npartials_chain(M, d->Ch, tc.h0_next != nullptr, desc_rs_mt(d, M));
+        chain->n_partial = fwn_tail_slots(desc_tail(d, M), M, tc.h0_next != nullptr);
     }
     fwn_launch_tail(o, (long)M * 256, d->L, d->Wskip, d->bskip, d->Wfinal, d->bfinal, d->Wzero, d->bzero,
                     d->ezero, d->an, xa, xb, inverse ? nullptr : partial, M, d->Ch, d->npt, inverse, hn, hc, chain ? &tc : nullptr, d->Wts, st);
@@ -762,13 +785,10 @@ int fwn_clip_adam_dev(float* w, const float* g, float* m, float* v, int64_t n, c
 // ---------------------------------------------------------------------------------------------
 // Whole-model sequencing
 // ---------------------------------------------------------------------------------------------
-struct Carve {
-    size_t cplanes, up0, up1, planes, plane3, h0, h1, o, P, Ppart, partial, mom, h8a, h8b, sync, total;
-    size_t sync_stride, sync_bytes;       // one block of counters per flow (flow_persist.h), zeroed once per pass
-    int n_partial;
-};
 static size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
 
+// Inference's hoisting rule (training keeps its own, train_api.hip: it hoists below 4096 rows whatever cin - on purpose, the
+// two differ).  cond_mode 1: never, 2: always.
 static bool hoist_cond(const fwn_model_desc* m, int64_t M, int cin) {
     if (m->cond_mode == 1) return false;
     if (m->cond_mode == 2) return true;
@@ -777,28 +797,25 @@ static bool hoist_cond(const fwn_model_desc* m, int64_t M, int cin) {
     constexpr int FWN_HOIST_M = 4096, FWN_HOIST_CIN = 256;
     return M < FWN_HOIST_M && cin >= FWN_HOIST_CIN;
 }
-// the register-streamed conditioning projection (csrc/cond_rs.h) serves this block at M rows: its stream is given
-static bool block_cond_rs(const fwn_model_desc* m, int blk, int64_t M) {
-    const fwn_flow_desc* f0 = &m->flows[blk * m->n_flow];
-    return blk < 16 && fwn_cond_rs_wanted((int)M, f0->cin, f0->kcpad, m->n_flow * m->n_layer, m->cond_stream[blk] != nullptr);
-}
-// K splits of the block's hoisted conditioning launch (sizes the partial buffer of the workspace, too)
-static int block_cond_nsplit(const fwn_model_desc* m, int blk, int64_t M) {
-    const fwn_flow_desc* f0 = &m->flows[blk * m->n_flow];
-    if (block_cond_rs(m, blk, M)) return fwn_cond_rs_nsplit((int)M, m->n_flow * m->n_layer, f0->kcpad);
-    return fwn_cond_nsplit((int)M, ((m->n_flow + 1) / 2) * m->n_layer, f0->kcpad);
-}
 
-// whether block blk's flows run as one launch each (flow_persist.h)
-static bool persist_block(const fwn_model_desc* m, int64_t M, int blk) {
+// What a whole-model pass runs for one block, decided once per (m, B, T) by carve(): the workspace sizing, the conditioning
+// launch, the flow loop and fwn_model_persist_status all read it.
+struct BlockPlan {
+    int64_t M;               // rows of the block's matrices
+    fwn_cond_plan cond;      // hoisted conditioning (cond.hoist) and the launch that computes it
+    bool one_launch;         // its flows run as one launch each (flow_persist.h)
+    int slots;               // log-det partial slots reserved per flow: its tail runs plain or chained (overlapping tiles)
+};
+
+// whether block b's flows run as one launch each (flow_persist.h); d: its first flow
+static bool persist_block(const fwn_model_desc* m, const BlockPlan& b, const fwn_flow_desc* d) {
     // 0: where it measured ahead of the launch-per-stage path (<= 512 rows: blocks 4 - 7 of one clip, block 7 of the 8-clip
     // pass - there with one level's worth of workgroups, flow_persist.h's launcher), 1: nowhere,
     // 2: wherever the form exists.  Same results bit for bit either way.
     if (m->persist_mode == 1) return false;       // (gate_fp8 models too: fp8 taps need fused conditioning and >= 12288 rows - never these blocks)
     constexpr int FWN_PERSIST_AUTO_ROWS = 512;
-    if (m->persist_mode != 2 && M > FWN_PERSIST_AUTO_ROWS) return false;
-    const fwn_flow_desc* d = &m->flows[blk * m->n_flow];
-    return hoist_cond(m, M, d->cin) && fwn_flow_persist_ok((int)M, d->Ch, d->L, d->npt, d->Wfront2 != nullptr, true);
+    if (m->persist_mode != 2 && b.M > FWN_PERSIST_AUTO_ROWS) return false;
+    return b.cond.hoist && fwn_flow_persist_ok((int)b.M, d->Ch, d->L, d->npt, d->Wfront2 != nullptr, true);
 }
 
 static int hop_of(const fwn_model_desc* m) {
@@ -835,11 +852,6 @@ static int check_model(const fwn_model_desc* m, int64_t B, int64_t T) {
     return FWN_OK;
 }
 
-static int tail_partials_max(int M, int Ch) {       // a flow's tail runs plain or chained (overlapping tiles): room for either
-    const int a = tail_partials_bound(M, Ch, 0), b = tail_partials_bound(M, Ch, 1);
-    return a > b ? a : b;
-}
-
 // ---- plane bookkeeping of the chained flows ----
 // The flow state lives in two fp32 planes (even / odd samples).  A chained tail writes out_b to a third buffer (its
 // neighbours still read the old rows), so the three buffers rotate: `at[k]` = where logical plane k lives now.
@@ -869,6 +881,12 @@ static int planes_go_home(Planes& pl, size_t plane_bytes, hipStream_t st) {   //
     return 0;
 }
 
+struct Carve {
+    size_t cplanes, up0, up1, planes, plane3, h0, h1, o, P, Ppart, partial, mom, h8a, h8b, sync, total;
+    size_t sync_stride, sync_bytes;       // one block of counters per flow (flow_persist.h), zeroed once per pass
+    BlockPlan blk[16];
+};
+
 static Carve carve(const fwn_model_desc* m, int64_t B, int64_t T) {
     Carve c;
     size_t off = 0;
@@ -885,32 +903,33 @@ static Carve carve(const fwn_model_desc* m, int64_t B, int64_t T) {
     c.o = off; off = align_up(off + (size_t)m->n_layer * Mmax * 256 * 2);
     size_t pbytes = 0, ppart = 0;
     int npart = 0;
+    c.sync_stride = 0;
     for (int i = 0; i < m->n_block; ++i) {
-        const int64_t M = B * T / ((int64_t)2 << i);
-        if (hoist_cond(m, M, m->flows[i * m->n_flow].cin)) {
-            const size_t need = (size_t)m->n_flow * m->n_layer * M * 512 * 4;
+        BlockPlan& b = c.blk[i];
+        const fwn_flow_desc* f0 = &m->flows[i * m->n_flow];
+        b.M = B * T / ((int64_t)2 << i);
+        b.cond = fwn_plan_cond(hoist_cond(m, b.M, f0->cin), (int)b.M, m->n_flow, m->n_layer, f0->cin, f0->kcpad, m->cond_stream[i]);
+        b.one_launch = persist_block(m, b, f0);
+        b.slots = fwn_tail_partials_chained((int)b.M, f0->Ch, 1);       // chained with a front conv: the most tiles
+        if (b.cond.hoist) {
+            const size_t need = (size_t)m->n_flow * m->n_layer * b.M * 512 * 4;
             if (need > pbytes) pbytes = need;
-            const size_t sp = (size_t)(block_cond_nsplit(m, i, M) - 1) * need;
+            const size_t sp = (size_t)(b.cond.nsplit - 1) * need;
             if (sp > ppart) ppart = sp;
         }
-        npart += m->n_flow * tail_partials_max((int)M, m->flows[i * m->n_flow].Ch);
+        npart += m->n_flow * b.slots;
+        if (b.one_launch) {
+            const size_t w = (size_t)fwn_flow_persist_sync_words((int)b.M, m->n_layer) * 4;
+            if (w > c.sync_stride) c.sync_stride = w;
+        }
     }
     c.P = off; off = align_up(off + pbytes);
     c.Ppart = off; off = align_up(off + ppart);        // split-K partials of the hoisted conditioning (few rows)
     c.partial = off; off = align_up(off + (size_t)npart * 4);
-    c.n_partial = npart;
     // per-flow moment buffers of the data-parallel ActNorm init: 4 Ch + 1 doubles each, Ch <= 2^(n_block-1)
     c.mom = off; off = align_up(off + (size_t)m->n_block * m->n_flow * (4 * ((size_t)1 << (m->n_block - 1)) + 1) * 8);
     c.h8a = off; off = align_up(off + (m->gate_fp8 ? Mmax * 256 : 0));      // e4m3 copies of h (fp8 gate path)
     c.h8b = off; off = align_up(off + (m->gate_fp8 ? Mmax * 256 : 0));
-    c.sync_stride = 0;
-    for (int i = 0; i < m->n_block; ++i) {
-        const int64_t M = B * T / ((int64_t)2 << i);
-        if (persist_block(m, M, i)) {
-            const size_t w = (size_t)fwn_flow_persist_sync_words((int)M, m->n_layer) * 4;
-            if (w > c.sync_stride) c.sync_stride = w;
-        }
-    }
     c.sync_bytes = c.sync_stride * (size_t)m->n_block * m->n_flow;
     c.sync = off; off = align_up(off + c.sync_bytes);
     c.total = off;
@@ -936,31 +955,6 @@ static void run_upsample(const fwn_model_desc* m, int64_t B, int64_t T, const fl
     }
 }
 
-static void run_cond_groups(const fwn_model_desc* m, int blk, int64_t M, const int* parity_of_flow,
-                            char* ws, const Carve& c, int64_t B, int64_t T, hipStream_t st) {
-    const fwn_flow_desc* f0 = &m->flows[blk * m->n_flow];
-    const size_t half = m->num_mels / 2;
-    const size_t plane_elems = (size_t)B * T * half;
-    const long pn = (long)m->n_flow * m->n_layer * M * 512;          // floats of the block's P matrices
-    const int ns = block_cond_nsplit(m, blk, M);
-    // even flows of the block read plane parity_of_flow[0], odd flows the other: one launch or one per parity group
-    const char* ca0 = ws + c.cplanes + (size_t)parity_of_flow[0] * plane_elems * 2;
-    const char* ca1 = ws + c.cplanes + (size_t)parity_of_flow[1] * plane_elems * 2;
-    const int nzg = ((m->n_flow + 1) / 2) * m->n_layer;
-    if (block_cond_rs(m, blk, M)) {        // the block's matrices from their fragment streams (csrc/cond_rs.h)
-        fwn_launch_cond_rs(ca0, m->n_flow > 1 ? ca1 : nullptr, m->cond_stream[blk], (float*)(ws + c.P), m->n_flow * m->n_layer, m->n_layer,
-                           (int)M, f0->cin, f0->kcpad, (float*)(ws + c.Ppart), pn, ns, st);
-    } else if (m->n_flow > 1 && fwn_cond_merge((int)M, nzg, ns)) {
-        fwn_launch_cond2(ca0, ca1, f0->Wc[0], (float*)(ws + c.P), (long)512 * f0->kcpad, (long)M * 512, 0, 1, m->n_flow,
-                         m->n_layer, (int)M, f0->cin, f0->kcpad, (float*)(ws + c.Ppart), pn, ns, st);
-    } else {
-        for (int g = 0; g < 2 && g < m->n_flow; ++g)
-            fwn_launch_cond(g ? ca1 : ca0, f0->Wc[0], (float*)(ws + c.P), (long)512 * f0->kcpad, (long)M * 512, g, 2, (m->n_flow - g + 1) / 2,
-                            m->n_layer, (int)M, f0->cin, f0->kcpad, (float*)(ws + c.Ppart), pn, ns, st);
-    }
-    fwn_launch_cond_reduce((float*)(ws + c.P), (const float*)(ws + c.Ppart), pn, ns, pn, st);
-}
-
 static int check_block_contiguity(const fwn_model_desc* m, int blk) {
     const fwn_flow_desc* f0 = &m->flows[blk * m->n_flow];
     const size_t stride = (size_t)512 * f0->kcpad * 2;
@@ -982,9 +976,9 @@ static FlowChain flow_chain(const fwn_model_desc* m, const fwn_flow_desc* d, con
     memset(&ch, 0, sizeof(ch));
     // (a block whose flows run as ONE launch each - flow_persist.h - does not chain: that form holds the whole flow already)
     const bool on = m->chain_mode != 1 && !one_launch;
-    const int rs_mt = desc_rs_mt(d, M);
-    ch.xb_out = (on && fwn_tail_chain_xb_out(M, d->npt, rs_mt)) ? spare : nullptr;
-    ch.next = (ch.xb_out && next && !init && !m->gate_fp8 && next->Wfront3 && next->kf3 > 0 && fwn_tail_chain_front(M, d->Ch, d->npt, rs_mt)) ? next : nullptr;
+    const TailForm f = desc_tail(d, M);
+    ch.xb_out = (on && f.xb_out) ? spare : nullptr;
+    ch.next = (ch.xb_out && next && !init && !m->gate_fp8 && next->Wfront3 && next->kf3 > 0 && f.front) ? next : nullptr;
     ch.have_h0 = have_h0;
     return ch;
 }
@@ -1016,90 +1010,20 @@ int fwn_model_persist_status(const fwn_model_desc* m, int64_t B, int64_t T, cons
     return 0;
 }
 
-static int model_forward_impl(const fwn_model_desc* m, int64_t B, int64_t T, const float* x, const float* mel,
-                              void* workspace, size_t workspace_bytes, float* out2, float* z_planes, int init,
-                              fwn_reduce_fn reduce, void* user, void* stream) {
+// One pass over the blocks and flows in either direction.  Forward: blocks and flows in order, the parity flipped after each
+// flow (change_order, model.py:190); it collects the log-det partials and runs the data-dependent init (init 1: local, 2:
+// moments -> reduce callback), and ends in the prior.  Reverse: both orders backwards, the parity flipped before each flow
+// (model.py:199); it ends in the merge of the planes into x_out.  A block's plan (carve) decides its conditioning launch and
+// whether its flows run as one launch each; the init pass runs no flow as one launch, but zeroes the sync region all the same.
+static int model_pass(const fwn_model_desc* m, int64_t B, int64_t T, const float* in, const float* mel, void* workspace,
+                      size_t workspace_bytes, bool reverse, int init, fwn_reduce_fn reduce, void* user, float* out2, float* z_planes,
+                      float* x_out, void* stream) {
+    const char* what = reverse ? "fwn_model_reverse" : "fwn_model_forward";
     int rc = check_model(m, B, T);
     if (rc) return rc;
-    REQUIRE(x && mel && workspace && out2, "fwn_model_forward: null pointer");
+    REQUIRE(in && mel && workspace && (reverse ? x_out : out2), "%s: null pointer", what);
     REQUIRE((((uintptr_t)workspace) & 255) == 0, "workspace must be 256-byte aligned");
-    const Carve c = carve(m, B, T);
-    if (workspace_bytes < c.total)
-        return fail(FWN_ERR_WORKSPACE, "workspace %zu < required %zu bytes", workspace_bytes, c.total);
-    hipStream_t st = (hipStream_t)stream;
-    char* ws = (char*)workspace;
-    const size_t half = m->num_mels / 2;
-    const size_t cplane_bytes = (size_t)B * T * half * 2;
-    const size_t plane_elems = (size_t)B * T / 2;
-    float* planes = (float*)(ws + c.planes);
-
-    run_upsample(m, B, T, mel, ws, c, st);
-    fwn_launch_split(x, B, T, planes, st);
-    if (c.sync_bytes && !init && hipMemsetAsync(ws + c.sync, 0, c.sync_bytes, st) != hipSuccess)
-        return fail(FWN_ERR_HIP, "fwn_model_forward: hipMemsetAsync failed");
-    int p = 0;
-    float* partial = (float*)(ws + c.partial);
-    int poff = 0;
-    Planes pl{{planes, planes + plane_elems}, (float*)(ws + c.plane3), {planes, planes + plane_elems}};
-    for (int i = 0; i < m->n_block; ++i) {
-        if (record_block_event(m, i, st)) return fail(FWN_ERR_HIP, "fwn_model_forward: hipEventRecord failed");
-        const int64_t M = B * T / ((int64_t)2 << i);
-        const bool hoist = hoist_cond(m, M, m->flows[i * m->n_flow].cin);
-        if (hoist) {
-            rc = check_block_contiguity(m, i);
-            if (rc) return rc;
-            const int par[2] = {p, p ^ 1};
-            run_cond_groups(m, i, M, par, ws, c, B, T, st);
-        }
-        void* hA = ws + c.h0;
-        void* hB = ws + c.h1;
-        int have_h0 = 0;
-        for (int j = 0; j < m->n_flow; ++j) {
-            const fwn_flow_desc* d = &m->flows[i * m->n_flow + j];
-            const void* ca = hoist ? nullptr : (const void*)(ws + c.cplanes + (size_t)p * cplane_bytes);
-            const float* P = hoist ? (const float*)(ws + c.P) + (size_t)j * m->n_layer * M * 512 : nullptr;
-            double* mom = (double*)(ws + c.mom) + (size_t)(i * m->n_flow + j) * (4 * ((size_t)1 << (m->n_block - 1)) + 1);
-            unsigned* sync = (!init && persist_block(m, M, i)) ? (unsigned*)(ws + c.sync + (size_t)(i * m->n_flow + j) * c.sync_stride) : nullptr;
-            FlowChain ch = flow_chain(m, d, j + 1 < m->n_flow ? d + 1 : nullptr, (int)M, init != 0, pl.spare, have_h0, sync != nullptr);
-            rc = flow_run_impl(d, B, T, pl.at[p], pl.at[p ^ 1], ca, hA, hB, ws + c.o, P, partial + poff, 0, init, mom, reduce, user,
-                               m->gate_fp8 ? ws + c.h8a : nullptr, m->gate_fp8 ? ws + c.h8b : nullptr, &ch, stream, sync);
-            if (rc) return rc;
-            poff += ch.n_partial;
-            planes_after_flow(pl, p, ch.xb_out != nullptr);
-            have_h0 = ch.h0_next != nullptr;
-            if (have_h0 && ch.h0_next != hA) { void* t = hA; hA = hB; hB = t; }
-            p ^= 1;   // change_order (model.py:190)
-        }
-    }
-    if (record_block_event(m, m->n_block, st)) return fail(FWN_ERR_HIP, "fwn_model_forward: hipEventRecord failed");
-    if (planes_go_home(pl, plane_elems * 4, st)) return fail(FWN_ERR_HIP, "fwn_model_forward: plane copy failed");
-    fwn_launch_prior(planes, (long)(B * T), partial, poff, 1.0 / (double)(B * T), out2, st);
-    if (z_planes) {
-        hipError_t e = hipMemcpyAsync(z_planes, planes, (size_t)B * T * 4, hipMemcpyDeviceToDevice, st);
-        if (e != hipSuccess) return fail(FWN_ERR_HIP, "hipMemcpyAsync: %s", hipGetErrorString(e));
-    }
-    return check_launch("fwn_model_forward");
-}
-
-int fwn_model_forward(const fwn_model_desc* m, int64_t B, int64_t T, const float* x, const float* mel,
-                      void* workspace, size_t workspace_bytes, float* out2, float* z_planes, int init,
-                      void* stream) {
-    return model_forward_impl(m, B, T, x, mel, workspace, workspace_bytes, out2, z_planes, init ? 1 : 0, nullptr, nullptr,
-                              stream);
-}
-int fwn_model_forward_init(const fwn_model_desc* m, int64_t B, int64_t T, const float* x, const float* mel,
-                           void* workspace, size_t workspace_bytes, float* out2, float* z_planes,
-                           fwn_reduce_fn reduce, void* user, void* stream) {
-    return model_forward_impl(m, B, T, x, mel, workspace, workspace_bytes, out2, z_planes, 2, reduce, user, stream);
-}
-
-int fwn_model_reverse(const fwn_model_desc* m, int64_t B, int64_t T, const float* z, const float* mel,
-                      void* workspace, size_t workspace_bytes, float* x_out, void* stream) {
-    int rc = check_model(m, B, T);
-    if (rc) return rc;
-    REQUIRE(z && mel && workspace && x_out, "fwn_model_reverse: null pointer");
-    REQUIRE((((uintptr_t)workspace) & 255) == 0, "workspace must be 256-byte aligned");
-    REQUIRE(((m->n_block * m->n_flow) & 1) == 0,
+    REQUIRE(!reverse || ((m->n_block * m->n_flow) & 1) == 0,
             "reverse with odd n_block*n_flow ends in swapped channel order (model.py:199,254); unsupported");
     const Carve c = carve(m, B, T);
     if (workspace_bytes < c.total)
@@ -1109,52 +1033,84 @@ int fwn_model_reverse(const fwn_model_desc* m, int64_t B, int64_t T, const float
     const size_t half = m->num_mels / 2;
     const size_t cplane_bytes = (size_t)B * T * half * 2;
     const size_t plane_elems = (size_t)B * T / 2;
+    const size_t mom_stride = 4 * ((size_t)1 << (m->n_block - 1)) + 1;
     float* planes = (float*)(ws + c.planes);
+    const int nf = m->n_flow, L = m->n_layer;
 
     run_upsample(m, B, T, mel, ws, c, st);
-    fwn_launch_split(z, B, T, planes, st);   // the n_block pre-squeezes of model.py:374-392 are index math
+    fwn_launch_split(in, B, T, planes, st);   // (reverse: the n_block pre-squeezes of model.py:374-392 are index math)
     if (c.sync_bytes && hipMemsetAsync(ws + c.sync, 0, c.sync_bytes, st) != hipSuccess)
-        return fail(FWN_ERR_HIP, "fwn_model_reverse: hipMemsetAsync failed");
+        return fail(FWN_ERR_HIP, "%s: hipMemsetAsync failed", what);
     int p = 0;
+    float* partial = reverse ? nullptr : (float*)(ws + c.partial);
+    int poff = 0;
     Planes pl{{planes, planes + plane_elems}, (float*)(ws + c.plane3), {planes, planes + plane_elems}};
-    for (int i = m->n_block - 1; i >= 0; --i) {
-        if (record_block_event(m, m->n_block - 1 - i, st)) return fail(FWN_ERR_HIP, "fwn_model_reverse: hipEventRecord failed");
-        const int64_t M = B * T / ((int64_t)2 << i);
-        const bool hoist = hoist_cond(m, M, m->flows[i * m->n_flow].cin);
-        if (hoist) {
+    for (int k = 0; k < m->n_block; ++k) {
+        if (record_block_event(m, k, st)) return fail(FWN_ERR_HIP, "%s: hipEventRecord failed", what);
+        const int i = reverse ? m->n_block - 1 - k : k;
+        const BlockPlan& b = c.blk[i];
+        const int M = (int)b.M;
+        const fwn_flow_desc* f0 = &m->flows[i * nf];
+        if (b.cond.hoist) {
             rc = check_block_contiguity(m, i);
             if (rc) return rc;
-            // parity seen by flow j: p is flipped before each flow, visiting j = n_flow-1 .. 0
-            int par[2] = {0, 0};
-            int pc = p;
-            for (int j = m->n_flow - 1; j >= 0; --j) {
-                pc ^= 1;
-                if (j < 2) par[j] = pc;
-            }
-            run_cond_groups(m, i, M, par, ws, c, B, T, st);
+            // the plane flows 0 and 1 read: the parity flips once per flow, after it (forward) or before it (reverse)
+            const int par0 = reverse ? p ^ (nf & 1) : p, par1 = reverse ? p ^ ((nf - 1) & 1) : p ^ 1;
+            fwn_run_cond(b.cond, ws + c.cplanes + (size_t)par0 * cplane_bytes, ws + c.cplanes + (size_t)par1 * cplane_bytes, f0->Wc[0],
+                         (float*)(ws + c.P), (float*)(ws + c.Ppart), M, nf, L, f0->cin, f0->kcpad, st);
         }
         void* hA = ws + c.h0;
         void* hB = ws + c.h1;
         int have_h0 = 0;
-        for (int j = m->n_flow - 1; j >= 0; --j) {
-            p ^= 1;   // change_order first (model.py:199)
-            const fwn_flow_desc* d = &m->flows[i * m->n_flow + j];
-            const void* ca = hoist ? nullptr : (const void*)(ws + c.cplanes + (size_t)p * cplane_bytes);
-            const float* P = hoist ? (const float*)(ws + c.P) + (size_t)j * m->n_layer * M * 512 : nullptr;
-            unsigned* sync = persist_block(m, M, i) ? (unsigned*)(ws + c.sync + (size_t)(i * m->n_flow + j) * c.sync_stride) : nullptr;
-            FlowChain ch = flow_chain(m, d, j > 0 ? d - 1 : nullptr, (int)M, false, pl.spare, have_h0, sync != nullptr);
-            rc = flow_run_impl(d, B, T, pl.at[p], pl.at[p ^ 1], ca, hA, hB, ws + c.o, P, nullptr, 1, 0, nullptr, nullptr, nullptr,
-                               m->gate_fp8 ? ws + c.h8a : nullptr, m->gate_fp8 ? ws + c.h8b : nullptr, &ch, stream, sync);
+        for (int n = 0; n < nf; ++n) {
+            const int j = reverse ? nf - 1 - n : n;
+            if (reverse) p ^= 1;
+            const fwn_flow_desc* d = &m->flows[i * nf + j];
+            const fwn_flow_desc* next = reverse ? (j > 0 ? d - 1 : nullptr) : (j + 1 < nf ? d + 1 : nullptr);
+            const void* ca = b.cond.hoist ? nullptr : (const void*)(ws + c.cplanes + (size_t)p * cplane_bytes);
+            const float* P = b.cond.hoist ? (const float*)(ws + c.P) + (size_t)j * L * M * 512 : nullptr;
+            double* mom = (double*)(ws + c.mom) + (size_t)(i * nf + j) * mom_stride;
+            unsigned* sync = (!init && b.one_launch) ? (unsigned*)(ws + c.sync + (size_t)(i * nf + j) * c.sync_stride) : nullptr;
+            FlowChain ch = flow_chain(m, d, next, M, init != 0, pl.spare, have_h0, sync != nullptr);
+            rc = flow_run_impl(d, B, T, pl.at[p], pl.at[p ^ 1], ca, hA, hB, ws + c.o, P, reverse ? nullptr : partial + poff, reverse, init,
+                               mom, reduce, user, m->gate_fp8 ? ws + c.h8a : nullptr, m->gate_fp8 ? ws + c.h8b : nullptr, &ch, stream, sync);
             if (rc) return rc;
+            if (!reverse) poff += ch.n_partial;
             planes_after_flow(pl, p, ch.xb_out != nullptr);
             have_h0 = ch.h0_next != nullptr;
             if (have_h0 && ch.h0_next != hA) { void* t = hA; hA = hB; hB = t; }
+            if (!reverse) p ^= 1;
         }
     }
-    if (record_block_event(m, m->n_block, st)) return fail(FWN_ERR_HIP, "fwn_model_reverse: hipEventRecord failed");
-    if (planes_go_home(pl, plane_elems * 4, st)) return fail(FWN_ERR_HIP, "fwn_model_reverse: plane copy failed");
-    fwn_launch_merge(planes, B, T, x_out, st);
-    return check_launch("fwn_model_reverse");
+    if (record_block_event(m, m->n_block, st)) return fail(FWN_ERR_HIP, "%s: hipEventRecord failed", what);
+    if (planes_go_home(pl, plane_elems * 4, st)) return fail(FWN_ERR_HIP, "%s: plane copy failed", what);
+    if (reverse) {
+        fwn_launch_merge(planes, B, T, x_out, st);
+    } else {
+        fwn_launch_prior(planes, (long)(B * T), partial, poff, 1.0 / (double)(B * T), out2, st);
+        if (z_planes) {
+            hipError_t e = hipMemcpyAsync(z_planes, planes, (size_t)B * T * 4, hipMemcpyDeviceToDevice, st);
+            if (e != hipSuccess) return fail(FWN_ERR_HIP, "hipMemcpyAsync: %s", hipGetErrorString(e));
+        }
+    }
+    return check_launch(what);
+}
+
+int fwn_model_forward(const fwn_model_desc* m, int64_t B, int64_t T, const float* x, const float* mel,
+                      void* workspace, size_t workspace_bytes, float* out2, float* z_planes, int init,
+                      void* stream) {
+    return model_pass(m, B, T, x, mel, workspace, workspace_bytes, false, init ? 1 : 0, nullptr, nullptr, out2, z_planes, nullptr,
+                      stream);
+}
+int fwn_model_forward_init(const fwn_model_desc* m, int64_t B, int64_t T, const float* x, const float* mel,
+                           void* workspace, size_t workspace_bytes, float* out2, float* z_planes,
+                           fwn_reduce_fn reduce, void* user, void* stream) {
+    return model_pass(m, B, T, x, mel, workspace, workspace_bytes, false, 2, reduce, user, out2, z_planes, nullptr, stream);
+}
+
+int fwn_model_reverse(const fwn_model_desc* m, int64_t B, int64_t T, const float* z, const float* mel,
+                      void* workspace, size_t workspace_bytes, float* x_out, void* stream) {
+    return model_pass(m, B, T, z, mel, workspace, workspace_bytes, true, 0, nullptr, nullptr, nullptr, nullptr, x_out, stream);
 }
 
 }  // extern "C"

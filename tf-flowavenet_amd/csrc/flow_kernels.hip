@@ -800,25 +800,52 @@ struct TailLinProb {      // Y' = ReLU(sum_l A_l[M][256] . W[:, l*256 ..]^T + bi
 // ---------------------------------------------------------------------------
 constexpr int FWN_TAIL256_MIN = 192 * 256;       // rows from which the fused tail runs 256-row workgroups (they fill the chip)
 constexpr int FWN_TAIL_SPLIT_MAX = 12288;        // rows up to which the N-split tail (three ring GEMMs) replaces the fused tail
-int fwn_tail_rows(int M) { return M >= FWN_TAIL256_MIN ? 256 : 128; }   // rows per fused-tail workgroup
-int fwn_tail_is_split(int M) { return M <= FWN_TAIL_SPLIT_MAX; }
 // M <= FWN_TAIL_SPLIT_MAX: the skip sum as a ring GEMM that splits its weights over workgroups, then either
 // tail_kernel<.., HAS_P1 = false> = final conv + ZeroConv + coupling in one launch of 64-row workgroups, or (fewer rows than
 // FWN_TAIL_SPLIT_CHAIN_MIN) the round-2 form (two more ring GEMMs).
 constexpr int FWN_TAIL_SPLIT_CHAIN_MIN = 6144;   // fewer rows: too few 64-row workgroups to stream the final / ZeroConv weights through (in situ:
                                                  // block 4, 4032 rows, +2 us per flow; block 7, 504 rows, +17 us against the two ring GEMMs)
-static bool tail_split_chain(int M) { return M >= FWN_TAIL_SPLIT_CHAIN_MIN; }
-static int tail_chain_rows(int M) { return fwn_tail_is_split(M) ? 64 : fwn_tail_rows(M); }
-// rs_mt != 0: the register-streamed tail runs the launch (tail_rs.h: it can always write out_b elsewhere)
-int fwn_tail_chain_xb_out(int M, int npt, int rs_mt) { return rs_mt != 0 || !fwn_tail_is_split(M) || tail_split_chain(M); }
-int fwn_tail_chain_front(int M, int Ch, int npt, int rs_mt) { return fwn_tail_chain_xb_out(M, npt, rs_mt) && Ch <= 8 && npt == 1; }
-// rs_mt: 32-row tiles per workgroup of the register-streamed tail (tail_rs.h) when that kernel runs the launch (fwn_tail_rs_mt), else 0
-int fwn_tail_npartials_chain(int M, int Ch, int front, int rs_mt) {       // log-det partial slots one tail launch writes
-    if (rs_mt == 0 && fwn_tail_is_split(M) && !tail_split_chain(M)) return ((M + 63) / 64) * 8;
-    const int rw = (rs_mt ? 32 * rs_mt : tail_chain_rows(M)) - (front ? 2 : 0);      // chained front conv: tiles overlap by one row on either side
+constexpr int FWN_TRS_MIN_ROWS = 1008;       // fewer rows: the N-split ring GEMMs / the one-launch flow (flow_persist.h)
+// Register-streamed tail (tail_rs.h), tile height: the larger the better down to a few dozen workgroups - a workgroup streams all
+// 384 KB of Wskip | Wfinal from L2 whatever its rows (at ~64 B / clock / CU that alone is 6 k cycles), so smaller tiles buy occupancy
+// with L2 traffic and lose (tools/bench_tail_rs.hip, us per launch: 16 128 rows 17.1 as 126 workgroups of 128 rows / 19.0 as 252 of
+// 64; 8 064 rows 11.8 as 126 of 64 / 14.6 as 252 of 32).
+constexpr int FWN_TRS_ROWS128 = 12288;       // from here on 128-row workgroups (one per CU: 140 KB of LDS)
+constexpr int FWN_TRS_ROWS64 = 6144;         // 64-row workgroups down to here; 32-row ones below (one clip's blocks 1 - 3, blocks 4 / 5 of the
+                                             // 8-clip pass: a few dozen workgroups - 9.0 - 9.5 us per launch against 10.5 - 11 with 64 rows,
+                                             // where the N-split tail took three launches)
+// From 49 152 rows on (block 0 of the 8-clip pass: 504 workgroups of 128 rows = two rounds on 256 CUs) the 256-row register-chained
+// tail_kernel (252 workgroups, one round, weights read once per 256 rows) is still ahead in situ: 38 against 41 us per launch
+// (rocprofv3 per-block tables of the same box), although the stand-alone harness has this kernel ahead (42.8 against 46).
+constexpr int FWN_TRS_MAX_ROWS = 49152;
+int fwn_tail_stream_min_rows() { return FWN_TRS_MIN_ROWS; }
+
+// rows per workgroup of the tail_kernel forms (their template NW is this / 32; the three-launch form's ZeroConv GEMM also
+// tiles 64 rows)
+constexpr int FWN_TAIL_ROWS256 = 256, FWN_TAIL_ROWS128 = 128, FWN_TAIL_ROWS_SPLIT = 64;
+TailForm fwn_tail_form(int M, int L, int Ch, int npt, bool have_stream) {
+    TailForm f{};
+    if (have_stream && L == 2 && npt == 1 && Ch <= 32 && M >= FWN_TRS_MIN_ROWS && M < FWN_TRS_MAX_ROWS) {
+        f.kind = TAIL_RS;
+        f.rs_mt = M >= FWN_TRS_ROWS128 ? 4 : M >= FWN_TRS_ROWS64 ? 2 : 1;
+        f.rows = 32 * f.rs_mt;
+    } else if (M > FWN_TAIL_SPLIT_MAX) {
+        f.kind = M >= FWN_TAIL256_MIN ? TAIL_FUSED256 : TAIL_FUSED128;
+        f.rows = M >= FWN_TAIL256_MIN ? FWN_TAIL_ROWS256 : FWN_TAIL_ROWS128;
+    } else {
+        f.kind = M >= FWN_TAIL_SPLIT_CHAIN_MIN ? TAIL_SPLIT_CHAIN : TAIL_SPLIT3;
+        f.rows = FWN_TAIL_ROWS_SPLIT;
+        f.scratch = true;
+    }
+    f.xb_out = f.kind != TAIL_SPLIT3;
+    f.front = f.xb_out && Ch <= 8 && npt == 1;
+    return f;
+}
+int fwn_tail_slots(const TailForm& f, int M, bool front) {
+    if (f.kind == TAIL_SPLIT3) return ((M + 63) / 64) * 8;      // the ZeroConv ring GEMM: 8 slots per 64-row tile
+    const int rw = f.rows - (front ? 2 : 0);                    // chained front conv: tiles overlap by one row on either side
     return (M + rw - 1) / rw;
 }
-int fwn_tail_npartials(int M, int rs_mt) { return fwn_tail_npartials_chain(M, 0, 0, rs_mt); }
 
 // process-wide developer option (fwn_set_option in api.hip; round 4 read two environment variables on every gate launch)
 int g_fwn_opt_rs_persist = -1;
@@ -1063,7 +1090,7 @@ void fwn_launch_cond(const void* ca, const void* Wc_base, float* P_base, long w_
                      nsplit, st);
 }
 
-// ---- tail dispatch ----
+// ---- tail dispatch: the form fwn_tail_form picks ----
 // M > FWN_TAIL_SPLIT_MAX: the fused register-chained tail (tail_chain.h, HAS_P1), 256-row workgroups while those fill the
 // chip, else 128-row ones; below: see FWN_TAIL_SPLIT_CHAIN_MIN above.
 
@@ -1086,14 +1113,16 @@ void fwn_launch_tail(const void* o, long o_stride, int L, const void* Ws, const 
     a.save_s = chain ? (bf16*)chain->save_s : nullptr;
     a.save_u = chain ? (bf16*)chain->save_u : nullptr;
     a.save_z = chain ? chain->save_z : nullptr;
-    // the register-streamed tail (tail_rs.h) wherever the flow's fragment stream is packed and the shape is one of its
-    if (const int mt = fwn_tail_rs_mt(M, L, Ch, npt, Wts != nullptr)) {
-        fwn_launch_tail_rs(a, Wts, mt, st);
+    const TailForm f = fwn_tail_form(M, L, Ch, npt, Wts != nullptr);
+    if (f.kind == TAIL_RS) {
+        fwn_launch_tail_rs(a, Wts, f.rs_mt, st);
         return;
     }
+    // tail_kernel<NW, ..> tiles 32 NW rows per workgroup: NW comes from the same row constant as f.rows, and the grid is the
+    // slot count fwn_tail_slots gives the workspace sizing (one log-det partial per workgroup)
 #define TAIL_LAUNCH(NW, D, BK1, WDB, NPT, P1, FRONT)                                                                  \
-    hipLaunchKernelGGL((tail_kernel<NW, D, BK1, WDB, NPT, P1, FRONT>),                                                 \
-                       dim3((M + 32 * NW - (FRONT ? 2 : 0) - 1) / (32 * NW - (FRONT ? 2 : 0))), dim3(64 * NW), 0, st, a)
+    hipLaunchKernelGGL((tail_kernel<NW, D, BK1, WDB, NPT, P1, FRONT>), dim3(fwn_tail_slots(f, M, FRONT)), dim3(64 * NW), \
+                       0, st, a)
 #define TAIL_BY_NPT(NW, D, BK1, WDB, P1)                                                                              \
     do {                                                                                                              \
         if (front) TAIL_LAUNCH(NW, D, BK1, WDB, 1, P1, true);                                                         \
@@ -1101,26 +1130,30 @@ void fwn_launch_tail(const void* o, long o_stride, int L, const void* Ws, const 
         else if (npt == 2) TAIL_LAUNCH(NW, D, BK1, WDB, 2, P1, false);                                                \
         else TAIL_LAUNCH(NW, D, BK1, WDB, 4, P1, false);                                                              \
     } while (0)
-    if (fwn_tail_is_split(M)) {          // scratch_s / scratch_u: [M][256] bf16 each (api.hip checks they are there)
-        bf16* S = a.save_s ? a.save_s : (bf16*)scratch_s;      // training keeps S and U: they are written where it wants them
-        bf16* U = a.save_u ? a.save_u : (bf16*)scratch_u;
-        a.save_s = nullptr;                                    // (S comes from the ring GEMM, not from the chained kernel)
-        TailLinProb p1{(const bf16*)o, (const bf16*)Ws, bs, S, o_stride, L, M};
-        launch_ring(p1, M, 256, L * 16, st);
-        if (tail_split_chain(M)) {
-            a.S = S;
-            TAIL_BY_NPT(2, 4, 64, true, false);
-            return;
-        }
-        TailLinProb p2{S, (const bf16*)Wf, bfin, U, 0, 1, M};
-        launch_ring(p2, M, 256, 16, st);
-        TailZeroProb p3{U, (const bf16*)Wz, bz, ez, an, xa, xb, partial, M, Ch, npt, inverse, a.save_z};
-        hipLaunchKernelGGL((gemm_ring_kernel<64, 64, 2, 1, 128, 3, TailZeroProb, 2>), dim3(((M + 63) / 64) * npt), dim3(256), 0,
-                           st, p3, npt);
+    if (f.kind == TAIL_FUSED256) {
+        TAIL_BY_NPT(FWN_TAIL_ROWS256 / 32, 4, 32, false, true);
         return;
     }
-    if (fwn_tail_rows(M) == 256) TAIL_BY_NPT(8, 4, 32, false, true);
-    else TAIL_BY_NPT(4, 3, 64, true, true);
+    if (f.kind == TAIL_FUSED128) {
+        TAIL_BY_NPT(FWN_TAIL_ROWS128 / 32, 3, 64, true, true);
+        return;
+    }
+    // the N-split forms; scratch_s / scratch_u: [M][256] bf16 each (api.hip checks they are there)
+    bf16* S = a.save_s ? a.save_s : (bf16*)scratch_s;      // training keeps S and U: they are written where it wants them
+    bf16* U = a.save_u ? a.save_u : (bf16*)scratch_u;
+    a.save_s = nullptr;                                    // (S comes from the ring GEMM, not from the chained kernel)
+    TailLinProb p1{(const bf16*)o, (const bf16*)Ws, bs, S, o_stride, L, M};
+    launch_ring(p1, M, 256, L * 16, st);
+    if (f.kind == TAIL_SPLIT_CHAIN) {
+        a.S = S;
+        TAIL_BY_NPT(FWN_TAIL_ROWS_SPLIT / 32, 4, 64, true, false);
+        return;
+    }
+    TailLinProb p2{S, (const bf16*)Wf, bfin, U, 0, 1, M};
+    launch_ring(p2, M, 256, 16, st);
+    TailZeroProb p3{U, (const bf16*)Wz, bz, ez, an, xa, xb, partial, M, Ch, npt, inverse, a.save_z};
+    hipLaunchKernelGGL((gemm_ring_kernel<64, 64, 2, 1, 128, 3, TailZeroProb, 2>), dim3(((M + 63) / 64) * npt), dim3(256), 0,
+                       st, p3, npt);
 #undef TAIL_BY_NPT
 #undef TAIL_LAUNCH
 }

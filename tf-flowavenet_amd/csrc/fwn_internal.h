@@ -47,6 +47,19 @@ int fwn_cond_rs_nsplit(int M, int nz, int kcpad);
 void fwn_launch_cond_stream_pack(const void* Wc_base, long w_stride, int kcpad, int nz, void* out, hipStream_t st);
 void fwn_launch_cond_rs(const void* ca, const void* ca_odd, const void* Ws, float* P, int nz, int L, int M, int cin, int kcpad,
                         float* part, long part_stride, int nsplit, hipStream_t st);
+// The hoisted conditioning of a block of nflow flows (flow_kernels.hip): which launch computes its P matrices and with how many
+// K splits.  The caller decides whether to hoist (inference and training keep different rules); stream: the block's fragment
+// stream (fwn_launch_cond_stream_pack) or NULL.  fwn_run_cond launches it: ca0 is the plane even flows read, ca1 the odd flows',
+// P [nflow * L][M][512] fp32, Ppart (nsplit - 1) more of the same.
+struct fwn_cond_plan {
+    bool hoist;             // false: every gate fuses its conditioning (nothing to launch)
+    const void* stream;     // != NULL: the register-streamed kernel (cond_rs.h) reads this stream
+    bool merged;            // else: both parity groups in one ring launch (fwn_launch_cond2), else one launch per group
+    int nsplit;             // K splits
+};
+fwn_cond_plan fwn_plan_cond(bool hoist, int M, int nflow, int L, int cin, int kcpad, const void* stream);
+void fwn_run_cond(const fwn_cond_plan& cp, const void* ca0, const void* ca1, const void* Wc0, float* P, float* Ppart, int M, int nflow,
+                  int L, int cin, int kcpad, hipStream_t st);
 // Chaining the flows of a block (whole-model calls): out_b to a third plane buffer, and the NEXT flow's front conv computed
 // by this tail (csrc/tail_chain.h).  NULL / all-zero = the plain in-place tail.
 struct fwn_tail_chain {
@@ -66,12 +79,29 @@ void fwn_launch_tail(const void* o, long o_stride, int L, const void* Ws, const 
                      const float* bfin, const void* Wz, const float* bz, const float* ez, const float* an,
                      float* xa, float* xb, float* partial, int M, int Ch, int npt, int inverse, void* scratch_s,
                      void* scratch_u, const fwn_tail_chain* chain, const void* Wts, hipStream_t st);
-// register-streamed tail (tail_rs.h / tail_rs.hip).  Wts: Wskip | Wfinal in fragment order (fwn_launch_tail_stream_pack) or
-// nullptr; fwn_tail_rs_mt: 32-row tiles per workgroup of that kernel at this shape, 0 = another tail serves it
+// The one choice of tail kernel for a shape (flow_kernels.hip): fwn_launch_tail runs it, and every log-det slot count, scratch
+// check and chaining query of the host derives from it.  have_stream: the flow's fragment stream (Wts) is packed.
+enum TailKind {
+    TAIL_RS,             // register-streamed (tail_rs.h), rs_mt 32-row tiles per workgroup
+    TAIL_FUSED256,       // register-chained tail_kernel (tail_chain.h), 256-row workgroups
+    TAIL_FUSED128,       // ... 128-row workgroups
+    TAIL_SPLIT_CHAIN,    // N-split: skip-sum ring GEMM, then the chained kernel on 64-row tiles
+    TAIL_SPLIT3,         // N-split, three ring GEMM launches
+};
+struct TailForm {
+    TailKind kind;
+    int rows;            // rows per workgroup (the log-det slot per workgroup)
+    int rs_mt;           // TAIL_RS: 32-row tiles per workgroup, else 0
+    bool scratch;        // needs the [2][M][256] bf16 S / U scratch (or training's save_s / save_u)
+    bool xb_out;         // can write out_b elsewhere (fwn_tail_chain.xb_out)
+    bool front;          // ... and can compute the next flow's front conv (fwn_tail_chain.h0_next)
+};
+TailForm fwn_tail_form(int M, int L, int Ch, int npt, bool have_stream);
+int fwn_tail_slots(const TailForm& f, int M, bool front);   // log-det partial slots one launch writes (front: h0_next set)
+// register-streamed tail (tail_rs.h / tail_rs.hip).  Wts: Wskip | Wfinal in fragment order (fwn_launch_tail_stream_pack) or nullptr
 struct TailArgs;
 long fwn_tail_stream_size(int L);          // bytes, 0: no kernel for this layer count
 int fwn_tail_stream_min_rows();
-int fwn_tail_rs_mt(int M, int L, int Ch, int npt, bool have_stream);
 void fwn_launch_tail_stream_pack(const void* Ws, const void* Wf, void* out, hipStream_t st);
 void fwn_launch_tail_stream_pack_jobs(const void* jobs, int njobs, hipStream_t st);     // jobs: device array of {Wskip, Wfinal, out}
 void fwn_launch_tail_rs(const TailArgs& a, const void* Wts, int mt, hipStream_t st);
@@ -87,14 +117,6 @@ void fwn_launch_flow_persist_desc(const fwn_flow_desc* d, float* xa, float* xb, 
 extern int g_fwn_opt_rs_persist;
 extern int g_fwn_opt_persist_spin_us;     // flow_persist.h: bound of the one-launch flow's spins in microseconds (0 = 2 s)
 int fwn_device_cus();            // compute units of the current device (cached per device)
-
-int fwn_tail_rows(int M);        // rows per fused-tail workgroup
-int fwn_tail_is_split(int M);    // the N-split tail (ring GEMMs; needs [2][M][256] bf16 scratch) serves this M
-// rs_mt: fwn_tail_rs_mt of the launch (0: the register-streamed tail does not run it)
-int fwn_tail_npartials(int M, int rs_mt);   // log-det partial slots a plain (un-chained) tail launch writes
-int fwn_tail_npartials_chain(int M, int Ch, int front, int rs_mt);   // ... a chained launch (fwn_tail_chain given; front: h0_next set)
-int fwn_tail_chain_xb_out(int M, int npt, int rs_mt);         // whether the tail at this shape can write out_b elsewhere (xb_out)
-int fwn_tail_chain_front(int M, int Ch, int npt, int rs_mt);  // ... and can compute the next flow's front conv
 
 void fwn_launch_wn_scale(const float* v, const float* g, int k_src, int n_src, float* scale, hipStream_t st);
 void fwn_launch_pack(const float* v, const float* scale, const int* src_k, const int* src_n, int n_src,

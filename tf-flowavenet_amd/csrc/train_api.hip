@@ -138,10 +138,18 @@ struct FlowSaved {          // what the training forward keeps of one flow
     void* s_act; void* u_act; float* z; float* part; int nb, p;
 };
 
+// Training's hoisting rule: below 4096 rows whatever cin.  Inference (api.hip, hoist_cond) also asks for cin >= 256 and
+// follows cond_mode; the two differ on purpose (training runs no fragment-stream conditioning either).
+static fwn_cond_plan train_cond_plan(const fwn_model_desc* md, int i, long m) {
+    const fwn_flow_desc* d0 = &md->flows[i * md->n_flow];
+    return fwn_plan_cond(m < 4096, (int)m, md->n_flow, md->n_layer, d0->cin, d0->kcpad, nullptr);
+}
+
 struct BwdSet { void* dz; void* du; void* ds; void* dpre[FWN_MAX_LAYERS]; void* dh[FWN_MAX_LAYERS]; void* ya_bf; double* sg; };
 struct Plan {               // every buffer of one call
     void* cplanes; float* ups[FWN_MAX_UPSAMPLE]; float* planes; float* gplanes; float* dcplanes; float* P; float* Ppart;
     float* partial_all; float* out2; float* an_dummy;
+    fwn_cond_plan cond[16]; // per block: the hoisted conditioning (cond[i].hoist) and its launch
     FlowSaved* saved;       // host array, owned by the caller of plan()
     // backward temporaries, sized for the largest block and reused flow after flow
     void* xhl; float* dzz; void* d_all; void* d_o[FWN_MAX_LAYERS]; float* tn_part; void* tn_table; double* wn_scratch; double* up_wn;
@@ -192,10 +200,11 @@ void plan(const fwn_train_desc* t, long B, long T, void* ws, Plan& pl) {
     long mmax = B * T / 2;
     for (int i = 0; i < md->n_block; ++i) {
         const long ch = 1L << i, m = B * T / (2 * ch);
-        if (m < 4096) {
+        pl.cond[i] = train_cond_plan(md, i, m);
+        if (pl.cond[i].hoist) {
             const size_t need = (size_t)md->n_flow * L * m * 512 * 4;
             if (need > pbytes) pbytes = need;
-            const size_t sp = (size_t)(fwn_cond_nsplit((int)m, ((md->n_flow + 1) / 2) * L, md->flows[i * md->n_flow].kcpad) - 1) * need;
+            const size_t sp = (size_t)(pl.cond[i].nsplit - 1) * need;
             if (sp > ppart) ppart = sp;
         }
         for (int j = 0; j < md->n_flow; ++j) {
@@ -208,9 +217,9 @@ void plan(const fwn_train_desc* t, long B, long T, void* ws, Plan& pl) {
             s.s_act = b.take((size_t)m * 256 * 2);
             s.u_act = b.take((size_t)m * 256 * 2);
             s.z = (float*)b.take((size_t)m * 2 * ch * 4);
-            {       // log-det partial slots of the flow's tail launch (the register-streamed tail tiles differently: tail_rs.hip)
+            {       // log-det partial slots of the flow's tail launch (in place, without a front conv)
                 const fwn_flow_desc* fd = &md->flows[i * md->n_flow + j];
-                s.nb = fwn_tail_npartials((int)m, fwn_tail_rs_mt((int)m, fd->L, fd->Ch, fd->npt, fd->Wts != nullptr));
+                s.nb = fwn_tail_slots(fwn_tail_form((int)m, fd->L, fd->Ch, fd->npt, fd->Wts != nullptr), (int)m, false);
             }
             npart += s.nb;
         }
@@ -372,21 +381,10 @@ int fwn_train_loss_and_grads(const fwn_train_desc* t, int64_t B_, int64_t T_, co
         const long ti = T / (2 * ch), m = B * ti;
         const int cin = half * (2 << i);
         const fwn_flow_desc* d0 = &md->flows[i * NF];
-        const bool hoist = m < 4096;
-        if (hoist) {
-            const long pn = (long)NF * L * m * 512;
-            const int ns = fwn_cond_nsplit((int)m, ((NF + 1) / 2) * L, d0->kcpad);
-            const bf16* ca0 = (const bf16*)pl.cplanes + (size_t)p * cplane_elems;
-            const bf16* ca1 = (const bf16*)pl.cplanes + (size_t)(p ^ 1) * cplane_elems;
-            if (NF > 1 && fwn_cond_merge((int)m, ((NF + 1) / 2) * L, ns)) {
-                fwn_launch_cond2(ca0, ca1, d0->Wc[0], pl.P, (long)512 * d0->kcpad, m * 512, 0, 1, NF, L, (int)m, cin, d0->kcpad, pl.Ppart, pn, ns, st);
-            } else {
-                for (int g_ = 0; g_ < 2 && g_ < NF; ++g_)
-                    fwn_launch_cond(g_ ? ca1 : ca0, d0->Wc[0], pl.P, (long)512 * d0->kcpad, m * 512, g_, 2, (NF - g_ + 1) / 2, L, (int)m, cin, d0->kcpad,
-                                    pl.Ppart, pn, ns, st);
-            }
-            fwn_launch_cond_reduce(pl.P, pl.Ppart, pn, ns, pn, st);
-        }
+        const bool hoist = pl.cond[i].hoist;
+        if (hoist)
+            fwn_run_cond(pl.cond[i], (const bf16*)pl.cplanes + (size_t)p * cplane_elems, (const bf16*)pl.cplanes + (size_t)(p ^ 1) * cplane_elems,
+                         d0->Wc[0], pl.P, pl.Ppart, (int)m, NF, L, cin, d0->kcpad, st);
         for (int j = 0; j < NF; ++j) {
             const fwn_flow_desc* d = &md->flows[i * NF + j];
             FlowSaved& s = saved[i * NF + j];

@@ -152,7 +152,10 @@ class FloWaveNet:
         """0 unless a one-launch flow (csrc/flow_persist.h) of the last ``forward`` / ``reverse`` with batch ``b`` and length ``t`` on
         the current stream gave up a bounded dependency wait (a pass that was only delayed - a preempted queue, a debugger -
         can: its log_p / logdet / waveform are NaN then).  > 0: the give-up code; retry, or build the model with
-        ``persist_mode=1``.  Synchronises the stream (``fwn_model_persist_status``)."""
+        ``persist_mode=1``.  0 as well where no pass of that shape has run on this stream yet (its workspace holds nothing to
+        read).  Synchronises the stream (``fwn_model_persist_status``)."""
+        if (b, t, self._stream()) not in self._ws:
+            return 0
         ws, _ = self._workspace(b, t)
         return int(self._lib.fwn_model_persist_status(C.byref(self._packed.model_desc), b, t, ws, self._stream()))
 

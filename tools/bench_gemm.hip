@@ -110,9 +110,9 @@ int main(int argc, char** argv) {
             float* xb = (float*)dalloc((size_t)M * Ch * 4, 0);
             float* part = (float*)dalloc(1 << 16, 0);
             void* scr = dalloc((size_t)M * 1024, 0);
-            timeit(fwn_tail_is_split(M) ? "tail (N-split, 3 launches)" : "tail (fused)", 2.0 * M * (512.0 * 256 + 256 * 256 + 256.0 * 2 * Ch), [&] {
+            timeit(fwn_tail_form(M, 2, Ch, npt, false).scratch ? "tail (N-split)" : "tail (fused)", 2.0 * M * (512.0 * 256 + 256 * 256 + 256.0 * 2 * Ch), [&] {
                 fwn_launch_tail(o, (long)M * 256, 2, Ws, bias, Wf, bias, Wz, bz, bz, an, xa, xb, part, M, Ch, npt, 0, scr,
-                                (char*)scr + (size_t)M * 512, 0); });
+                                (char*)scr + (size_t)M * 512, nullptr, nullptr, 0); });
             CK(hipDeviceSynchronize());
             CK(hipFree(scr));
             CK(hipDeviceSynchronize());
