@@ -502,6 +502,26 @@ int fwn_model_reverse(const fwn_model_desc* m, int64_t B, int64_t T, const float
  * first that did (log_p / logdet / the waveform are NaN then: retry, e.g. with fwn_model_desc.persist_mode = 1).  Synchronises. */
 int fwn_model_persist_status(const fwn_model_desc* m, int64_t B, int64_t T, const void* workspace, void* stream);
 
+/* ---- ragged batches: clips of different lengths in one inverse pass ----
+ * Zero-fill of the rows past each clip's own length: rows [len[b] / samples_per_row, rows) of clip b in a
+ * [B][rows][row_bytes] buffer (base 4-byte aligned, row_bytes a multiple of 4).  len: DEVICE array of B lengths in samples,
+ * read by the kernel (the call stays asynchronous and graph-capturable) and clamped there to [0, rows * samples_per_row]: no
+ * value of it writes outside the buffer.  The stores are proportional to the padding, 16 bytes each where aligned. */
+int fwn_mask_rows(void* base, int64_t B, int64_t rows, int64_t row_bytes, const int32_t* len, int32_t samples_per_row,
+                  void* stream);
+/* Workspace of fwn_model_reverse_ragged: that of fwn_workspace_bytes plus the masked copy of the mel. */
+size_t fwn_ragged_workspace_bytes(const fwn_model_desc* m, int64_t B, int64_t T);
+/* fwn_model_reverse for B clips of len_dev[b] <= T samples each (DEVICE int32 [B], every length a multiple of hop and of
+ * 2^n_block, validated by the caller): clip b is z[b][0 .. len) with mel[b][0 .. len / hop).  x_out[b][0 .. len) is what
+ * the clip gives alone, to rounding; x_out[b][len .. T) is 0; nothing past a clip's length in z or mel reaches an output bit
+ * (any finite values) and neither input is written.  Every stage reads a clip's neighbours in time only through rows that
+ * are exact zeros past its end (the convolutions' own zero padding at T): the pass zero-fills those rows of the mel and of
+ * each inner up-sampling stage, of the flow state (at the split and after every flow) and of h (after the front conv and
+ * every res conv).  It runs every flow as a launch per stage - no one-launch flows, no chaining, whatever persist_mode and
+ * chain_mode say.  A gate_fp8 descriptor is refused (FWN_ERR_ARG). */
+int fwn_model_reverse_ragged(const fwn_model_desc* m, int64_t B, int64_t T, const float* z, const float* mel,
+                             const int32_t* len_dev, void* workspace, size_t workspace_bytes, float* x_out, void* stream);
+
 /* ---- training: loss = -(log_p + logdet) (train.py:56-60) and its gradient with respect to every trainable tensor
  * (the one tf.gradients call of train.py:63-66) for one batch, in ONE call: training forward with what the backward
  * needs kept per flow, then the flows in reverse (coupling, ZeroConv / final / skip / res, the gated layers with their

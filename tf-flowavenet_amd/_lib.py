@@ -231,6 +231,9 @@ SIGNATURES = {
     "fwn_train_loss_and_grads": (C.c_int, [C.POINTER(TrainDesc), i64, i64, vp, vp, vp, C.c_size_t, vp, BLOCK_DONE_FN, vp, vp]),
     "fwn_model_reverse": (C.c_int, [C.POINTER(ModelDesc), i64, i64, vp, vp, vp, C.c_size_t, vp, vp]),
     "fwn_model_persist_status": (C.c_int, [C.POINTER(ModelDesc), i64, i64, vp, vp]),
+    "fwn_mask_rows": (C.c_int, [vp, i64, i64, i64, vp, i32, vp]),
+    "fwn_ragged_workspace_bytes": (C.c_size_t, [C.POINTER(ModelDesc), i64, i64]),
+    "fwn_model_reverse_ragged": (C.c_int, [C.POINTER(ModelDesc), i64, i64, vp, vp, vp, vp, C.c_size_t, vp, vp]),
 }
 
 _lib = None

@@ -137,6 +137,13 @@ int fwn_merge_planes(const float* planes, int64_t B, int64_t T, float* x, void* 
     fwn_launch_merge(planes, B, T, x, (hipStream_t)stream);
     return check_launch("fwn_merge_planes");
 }
+int fwn_mask_rows(void* base, int64_t B, int64_t rows, int64_t row_bytes, const int32_t* len, int32_t samples_per_row, void* stream) {
+    REQUIRE(base && len && B > 0 && B < 65536 && rows > 0 && row_bytes > 0 && samples_per_row > 0, "fwn_mask_rows: bad argument");
+    REQUIRE((((uintptr_t)base) & 3) == 0 && row_bytes % 4 == 0, "fwn_mask_rows: base and row_bytes must be multiples of 4");
+    REQUIRE(rows <= ((int64_t)1 << 31) / samples_per_row, "fwn_mask_rows: rows * samples_per_row exceeds 2^31");
+    fwn_launch_mask_rows(base, (long)B, (long)rows, (long)row_bytes, len, (int)B, samples_per_row, (hipStream_t)stream);
+    return check_launch("fwn_mask_rows");
+}
 
 int fwn_actnorm_ddi(const float* xa, const float* xb, int M, int Ch, float* an, void* stream) {
     REQUIRE(xa && xb && an && M > 0 && Ch > 0, "fwn_actnorm_ddi: bad argument");
@@ -448,7 +455,7 @@ struct FlowChain {
 static int flow_run_impl(const fwn_flow_desc* d, int64_t B, int64_t T, float* xa, float* xb, const void* ca,
                          void* h0, void* h1, void* o, const float* P, float* partial, int inverse, int ddi,
                          double* mom, fwn_reduce_fn reduce, void* user, void* h8a, void* h8b, FlowChain* chain, void* stream,
-                         unsigned* sync = nullptr) {
+                         unsigned* sync = nullptr, const int32_t* len = nullptr) {
     int rc = check_desc(d);
     if (rc) return rc;
     REQUIRE(B > 0 && T > 0 && T % (2 * (int64_t)d->Ch) == 0, "fwn_flow_run: T=%lld not divisible by 2*Ch=%d",
@@ -461,6 +468,11 @@ static int flow_run_impl(const fwn_flow_desc* d, int64_t B, int64_t T, float* xa
     hipStream_t st = (hipStream_t)stream;
     const int Ti = (int)(T / (2 * d->Ch));
     const int M = (int)(B * Ti);
+    // ragged batch (len: the clips' lengths in samples, on the device): h rows past a clip's end are zeroed behind every
+    // kernel that writes h, so that the taps of the next one read what they read at the end of a clip on its own
+    REQUIRE(!len || (inverse && !sync && !h8a && !(chain && (chain->xb_out || chain->have_h0))),
+            "fwn_flow_run: lengths go with the plain inverse stages only");
+    auto mask_h = [&](void* h) { if (len) fwn_launch_mask_rows(h, (long)B, Ti, 512, len, (int)B, 2 * d->Ch, st); };
     if (ddi == 1) fwn_launch_ddi(xa, xb, M, d->Ch, d->an, st);
     if (ddi == 2) {
         REQUIRE(mom, "fwn_flow_run: no moment buffer");
@@ -491,6 +503,7 @@ static int flow_run_impl(const fwn_flow_desc* d, int64_t B, int64_t T, float* xa
     if (!(chain && chain->have_h0))
         fwn_launch_front(xa, d->an, d->Wfront, d->Wfront2, d->bfront, h0, h1, M, Ti, d->Ch, d->kfpad, inverse ? 0 : 1,
                          fp8_layer(0) ? h8c : nullptr, st);
+    mask_h(h0);
     void* hc = h0;
     void* hn = h1;
     for (int l = 0; l < d->L; ++l) {
@@ -503,6 +516,7 @@ static int flow_run_impl(const fwn_flow_desc* d, int64_t B, int64_t T, float* xa
                             Ti, dilation_of(l), d->cin, d->kcpad, nullptr, st);
         if (l + 1 < d->L) {
             fwn_launch_res(ol, hc, d->Wres[l], d->bres[l], hn, M, fp8_layer(l + 1) ? h8n : nullptr, st);
+            mask_h(hn);
             void* t = hc; hc = hn; hn = t;
             t = h8c; h8c = h8n; h8n = t;
         }
@@ -804,6 +818,7 @@ struct BlockPlan {
     int64_t M;               // rows of the block's matrices
     fwn_cond_plan cond;      // hoisted conditioning (cond.hoist) and the launch that computes it
     bool one_launch;         // its flows run as one launch each (flow_persist.h)
+    bool chained;            // a flow of it that runs as a launch per stage chains with the next one (flow_chain)
     int slots;               // log-det partial slots reserved per flow: its tail runs plain or chained (overlapping tiles)
 };
 
@@ -882,12 +897,14 @@ static int planes_go_home(Planes& pl, size_t plane_bytes, hipStream_t st) {   //
 }
 
 struct Carve {
-    size_t cplanes, up0, up1, planes, plane3, h0, h1, o, P, Ppart, partial, mom, h8a, h8b, sync, total;
+    size_t cplanes, up0, up1, planes, plane3, h0, h1, o, P, Ppart, partial, mom, h8a, h8b, sync, mel, total;
     size_t sync_stride, sync_bytes;       // one block of counters per flow (flow_persist.h), zeroed once per pass
     BlockPlan blk[16];
 };
 
-static Carve carve(const fwn_model_desc* m, int64_t B, int64_t T) {
+// ragged: a pass with per-clip lengths - every flow a launch per stage (the zero-fills of model_pass run between the
+// stages; the chained front conv reads out_b rows inside the launch that writes them), plus a copy of the mel to mask
+static Carve carve(const fwn_model_desc* m, int64_t B, int64_t T, bool ragged = false) {
     Carve c;
     size_t off = 0;
     const size_t half = m->num_mels / 2;
@@ -909,7 +926,8 @@ static Carve carve(const fwn_model_desc* m, int64_t B, int64_t T) {
         const fwn_flow_desc* f0 = &m->flows[i * m->n_flow];
         b.M = B * T / ((int64_t)2 << i);
         b.cond = fwn_plan_cond(hoist_cond(m, b.M, f0->cin), (int)b.M, m->n_flow, m->n_layer, f0->cin, f0->kcpad, m->cond_stream[i]);
-        b.one_launch = persist_block(m, b, f0);
+        b.one_launch = !ragged && persist_block(m, b, f0);
+        b.chained = !ragged && m->chain_mode != 1;
         b.slots = fwn_tail_partials_chained((int)b.M, f0->Ch, 1);       // chained with a front conv: the most tiles
         if (b.cond.hoist) {
             const size_t need = (size_t)m->n_flow * m->n_layer * b.M * 512 * 4;
@@ -932,6 +950,7 @@ static Carve carve(const fwn_model_desc* m, int64_t B, int64_t T) {
     c.h8b = off; off = align_up(off + (m->gate_fp8 ? Mmax * 256 : 0));
     c.sync_bytes = c.sync_stride * (size_t)m->n_block * m->n_flow;
     c.sync = off; off = align_up(off + c.sync_bytes);
+    c.mel = off; off = align_up(off + (ragged ? (size_t)B * (T / hop_of(m)) * m->num_mels * 4 : 0));
     c.total = off;
     return c;
 }
@@ -940,19 +959,36 @@ size_t fwn_workspace_bytes(const fwn_model_desc* m, int64_t B, int64_t T) {
     if (check_model(m, B, T) != FWN_OK) return 0;
     return carve(m, B, T).total;
 }
+size_t fwn_ragged_workspace_bytes(const fwn_model_desc* m, int64_t B, int64_t T) {
+    if (check_model(m, B, T) != FWN_OK) return 0;
+    return carve(m, B, T, true).total;
+}
 
-static void run_upsample(const fwn_model_desc* m, int64_t B, int64_t T, const float* mel, char* ws,
-                         const Carve& c, hipStream_t st) {
+// len (ragged batch): the stages run on a copy of the mel with the frames past each clip's end zeroed, and so is every inner
+// stage's output - the transposed conv of the next stage reads one row across a clip's end.  The last stage's rows past the
+// end stay as they come out: the conditioning is pointwise in time.
+static int run_upsample(const fwn_model_desc* m, int64_t B, int64_t T, const float* mel, char* ws,
+                        const Carve& c, hipStream_t st, const int32_t* len) {
     int H = (int)(T / hop_of(m));
+    int spr = hop_of(m);                 // samples per row of the current stage's input
     const float* in = mel;
+    if (len) {
+        float* mc = (float*)(ws + c.mel);
+        if (hipMemcpyAsync(mc, mel, (size_t)B * H * m->num_mels * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return -1;
+        fwn_launch_mask_rows(mc, (long)B, H, (long)m->num_mels * 4, len, (int)B, spr, st);
+        in = mc;
+    }
     for (int i = 0; i < m->n_up; ++i) {
         const bool last = (i == m->n_up - 1);
         float* outf = last ? nullptr : (float*)(ws + ((i & 1) ? c.up1 : c.up0));
         fwn_launch_upsample(in, (int)B, H, m->num_mels, m->up_w[i], m->up_bias[i], nullptr, m->up_scale[i], outf,
                             last ? (void*)(ws + c.cplanes) : nullptr, st);
         H *= m->up_scale[i];
+        spr /= m->up_scale[i];
+        if (len && !last) fwn_launch_mask_rows(outf, (long)B, H, (long)m->num_mels * 4, len, (int)B, spr, st);
         in = outf;
     }
+    return 0;
 }
 
 static int check_block_contiguity(const fwn_model_desc* m, int blk) {
@@ -971,11 +1007,12 @@ static int check_block_contiguity(const fwn_model_desc* m, int blk) {
 // that kernel exists (Ch <= 8) - not during the data-dependent init (next's ActNorm table does not exist yet) and not on
 // the fp8 path (its first gate reads an e4m3 copy of h0 that only the stand-alone front conv writes).
 static FlowChain flow_chain(const fwn_model_desc* m, const fwn_flow_desc* d, const fwn_flow_desc* next, int M, bool init, float* spare,
-                            int have_h0, bool one_launch) {
+                            int have_h0, bool chained) {
     FlowChain ch;
     memset(&ch, 0, sizeof(ch));
-    // (a block whose flows run as ONE launch each - flow_persist.h - does not chain: that form holds the whole flow already)
-    const bool on = m->chain_mode != 1 && !one_launch;
+    // (a block whose flows run as ONE launch each - flow_persist.h - does not chain: that form holds the whole flow already;
+    // BlockPlan.chained)
+    const bool on = chained;
     const TailForm f = desc_tail(d, M);
     ch.xb_out = (on && f.xb_out) ? spare : nullptr;
     ch.next = (ch.xb_out && next && !init && !m->gate_fp8 && next->Wfront3 && next->kf3 > 0 && f.front) ? next : nullptr;
@@ -1015,17 +1052,21 @@ int fwn_model_persist_status(const fwn_model_desc* m, int64_t B, int64_t T, cons
 // moments -> reduce callback), and ends in the prior.  Reverse: both orders backwards, the parity flipped before each flow
 // (model.py:199); it ends in the merge of the planes into x_out.  A block's plan (carve) decides its conditioning launch and
 // whether its flows run as one launch each; the init pass runs no flow as one launch, but zeroes the sync region all the same.
+// len (reverse only): a ragged batch - the same stages under the plan of carve(.., ragged), with the rows past each clip's end
+// zeroed wherever a later stage reads across it: mel and inner up-sampling stages, planes, h (flow_run_impl), and x_out.
 static int model_pass(const fwn_model_desc* m, int64_t B, int64_t T, const float* in, const float* mel, void* workspace,
                       size_t workspace_bytes, bool reverse, int init, fwn_reduce_fn reduce, void* user, float* out2, float* z_planes,
-                      float* x_out, void* stream) {
-    const char* what = reverse ? "fwn_model_reverse" : "fwn_model_forward";
+                      float* x_out, void* stream, const int32_t* len = nullptr) {
+    const char* what = len ? "fwn_model_reverse_ragged" : reverse ? "fwn_model_reverse" : "fwn_model_forward";
     int rc = check_model(m, B, T);
     if (rc) return rc;
     REQUIRE(in && mel && workspace && (reverse ? x_out : out2), "%s: null pointer", what);
     REQUIRE((((uintptr_t)workspace) & 255) == 0, "workspace must be 256-byte aligned");
     REQUIRE(!reverse || ((m->n_block * m->n_flow) & 1) == 0,
             "reverse with odd n_block*n_flow ends in swapped channel order (model.py:199,254); unsupported");
-    const Carve c = carve(m, B, T);
+    REQUIRE(!len || (reverse && !m->gate_fp8),
+            "%s: per-clip lengths go with the inverse pass of a model without fp8 gates (its e4m3 copies of h are not masked)", what);
+    const Carve c = carve(m, B, T, len != nullptr);
     if (workspace_bytes < c.total)
         return fail(FWN_ERR_WORKSPACE, "workspace %zu < required %zu bytes", workspace_bytes, c.total);
     hipStream_t st = (hipStream_t)stream;
@@ -1037,8 +1078,13 @@ static int model_pass(const fwn_model_desc* m, int64_t B, int64_t T, const float
     float* planes = (float*)(ws + c.planes);
     const int nf = m->n_flow, L = m->n_layer;
 
-    run_upsample(m, B, T, mel, ws, c, st);
+    if (run_upsample(m, B, T, mel, ws, c, st, len)) return fail(FWN_ERR_HIP, "%s: mel copy failed", what);
     fwn_launch_split(in, B, T, planes, st);   // (reverse: the n_block pre-squeezes of model.py:374-392 are index math)
+    // ragged batch: both planes hold clip b's samples at [b][0, len / 2) at every block (a row of block i is 2^i of them, and
+    // len is a multiple of 2^n_block); the rest is zeroed here and behind every flow (ActNorm^-1 and the coupling leave -b
+    // and t there, and the next front conv reads one row across the clip's end)
+    auto mask_planes = [&]() { if (len) fwn_launch_mask_rows(planes, 2 * (long)B, (long)(T / 2), 4, len, (int)B, 2, st); };
+    mask_planes();
     if (c.sync_bytes && hipMemsetAsync(ws + c.sync, 0, c.sync_bytes, st) != hipSuccess)
         return fail(FWN_ERR_HIP, "%s: hipMemsetAsync failed", what);
     int p = 0;
@@ -1071,10 +1117,11 @@ static int model_pass(const fwn_model_desc* m, int64_t B, int64_t T, const float
             const float* P = b.cond.hoist ? (const float*)(ws + c.P) + (size_t)j * L * M * 512 : nullptr;
             double* mom = (double*)(ws + c.mom) + (size_t)(i * nf + j) * mom_stride;
             unsigned* sync = (!init && b.one_launch) ? (unsigned*)(ws + c.sync + (size_t)(i * nf + j) * c.sync_stride) : nullptr;
-            FlowChain ch = flow_chain(m, d, next, M, init != 0, pl.spare, have_h0, sync != nullptr);
+            FlowChain ch = flow_chain(m, d, next, M, init != 0, pl.spare, have_h0, b.chained && !sync);
             rc = flow_run_impl(d, B, T, pl.at[p], pl.at[p ^ 1], ca, hA, hB, ws + c.o, P, reverse ? nullptr : partial + poff, reverse, init,
-                               mom, reduce, user, m->gate_fp8 ? ws + c.h8a : nullptr, m->gate_fp8 ? ws + c.h8b : nullptr, &ch, stream, sync);
+                               mom, reduce, user, m->gate_fp8 ? ws + c.h8a : nullptr, m->gate_fp8 ? ws + c.h8b : nullptr, &ch, stream, sync, len);
             if (rc) return rc;
+            mask_planes();
             if (!reverse) poff += ch.n_partial;
             planes_after_flow(pl, p, ch.xb_out != nullptr);
             have_h0 = ch.h0_next != nullptr;
@@ -1086,6 +1133,7 @@ static int model_pass(const fwn_model_desc* m, int64_t B, int64_t T, const float
     if (planes_go_home(pl, plane_elems * 4, st)) return fail(FWN_ERR_HIP, "%s: plane copy failed", what);
     if (reverse) {
         fwn_launch_merge(planes, B, T, x_out, st);
+        if (len) fwn_launch_mask_rows(x_out, (long)B, (long)T, 4, len, (int)B, 1, st);
     } else {
         fwn_launch_prior(planes, (long)(B * T), partial, poff, 1.0 / (double)(B * T), out2, st);
         if (z_planes) {
@@ -1111,6 +1159,12 @@ int fwn_model_forward_init(const fwn_model_desc* m, int64_t B, int64_t T, const 
 int fwn_model_reverse(const fwn_model_desc* m, int64_t B, int64_t T, const float* z, const float* mel,
                       void* workspace, size_t workspace_bytes, float* x_out, void* stream) {
     return model_pass(m, B, T, z, mel, workspace, workspace_bytes, true, 0, nullptr, nullptr, nullptr, nullptr, x_out, stream);
+}
+int fwn_model_reverse_ragged(const fwn_model_desc* m, int64_t B, int64_t T, const float* z, const float* mel, const int32_t* len_dev,
+                             void* workspace, size_t workspace_bytes, float* x_out, void* stream) {
+    REQUIRE(len_dev, "fwn_model_reverse_ragged: null lengths");
+    REQUIRE(B < 32768, "fwn_model_reverse_ragged: B=%lld clips (at most 32767 per call)", (long long)B);
+    return model_pass(m, B, T, z, mel, workspace, workspace_bytes, true, 0, nullptr, nullptr, nullptr, nullptr, x_out, stream, len_dev);
 }
 
 }  // extern "C"

@@ -464,6 +464,33 @@ __global__ __launch_bounds__(256) void merge_kernel(const float* __restrict__ pl
     }
 }
 
+// ---- ragged batches: zero the rows past each clip's own length --------------------------------
+// buf [nclip][rows][row_bytes]; clip c keeps rows [0, len[c % nlen] / spr) and has the rest set to zero.  blockIdx.y = clip,
+// the workgroups of a clip stride over its padded bytes only: a clip of full length costs each of them one load of len.  The
+// length is clamped to the buffer here, so no value of it stores outside.  Whole 16-byte pieces between the first and the
+// last 16-byte boundary of the padded range, single dwords (at most three each side) around them.
+__global__ __launch_bounds__(256) void mask_rows_kernel(char* __restrict__ buf, long rows, long row_bytes,
+                                                        const int* __restrict__ len, int nlen, int spr) {
+    const long c = blockIdx.y;
+    long keep = (long)len[c % nlen] / spr;
+    keep = keep < 0 ? 0 : (keep > rows ? rows : keep);
+    if (keep == rows) return;
+    const uintptr_t clip = (uintptr_t)buf + (size_t)c * rows * row_bytes;
+    const uintptr_t p0 = clip + (size_t)keep * row_bytes, p1 = clip + (size_t)rows * row_bytes;
+    uintptr_t a0 = (p0 + 15) & ~(uintptr_t)15;
+    if (a0 > p1) a0 = p1;
+    uintptr_t a1 = p1 & ~(uintptr_t)15;
+    if (a1 < a0) a1 = a0;
+    const uint4 z4 = make_uint4(0u, 0u, 0u, 0u);
+    for (uintptr_t q = a0 + ((size_t)blockIdx.x * 256 + threadIdx.x) * 16; q < a1; q += (size_t)gridDim.x * 256 * 16)
+        *(uint4*)q = z4;
+    if (blockIdx.x == 0) {
+        const uintptr_t h = p0 + (size_t)threadIdx.x * 4, t = a1 + (size_t)(threadIdx.x - 4) * 4;
+        if (threadIdx.x < 4 && h < a0) *(unsigned*)h = 0u;
+        if (threadIdx.x >= 4 && threadIdx.x < 8 && t < p1) *(unsigned*)t = 0u;
+    }
+}
+
 // ---- ActNorm data-dependent init for one flow -----------------------------------------------
 // One workgroup per (plane role, channel).  an[role][0..3][tau] = shift b, scale exp(3 logs),
 // inverse scale, 3*logs.  model.py:55-56 (b = -mean), :65-71 (logs from mean((x+b)^2)).
@@ -689,6 +716,14 @@ void fwn_launch_split(const float* x, long B, long T, float* planes, hipStream_t
 }
 void fwn_launch_merge(const float* planes, long B, long T, float* x, hipStream_t st) {
     hipLaunchKernelGGL(merge_kernel, dim3(grid_for(B * T)), dim3(256), 0, st, planes, B, T, x);
+}
+void fwn_launch_mask_rows(void* base, long nclip, long rows, long row_bytes, const int* len, int nlen, int samples_per_row,
+                          hipStream_t st) {
+    // four 16-byte stores per thread if the whole clip were padding; at most ~2048 workgroups over all clips
+    const long want = (rows * row_bytes + 16383) / 16384, cap = nclip < 2048 ? 2048 / nclip : 1;
+    const long gx = want < 1 ? 1 : (want > cap ? cap : want);
+    hipLaunchKernelGGL(mask_rows_kernel, dim3((unsigned)gx, (unsigned)nclip), dim3(256), 0, st, (char*)base, rows, row_bytes, len,
+                       nlen, samples_per_row);
 }
 void fwn_launch_ddi_moments(const float* xa, const float* xb, int M, int Ch, double* mom, hipStream_t st) {
     hipLaunchKernelGGL(ddi_moments_kernel, dim3(2 * Ch), dim3(256), 0, st, xa, xb, M, Ch, mom);

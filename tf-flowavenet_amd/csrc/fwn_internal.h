@@ -133,6 +133,10 @@ void fwn_launch_upsample(const float* in, int B, int H, int W, const float* wk, 
                          float* out_f32, void* out_planes, hipStream_t st);
 void fwn_launch_split(const float* x, long B, long T, float* planes, hipStream_t st);
 void fwn_launch_merge(const float* planes, long B, long T, float* x, hipStream_t st);
+// zero rows [len[c % nlen] / samples_per_row, rows) of every clip c of a [nclip][rows][row_bytes] buffer (ragged batches: the
+// rows past a clip's own length); len is read on the device and clamped to the buffer.  base and row_bytes: multiples of 4.
+void fwn_launch_mask_rows(void* base, long nclip, long rows, long row_bytes, const int* len, int nlen, int samples_per_row,
+                          hipStream_t st);
 void fwn_launch_ddi(const float* xa, const float* xb, int M, int Ch, float* an, hipStream_t st);
 void fwn_launch_ddi_moments(const float* xa, const float* xb, int M, int Ch, double* mom, hipStream_t st);
 void fwn_launch_ddi_from_moments(const double* mom, int Ch, float* an, hipStream_t st);

@@ -127,16 +127,18 @@ class FloWaveNet:
         c32 = c.to(device=dev, dtype=torch.float32).contiguous()
         return b, t, x32, c32
 
-    def _workspace(self, b, t):
+    def _workspace(self, b, t, ragged=False):
         """Scratch for one pass.  One workspace per (B, T, HIP stream): passes issued on different
-        streams (e.g. a forward and an inverse overlapping on the chip) never share scratch."""
+        streams (e.g. a forward and an inverse overlapping on the chip) never share scratch.  A ragged inverse
+        (``reverse(..., lengths=)``) keeps a workspace of its own: it also holds the masked copy of the mel."""
         import torch
-        key = (b, t, self._stream())
+        key = (b, t, self._stream()) + (("ragged",) if ragged else ())
         ws = self._ws.get(key)
         if ws is None:
-            n = self._lib.fwn_workspace_bytes(C.byref(self._packed.model_desc), b, t)
+            size = self._lib.fwn_ragged_workspace_bytes if ragged else self._lib.fwn_workspace_bytes
+            n = size(C.byref(self._packed.model_desc), b, t)
             if n == 0:
-                _lib.check(-1, "fwn_workspace_bytes")
+                _lib.check(-1, "fwn_ragged_workspace_bytes" if ragged else "fwn_workspace_bytes")
             for k in [k for k in self._ws if k[:2] != (b, t)]:
                 del self._ws[k]   # keep only the current shape's workspaces
             ws = torch.empty(n + 256, dtype=torch.uint8, device=self._device)
@@ -212,19 +214,51 @@ class FloWaveNet:
             raise failure[0]
         _lib.check(rc, "fwn_model_forward_init")
 
-    def reverse(self, z, c, g=None, dtype=None):
+    def _check_lengths(self, lengths, b, t):
+        """``lengths`` of a ragged ``reverse`` -> list of B ints, validated on the host before anything is launched."""
+        import math
+        vals = lengths.detach().cpu().tolist() if hasattr(lengths, "detach") else np.asarray(lengths).tolist()
+        if not isinstance(vals, list) or len(vals) != b:
+            raise ValueError("lengths must hold one length per clip (B=%d), got %r" % (b, vals))
+        unit = math.lcm(self.hop, 1 << self._hparams.n_block)
+        for v in vals:
+            if int(v) != v:
+                raise ValueError("lengths must be integers (samples), got %r" % (v,))
+            if not unit <= v <= t:
+                raise ValueError("length %d outside [%d, T=%d]" % (v, unit, t))
+            if v % unit:
+                raise ValueError("length %d must be a multiple of lcm(hop_size=%d, 2^n_block=%d) = %d"
+                                 % (v, self.hop, 1 << self._hparams.n_block, unit))
+        return [int(v) for v in vals]
+
+    def reverse(self, z, c, g=None, dtype=None, lengths=None):
         """z [B,T,1], c [B,T/hop,num_mels] -> x [B,T,1] (model.py:350-396).  fp32 unless ``dtype`` is given: a torch dtype, or
-        "hparams" for the reference's return type, ``hparams.dtype`` (float16 / bfloat16 / float32; model.py:356-357,396)."""
+        "hparams" for the reference's return type, ``hparams.dtype`` (float16 / bfloat16 / float32; model.py:356-357,396).
+
+        lengths (a list, NumPy array or tensor of B sample counts): a ragged batch.  Clip ``b`` is ``z[b, :lengths[b]]``
+        with ``c[b, :lengths[b] // hop]``; ``x[b, :lengths[b]]`` is what ``reverse`` gives for that clip alone (to
+        rounding) and ``x[b, lengths[b]:]`` is 0.  Whatever (finite) ``z`` and ``c`` hold past a clip's length reaches no
+        output bit.  Every length must be a multiple of lcm(hop_size, 2^n_block), at least that, at most T
+        (``ValueError`` otherwise).  ``gate_fp8`` models do not take lengths.  None: the plain pass."""
         import torch
         self._check_g(g)
         if dtype == "hparams":
             dtype = {"float16": torch.float16, "bfloat16": torch.bfloat16, "float32": torch.float32}[str(self._hparams.dtype).replace("tf.", "")]
         b, t, z32, c32 = self._prep(z, c, "z")
-        wsp, wsn = self._workspace(b, t)
+        if lengths is not None:
+            if self._gate_fp8:
+                raise ValueError("a gate_fp8 model takes no lengths: the e4m3 copies of h are not masked")
+            lens = torch.tensor(self._check_lengths(lengths, b, t), dtype=torch.int32).to(self._device)
+        wsp, wsn = self._workspace(b, t, ragged=lengths is not None)
         x = torch.empty(b, t, 1, dtype=torch.float32, device=self._device)
-        rc = self._lib.fwn_model_reverse(C.byref(self._packed.model_desc), b, t, z32.data_ptr(), c32.data_ptr(),
-                                         wsp, wsn, x.data_ptr(), self._stream())
-        _lib.check(rc, "fwn_model_reverse")
+        if lengths is None:
+            rc = self._lib.fwn_model_reverse(C.byref(self._packed.model_desc), b, t, z32.data_ptr(), c32.data_ptr(),
+                                             wsp, wsn, x.data_ptr(), self._stream())
+            _lib.check(rc, "fwn_model_reverse")
+        else:
+            rc = self._lib.fwn_model_reverse_ragged(C.byref(self._packed.model_desc), b, t, z32.data_ptr(), c32.data_ptr(),
+                                                    lens.data_ptr(), wsp, wsn, x.data_ptr(), self._stream())
+            _lib.check(rc, "fwn_model_reverse_ragged")
         return x if dtype is None or dtype == torch.float32 else x.to(dtype)
 
     def upsample(self, c):

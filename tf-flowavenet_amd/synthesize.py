@@ -8,7 +8,9 @@
 names ``vocoder/FloWaveNet/...:0`` as dumped from a TF checkpoint - ``weights.from_reference_names``; the TF
 tensor-bundle format itself is out of scope), the wav writer is the stdlib ``wave`` module (librosa is not a dependency), ``z`` is
 seedable (``--seed``; TF's Philox stream cannot be reproduced), and mels of equal length are
-batched into one launch.
+batched into one launch.  ``--ragged`` batches mels of *similar* length too (``plan_batches``; ``FloWaveNet.reverse(...,
+lengths=)`` gives every clip what it gives alone), and draws each clip's ``z`` from a generator of its own, so a clip's
+audio does not depend on the batch it lands in.
 """
 from __future__ import annotations
 
@@ -59,6 +61,41 @@ def max_clips_per_call(hparams, t):
     return int((lim - 1) // t)
 
 
+def _aligned_frames(frames, hparams):
+    """frames rounded up so that frames * hop divides by 2^n_block (model.py:226)."""
+    align = max(1, (1 << hparams.n_block) // int(np.gcd(1 << hparams.n_block, hparams.hop_size)))
+    return int(frames) + (-int(frames)) % align
+
+
+def plan_batches(frame_counts, batch, max_pad_frac, hparams):
+    """Which clips share a ragged ``reverse`` call: a list of groups of indices into ``frame_counts`` (mel frames per clip).
+
+    The clips are sorted by length (ties in index order) and taken greedily: a clip joins the open group unless the group
+    already holds ``batch`` clips, or ``max_clips_per_call`` at the group's new length would be exceeded, or the padding
+    (the samples of the group's ``B * T`` that belong to no clip; T = the longest clip, each clip first rounded up to the
+    model's alignment) would exceed ``max_pad_frac`` of ``B * T``.  Padded rows cost what real rows cost, so
+    ``max_pad_frac`` trades launches saved against samples wasted: a policy knob, not a correctness one - 0 groups clips
+    of equal length only (the grouping without ``--ragged``), the CLI's default is 0.25.  Pure host code."""
+    hop = hparams.hop_size
+    t_of = [_aligned_frames(f, hparams) * hop for f in frame_counts]
+    groups, cur, cur_sum = [], [], 0
+    for k in sorted(range(len(t_of)), key=lambda k: (t_of[k], frame_counts[k], k)):
+        t = t_of[k]                                  # ascending: the newcomer sets the group's T
+        per_call = max_clips_per_call(hparams, t)
+        if per_call < 1:
+            raise ValueError("an utterance of %d samples exceeds what one call can address (%d samples): split the mel"
+                             % (t, max_clips_per_call(hparams, 1)))
+        n = len(cur) + 1
+        if cur and (n > int(batch) or n > per_call or n * t - (cur_sum + t) > max_pad_frac * n * t):
+            groups.append(cur)
+            cur, cur_sum = [], 0
+        cur.append(k)
+        cur_sum += t
+    if cur:
+        groups.append(cur)
+    return groups
+
+
 def write_wav(path, audio, sample_rate):
     pcm = np.clip(np.asarray(audio, dtype=np.float64), -1.0, 1.0)
     pcm = (pcm * 32767.0).round().astype("<i2")
@@ -77,6 +114,8 @@ def synthesize(args, hparams, model=None):
     os.makedirs(args.output_dir, exist_ok=True)
     names = sorted(f for f in os.listdir(args.mels_dir) if f.endswith(".npy"))
     mels = {n: np.load(os.path.join(args.mels_dir, n)).astype(np.float32) for n in names}
+    if getattr(args, "ragged", False):
+        return _synthesize_ragged(args, hparams, model, names, mels)
     by_len = {}
     for n in names:
         by_len.setdefault(mels[n].shape[0], []).append(n)
@@ -100,6 +139,28 @@ def synthesize(args, hparams, model=None):
     return names
 
 
+def _synthesize_ragged(args, hparams, model, names, mels):
+    """``--ragged``: clips of similar length share a call (``plan_batches``).  Each clip is edge-padded to the model's
+    alignment as without the flag - that is its ``length`` - and zero-padded from there to the group's T; clip k (in sorted
+    file-name order) draws its z from ``torch.Generator().manual_seed(seed + k)``."""
+    import torch
+    hop = hparams.hop_size
+    frames = [mels[n].shape[0] for n in names]
+    for group in plan_batches(frames, int(args.batch), float(getattr(args, "max_pad_frac", 0.25)), hparams):
+        own = [_aligned_frames(frames[k], hparams) for k in group]        # frames of each clip after its own edge padding
+        top = max(own)
+        c = np.zeros((len(group), top, hparams.num_mels), dtype=np.float32)
+        z = torch.zeros(len(group), top * hop, 1)
+        for row, (k, f) in enumerate(zip(group, own)):
+            c[row, :f] = np.pad(mels[names[k]], ((0, f - frames[k]), (0, 0)), mode="edge")
+            gen = torch.Generator(device="cpu").manual_seed(int(args.seed) + k)
+            z[row, :f * hop] = torch.randn(f * hop, 1, generator=gen) * hparams.temp
+        wav = model.reverse(z.cuda(), torch.from_numpy(c).cuda(), lengths=[f * hop for f in own]).squeeze(-1).cpu().numpy()
+        for row, k in enumerate(group):
+            write_wav(os.path.join(args.output_dir, names[k][:-4] + ".wav"), wav[row, :frames[k] * hop], hparams.sample_rate)
+    return names
+
+
 def main(argv=None):
     from .hparams import hparams
     parser = argparse.ArgumentParser()
@@ -107,7 +168,12 @@ def main(argv=None):
     parser.add_argument("--mels_dir", default="mels/", help="folder to contain mels to synthesize audio from using the model")
     parser.add_argument("--output_dir", default="output/", help="folder to contain synthesized audio files")
     parser.add_argument("--seed", type=int, default=hparams.tf_random_seed, help="seed of the latent z")
-    parser.add_argument("--batch", type=int, default=8, help="equal-length mels per launch")
+    parser.add_argument("--batch", type=int, default=8, help="mels per launch (of equal length; of similar length with --ragged)")
+    parser.add_argument("--ragged", action="store_true",
+                        help="batch mels of different lengths into one launch; z is then drawn per clip from seed + index")
+    parser.add_argument("--max_pad_frac", type=float, default=0.25,
+                        help="with --ragged: the largest share of a launch's samples that may be padding (policy: launches "
+                             "saved against samples wasted)")
     args = parser.parse_args(argv)
     synthesize(args, hparams)
 
