@@ -522,6 +522,37 @@ size_t fwn_ragged_workspace_bytes(const fwn_model_desc* m, int64_t B, int64_t T)
 int fwn_model_reverse_ragged(const fwn_model_desc* m, int64_t B, int64_t T, const float* z, const float* mel,
                              const int32_t* len_dev, void* workspace, size_t workspace_bytes, float* x_out, void* stream);
 
+/* ---- ragged batches, forward direction: per-clip log_p and logdet (additive; FWN_VERSION unchanged) ----
+ * fwn_model_forward for B clips of len_dev[b] <= T samples each (DEVICE int32 [B], validated by the caller as above).
+ * out2B [2][B] fp32: out2B[b] = log_p and out2B[B + b] = logdet of clip b - what fwn_model_forward gives for
+ * x[b][0 .. len) with mel[b][0 .. len / hop) alone, to rounding: the prior mean over the clip's own len samples, and per flow
+ * mean_C(3 logs) + mean over the clip's own rows of -log_s, halved.  z_planes (may be NULL) [2][B][T/2]: the latent planes,
+ * exactly 0 past each clip's end (fwn_model_reverse_ragged inverts them).  Nothing past a clip's length in x or mel reaches
+ * an output bit and neither input is written.  The pass is fwn_model_reverse_ragged's in the other direction - a launch per
+ * stage, the same zero-fills - with two additions.  The front conv applies ActNorm on the fly, so the rows past a clip's end of
+ * each flow's x_a plane are filled with -shift first (fwn_fill_neg_shift): ActNorm of them is an exact 0, the zero padding a
+ * clip on its own gets behind ActNorm.  And every flow's tail keeps its ZeroConv output (as fwn_tail_train does), from which
+ * fwn_ragged_logdet_rows sums -log_s per clip over the clip's own rows; the tail's own whole-batch partials are ignored.
+ * All sums are fp64 in a fixed order (no atomics): two identical calls give identical bits.  No data-dependent init; a
+ * gate_fp8 descriptor is refused (FWN_ERR_ARG).  Workspace: fwn_ragged_forward_workspace_bytes (0 for a bad descriptor). */
+size_t fwn_ragged_forward_workspace_bytes(const fwn_model_desc* m, int64_t B, int64_t T);
+int fwn_model_forward_ragged(const fwn_model_desc* m, int64_t B, int64_t T, const float* x, const float* mel,
+                             const int32_t* len_dev, void* workspace, size_t workspace_bytes, float* out2B, float* z_planes,
+                             void* stream);
+/* -shift[c] into rows [len[b] / samples_per_row, rows) of clip b of a [B][rows][Ch] fp32 plane (Ch a power of two, shift
+ * [Ch]: the first row of a flow's ActNorm table).  len as in fwn_mask_rows: read and clamped on the device, no value of it
+ * writes outside the plane.  plane 4-byte aligned. */
+int fwn_fill_neg_shift(float* plane, int64_t B, int64_t rows, int Ch, const float* shift, const int32_t* len,
+                       int32_t samples_per_row, void* stream);
+/* One flow's log-det terms per clip.  Z [B][rows][2 Ch] fp32 (fwn_tail_train's save_z: log_s channels, then t channels),
+ * ez: the flow's ezero.  acc [B][nslot] fp64 with nslot = fwn_ragged_logdet_slots(B): acc[b][0 .. nslot - 1) are chunk sums
+ * of -Z[row][c] * ez(c) over rows [0, len[b] / samples_per_row) and c < Ch - their sum in index order is the clip's sum; no
+ * row past a clip's end is loaded - and acc[b][nslot - 1] = sum_c of both planes' 3 logs from the ActNorm table an (NULL:
+ * left unwritten). */
+int fwn_ragged_logdet_slots(int64_t B);
+int fwn_ragged_logdet_rows(const float* Z, int64_t B, int64_t rows, int Ch, const float* ez, const float* an,
+                           const int32_t* len, int32_t samples_per_row, double* acc, void* stream);
+
 /* ---- training: loss = -(log_p + logdet) (train.py:56-60) and its gradient with respect to every trainable tensor
  * (the one tf.gradients call of train.py:63-66) for one batch, in ONE call: training forward with what the backward
  * needs kept per flow, then the flows in reverse (coupling, ZeroConv / final / skip / res, the gated layers with their

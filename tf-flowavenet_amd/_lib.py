@@ -234,6 +234,11 @@ SIGNATURES = {
     "fwn_mask_rows": (C.c_int, [vp, i64, i64, i64, vp, i32, vp]),
     "fwn_ragged_workspace_bytes": (C.c_size_t, [C.POINTER(ModelDesc), i64, i64]),
     "fwn_model_reverse_ragged": (C.c_int, [C.POINTER(ModelDesc), i64, i64, vp, vp, vp, vp, C.c_size_t, vp, vp]),
+    "fwn_ragged_forward_workspace_bytes": (C.c_size_t, [C.POINTER(ModelDesc), i64, i64]),
+    "fwn_model_forward_ragged": (C.c_int, [C.POINTER(ModelDesc), i64, i64, vp, vp, vp, vp, C.c_size_t, vp, vp, vp]),
+    "fwn_fill_neg_shift": (C.c_int, [vp, i64, i64, C.c_int, vp, vp, i32, vp]),
+    "fwn_ragged_logdet_slots": (C.c_int, [i64]),
+    "fwn_ragged_logdet_rows": (C.c_int, [vp, i64, i64, C.c_int, vp, vp, vp, i32, vp, vp]),
 }
 
 _lib = None

@@ -145,6 +145,26 @@ int fwn_mask_rows(void* base, int64_t B, int64_t rows, int64_t row_bytes, const 
     return check_launch("fwn_mask_rows");
 }
 
+int fwn_fill_neg_shift(float* plane, int64_t B, int64_t rows, int Ch, const float* shift, const int32_t* len,
+                       int32_t samples_per_row, void* stream) {
+    REQUIRE(plane && shift && len && B > 0 && B < 65536 && rows > 0 && samples_per_row > 0, "fwn_fill_neg_shift: bad argument");
+    REQUIRE(Ch >= 1 && (Ch & (Ch - 1)) == 0, "fwn_fill_neg_shift: Ch=%d must be a power of two", Ch);
+    REQUIRE((((uintptr_t)plane) & 3) == 0, "fwn_fill_neg_shift: plane must be 4-byte aligned");
+    REQUIRE(rows <= ((int64_t)1 << 31) / samples_per_row, "fwn_fill_neg_shift: rows * samples_per_row exceeds 2^31");
+    fwn_launch_fill_neg_shift(plane, (long)B, (long)rows, Ch, shift, len, (int)B, samples_per_row, (hipStream_t)stream);
+    return check_launch("fwn_fill_neg_shift");
+}
+int fwn_ragged_logdet_slots(int64_t B) { return B > 0 ? fwn_ragged_logdet_nslot((long)B) : 0; }
+int fwn_ragged_logdet_rows(const float* Z, int64_t B, int64_t rows, int Ch, const float* ez, const float* an, const int32_t* len,
+                           int32_t samples_per_row, double* acc, void* stream) {
+    REQUIRE(Z && ez && len && acc && B > 0 && B < 65536 && rows > 0 && samples_per_row > 0, "fwn_ragged_logdet_rows: bad argument");
+    REQUIRE(Ch >= 1 && (Ch & (Ch - 1)) == 0, "fwn_ragged_logdet_rows: Ch=%d must be a power of two", Ch);
+    REQUIRE((((uintptr_t)Z) & 3) == 0 && (((uintptr_t)acc) & 7) == 0, "fwn_ragged_logdet_rows: misaligned buffer");
+    REQUIRE(rows <= ((int64_t)1 << 31) / samples_per_row, "fwn_ragged_logdet_rows: rows * samples_per_row exceeds 2^31");
+    fwn_launch_ragged_logdet(Z, (long)B, (long)rows, Ch, ez, an, len, (int)B, samples_per_row, acc, (hipStream_t)stream);
+    return check_launch("fwn_ragged_logdet_rows");
+}
+
 int fwn_actnorm_ddi(const float* xa, const float* xb, int M, int Ch, float* an, void* stream) {
     REQUIRE(xa && xb && an && M > 0 && Ch > 0, "fwn_actnorm_ddi: bad argument");
     fwn_launch_ddi(xa, xb, M, Ch, an, (hipStream_t)stream);
@@ -451,11 +471,17 @@ struct FlowChain {
     void* h0_next;               // out: the buffer the next flow's h0 was written to (one of h0 / h1), NULL if none
     int n_partial;               // out: log-det partial slots this flow's tail wrote
 };
+// A flow of a ragged forward pass (fwn_model_forward_ragged): where its tail keeps Z = (log_s | t) [M][2 Ch] fp32 and where
+// the per-clip sums of -log_s go ([B][fwn_ragged_logdet_nslot(B)] fp64).
+struct FlowRagged {
+    float* z;
+    double* acc;
+};
 
 static int flow_run_impl(const fwn_flow_desc* d, int64_t B, int64_t T, float* xa, float* xb, const void* ca,
                          void* h0, void* h1, void* o, const float* P, float* partial, int inverse, int ddi,
                          double* mom, fwn_reduce_fn reduce, void* user, void* h8a, void* h8b, FlowChain* chain, void* stream,
-                         unsigned* sync = nullptr, const int32_t* len = nullptr) {
+                         unsigned* sync = nullptr, const int32_t* len = nullptr, const FlowRagged* rg = nullptr) {
     int rc = check_desc(d);
     if (rc) return rc;
     REQUIRE(B > 0 && T > 0 && T % (2 * (int64_t)d->Ch) == 0, "fwn_flow_run: T=%lld not divisible by 2*Ch=%d",
@@ -470,8 +496,8 @@ static int flow_run_impl(const fwn_flow_desc* d, int64_t B, int64_t T, float* xa
     const int M = (int)(B * Ti);
     // ragged batch (len: the clips' lengths in samples, on the device): h rows past a clip's end are zeroed behind every
     // kernel that writes h, so that the taps of the next one read what they read at the end of a clip on its own
-    REQUIRE(!len || (inverse && !sync && !h8a && !(chain && (chain->xb_out || chain->have_h0))),
-            "fwn_flow_run: lengths go with the plain inverse stages only");
+    REQUIRE(!len || (!sync && !h8a && !ddi && !(chain && (chain->xb_out || chain->have_h0)) && (inverse ? !rg : rg && rg->z && rg->acc)),
+            "fwn_flow_run: lengths go with the plain stages only (forward: with the buffers of the per-clip log-det, no init)");
     auto mask_h = [&](void* h) { if (len) fwn_launch_mask_rows(h, (long)B, Ti, 512, len, (int)B, 2 * d->Ch, st); };
     if (ddi == 1) fwn_launch_ddi(xa, xb, M, d->Ch, d->an, st);
     if (ddi == 2) {
@@ -500,6 +526,10 @@ static int flow_run_impl(const fwn_flow_desc* d, int64_t B, int64_t T, float* xa
     }
     void* h8c = h8a;
     void* h8n = h8b;
+    // ragged forward: the front conv applies ActNorm on the fly, (v + shift) * scale - with -shift in the rows past a clip's
+    // end it reads exact zeros there, the padding a clip on its own gets behind ActNorm (the tail then leaves ActNorm(x_a) = 0
+    // in those rows by itself)
+    if (len && !inverse) fwn_launch_fill_neg_shift(xa, (long)B, Ti, d->Ch, d->an, len, (int)B, 2 * d->Ch, st);
     if (!(chain && chain->have_h0))
         fwn_launch_front(xa, d->an, d->Wfront, d->Wfront2, d->bfront, h0, h1, M, Ti, d->Ch, d->kfpad, inverse ? 0 : 1,
                          fp8_layer(0) ? h8c : nullptr, st);
@@ -535,8 +565,12 @@ static int flow_run_impl(const fwn_flow_desc* d, int64_t B, int64_t T, float* xa
         }
         chain->n_partial = fwn_tail_slots(desc_tail(d, M), M, tc.h0_next != nullptr);
     }
+    // ragged forward: the saving tail (fwn_tail_train's), S and U parked in the two free h buffers, Z kept for the per-clip sums
+    if (rg) { tc.save_s = hn; tc.save_u = hc; tc.save_z = rg->z; }
     fwn_launch_tail(o, (long)M * 256, d->L, d->Wskip, d->bskip, d->Wfinal, d->bfinal, d->Wzero, d->bzero,
-                    d->ezero, d->an, xa, xb, inverse ? nullptr : partial, M, d->Ch, d->npt, inverse, hn, hc, chain ? &tc : nullptr, d->Wts, st);
+                    d->ezero, d->an, xa, xb, inverse ? nullptr : partial, M, d->Ch, d->npt, inverse, hn, hc, (chain || rg) ? &tc : nullptr,
+                    d->Wts, st);
+    if (rg) fwn_launch_ragged_logdet(rg->z, (long)B, Ti, d->Ch, d->ezero, d->an, len, (int)B, 2 * d->Ch, rg->acc, st);
     return check_launch("fwn_flow_run");
 }
 
@@ -897,14 +931,15 @@ static int planes_go_home(Planes& pl, size_t plane_bytes, hipStream_t st) {   //
 }
 
 struct Carve {
-    size_t cplanes, up0, up1, planes, plane3, h0, h1, o, P, Ppart, partial, mom, h8a, h8b, sync, mel, total;
+    size_t cplanes, up0, up1, planes, plane3, h0, h1, o, P, Ppart, partial, mom, h8a, h8b, sync, mel, zsave, acc, total;
     size_t sync_stride, sync_bytes;       // one block of counters per flow (flow_persist.h), zeroed once per pass
     BlockPlan blk[16];
 };
 
 // ragged: a pass with per-clip lengths - every flow a launch per stage (the zero-fills of model_pass run between the
 // stages; the chained front conv reads out_b rows inside the launch that writes them), plus a copy of the mel to mask
-static Carve carve(const fwn_model_desc* m, int64_t B, int64_t T, bool ragged = false) {
+// ragged_fwd: a ragged forward pass - also one flow's Z (reused by the next flow) and every flow's per-clip log-det sums
+static Carve carve(const fwn_model_desc* m, int64_t B, int64_t T, bool ragged = false, bool ragged_fwd = false) {
     Carve c;
     size_t off = 0;
     const size_t half = m->num_mels / 2;
@@ -951,6 +986,8 @@ static Carve carve(const fwn_model_desc* m, int64_t B, int64_t T, bool ragged = 
     c.sync_bytes = c.sync_stride * (size_t)m->n_block * m->n_flow;
     c.sync = off; off = align_up(off + c.sync_bytes);
     c.mel = off; off = align_up(off + (ragged ? (size_t)B * (T / hop_of(m)) * m->num_mels * 4 : 0));
+    c.zsave = off; off = align_up(off + (ragged_fwd ? (size_t)B * T * 4 : 0));          // [M][2 Ch] fp32 = B T floats at every block
+    c.acc = off; off = align_up(off + (ragged_fwd ? (size_t)m->n_block * m->n_flow * B * fwn_ragged_logdet_nslot((long)B) * 8 : 0));
     c.total = off;
     return c;
 }
@@ -962,6 +999,10 @@ size_t fwn_workspace_bytes(const fwn_model_desc* m, int64_t B, int64_t T) {
 size_t fwn_ragged_workspace_bytes(const fwn_model_desc* m, int64_t B, int64_t T) {
     if (check_model(m, B, T) != FWN_OK) return 0;
     return carve(m, B, T, true).total;
+}
+size_t fwn_ragged_forward_workspace_bytes(const fwn_model_desc* m, int64_t B, int64_t T) {
+    if (check_model(m, B, T) != FWN_OK || B >= 32768) return 0;
+    return carve(m, B, T, true, true).total;
 }
 
 // len (ragged batch): the stages run on a copy of the mel with the frames past each clip's end zeroed, and so is every inner
@@ -1052,21 +1093,23 @@ int fwn_model_persist_status(const fwn_model_desc* m, int64_t B, int64_t T, cons
 // moments -> reduce callback), and ends in the prior.  Reverse: both orders backwards, the parity flipped before each flow
 // (model.py:199); it ends in the merge of the planes into x_out.  A block's plan (carve) decides its conditioning launch and
 // whether its flows run as one launch each; the init pass runs no flow as one launch, but zeroes the sync region all the same.
-// len (reverse only): a ragged batch - the same stages under the plan of carve(.., ragged), with the rows past each clip's end
-// zeroed wherever a later stage reads across it: mel and inner up-sampling stages, planes, h (flow_run_impl), and x_out.
+// len: a ragged batch - the same stages under the plan of carve(.., ragged), with the rows past each clip's end zeroed wherever
+// a later stage reads across it: mel and inner up-sampling stages, planes, h (flow_run_impl), and x_out.  Forward with len:
+// no init; every flow's x_a plane gets -shift in those rows before its front conv and its tail keeps Z (flow_run_impl), the
+// per-clip log-det sums of all flows and the per-clip prior end in out2 [2][B] (the tails' own partials are ignored).
 static int model_pass(const fwn_model_desc* m, int64_t B, int64_t T, const float* in, const float* mel, void* workspace,
                       size_t workspace_bytes, bool reverse, int init, fwn_reduce_fn reduce, void* user, float* out2, float* z_planes,
                       float* x_out, void* stream, const int32_t* len = nullptr) {
-    const char* what = len ? "fwn_model_reverse_ragged" : reverse ? "fwn_model_reverse" : "fwn_model_forward";
+    const char* what = len ? (reverse ? "fwn_model_reverse_ragged" : "fwn_model_forward_ragged") : reverse ? "fwn_model_reverse" : "fwn_model_forward";
     int rc = check_model(m, B, T);
     if (rc) return rc;
     REQUIRE(in && mel && workspace && (reverse ? x_out : out2), "%s: null pointer", what);
     REQUIRE((((uintptr_t)workspace) & 255) == 0, "workspace must be 256-byte aligned");
     REQUIRE(!reverse || ((m->n_block * m->n_flow) & 1) == 0,
             "reverse with odd n_block*n_flow ends in swapped channel order (model.py:199,254); unsupported");
-    REQUIRE(!len || (reverse && !m->gate_fp8),
-            "%s: per-clip lengths go with the inverse pass of a model without fp8 gates (its e4m3 copies of h are not masked)", what);
-    const Carve c = carve(m, B, T, len != nullptr);
+    REQUIRE(!len || (!m->gate_fp8 && !init),
+            "%s: per-clip lengths go with a model without fp8 gates (its e4m3 copies of h are not masked) and without the data-dependent init", what);
+    const Carve c = carve(m, B, T, len != nullptr, len && !reverse);
     if (workspace_bytes < c.total)
         return fail(FWN_ERR_WORKSPACE, "workspace %zu < required %zu bytes", workspace_bytes, c.total);
     hipStream_t st = (hipStream_t)stream;
@@ -1118,8 +1161,10 @@ static int model_pass(const fwn_model_desc* m, int64_t B, int64_t T, const float
             double* mom = (double*)(ws + c.mom) + (size_t)(i * nf + j) * mom_stride;
             unsigned* sync = (!init && b.one_launch) ? (unsigned*)(ws + c.sync + (size_t)(i * nf + j) * c.sync_stride) : nullptr;
             FlowChain ch = flow_chain(m, d, next, M, init != 0, pl.spare, have_h0, b.chained && !sync);
+            const FlowRagged rg{(float*)(ws + c.zsave), (double*)(ws + c.acc) + (size_t)(i * nf + j) * B * fwn_ragged_logdet_nslot((long)B)};
             rc = flow_run_impl(d, B, T, pl.at[p], pl.at[p ^ 1], ca, hA, hB, ws + c.o, P, reverse ? nullptr : partial + poff, reverse, init,
-                               mom, reduce, user, m->gate_fp8 ? ws + c.h8a : nullptr, m->gate_fp8 ? ws + c.h8b : nullptr, &ch, stream, sync, len);
+                               mom, reduce, user, m->gate_fp8 ? ws + c.h8a : nullptr, m->gate_fp8 ? ws + c.h8b : nullptr, &ch, stream, sync, len,
+                               len && !reverse ? &rg : nullptr);
             if (rc) return rc;
             mask_planes();
             if (!reverse) poff += ch.n_partial;
@@ -1135,7 +1180,8 @@ static int model_pass(const fwn_model_desc* m, int64_t B, int64_t T, const float
         fwn_launch_merge(planes, B, T, x_out, st);
         if (len) fwn_launch_mask_rows(x_out, (long)B, (long)T, 4, len, (int)B, 1, st);
     } else {
-        fwn_launch_prior(planes, (long)(B * T), partial, poff, 1.0 / (double)(B * T), out2, st);
+        if (len) fwn_launch_ragged_finish(planes, (long)B, (long)T, (const double*)(ws + c.acc), m->n_block * nf, nf, len, out2, st);
+        else fwn_launch_prior(planes, (long)(B * T), partial, poff, 1.0 / (double)(B * T), out2, st);
         if (z_planes) {
             hipError_t e = hipMemcpyAsync(z_planes, planes, (size_t)B * T * 4, hipMemcpyDeviceToDevice, st);
             if (e != hipSuccess) return fail(FWN_ERR_HIP, "hipMemcpyAsync: %s", hipGetErrorString(e));
@@ -1165,6 +1211,12 @@ int fwn_model_reverse_ragged(const fwn_model_desc* m, int64_t B, int64_t T, cons
     REQUIRE(len_dev, "fwn_model_reverse_ragged: null lengths");
     REQUIRE(B < 32768, "fwn_model_reverse_ragged: B=%lld clips (at most 32767 per call)", (long long)B);
     return model_pass(m, B, T, z, mel, workspace, workspace_bytes, true, 0, nullptr, nullptr, nullptr, nullptr, x_out, stream, len_dev);
+}
+int fwn_model_forward_ragged(const fwn_model_desc* m, int64_t B, int64_t T, const float* x, const float* mel, const int32_t* len_dev,
+                             void* workspace, size_t workspace_bytes, float* out2B, float* z_planes, void* stream) {
+    REQUIRE(len_dev, "fwn_model_forward_ragged: null lengths");
+    REQUIRE(B < 32768, "fwn_model_forward_ragged: B=%lld clips (at most 32767 per call)", (long long)B);
+    return model_pass(m, B, T, x, mel, workspace, workspace_bytes, false, 0, nullptr, nullptr, out2B, z_planes, nullptr, stream, len_dev);
 }
 
 }  // extern "C"

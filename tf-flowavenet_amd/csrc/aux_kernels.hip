@@ -491,6 +491,155 @@ __global__ __launch_bounds__(256) void mask_rows_kernel(char* __restrict__ buf, 
     }
 }
 
+// ---- ragged forward: the rows past each clip's end of a flow's x_a plane hold -shift --------------------
+// The front conv applies ActNorm on the fly, (v + shift[tau]) * scale[tau]: a zero in a padded row would reach its +-1 taps
+// as shift * scale, where a clip on its own is zero-padded AFTER ActNorm.  (-s + s) is exactly +0, so with -shift[tau] in
+// those rows every product is an exact zero.  buf [nclip][rows][Ch] fp32 (Ch a power of two), shift [Ch]; the clamping, the
+// grid and the 16-byte stores with dword heads and tails are mask_rows_kernel's.
+__global__ __launch_bounds__(256) void fill_neg_shift_kernel(float* __restrict__ buf, long rows, int Ch,
+                                                             const float* __restrict__ shift, const int* __restrict__ len,
+                                                             int nlen, int spr) {
+    const long c = blockIdx.y;
+    long keep = (long)len[c % nlen] / spr;
+    keep = keep < 0 ? 0 : (keep > rows ? rows : keep);
+    if (keep == rows) return;
+    const size_t row_bytes = (size_t)Ch * 4;
+    const uintptr_t clip = (uintptr_t)buf + (size_t)c * rows * row_bytes;
+    const uintptr_t p0 = clip + (size_t)keep * row_bytes, p1 = clip + (size_t)rows * row_bytes;
+    uintptr_t a0 = (p0 + 15) & ~(uintptr_t)15;
+    if (a0 > p1) a0 = p1;
+    uintptr_t a1 = p1 & ~(uintptr_t)15;
+    if (a1 < a0) a1 = a0;
+    auto val = [&](uintptr_t q) { return -shift[((q - clip) >> 2) & (size_t)(Ch - 1)]; };     // rows start at the clip's base
+    for (uintptr_t q = a0 + ((size_t)blockIdx.x * 256 + threadIdx.x) * 16; q < a1; q += (size_t)gridDim.x * 256 * 16)
+        *(float4*)q = make_float4(val(q), val(q + 4), val(q + 8), val(q + 12));
+    if (blockIdx.x == 0) {
+        const uintptr_t h = p0 + (size_t)threadIdx.x * 4, t = a1 + (size_t)(threadIdx.x - 4) * 4;
+        if (threadIdx.x < 4 && h < a0) *(float*)h = val(h);
+        if (threadIdx.x >= 4 && threadIdx.x < 8 && t < p1) *(float*)t = val(t);
+    }
+}
+
+// ---- ragged forward: one flow's log-det terms per clip -------------------------------------------------
+// Z [nclip][rows][2 Ch] fp32 is what the saving tail keeps of the ZeroConv (fwn_tail_chain.save_z): log_s = Z[row][tau] *
+// ez[(tau / 32) * 64 + tau % 32] for tau < Ch (the pair-tile order of fwn_flow_desc.ezero).  blockIdx.y = clip, blockIdx.x =
+// chunk: the workgroups of a clip stride over its rows [0, len / spr) only - a padded row is never loaded - and each leaves
+// the fp64 sum of -log_s over its share in acc[clip][chunk] (a workgroup without a share leaves 0).  The order of every sum
+// is fixed by the grid: no atomics.  16-byte loads: Ch / 4 per row from Ch = 4 on, one per row at Ch = 2, one per two rows at
+// Ch = 1 (single dwords where the clip's base is not 16-byte aligned).  an (may be NULL): chunk 0 also leaves the flow's
+// ActNorm term sum_tau 3 logs_a + 3 logs_b in acc[clip][nslot - 1].
+__device__ __forceinline__ float ez_of(const float* __restrict__ ez, int tau) { return ez[(tau >> 5) * 64 + (tau & 31)]; }
+__global__ __launch_bounds__(256) void ragged_logdet_kernel(const float* __restrict__ Z, long rows, int Ch,
+                                                            const float* __restrict__ ez, const float* __restrict__ an,
+                                                            const int* __restrict__ len, int nlen, int spr,
+                                                            double* __restrict__ acc, int nslot) {
+    __shared__ double red[256];
+    const long c = blockIdx.y;
+    long keep = (long)len[c % nlen] / spr;
+    keep = keep < 0 ? 0 : (keep > rows ? rows : keep);
+    const float* zc = Z + (size_t)c * rows * 2 * Ch;
+    const long stride = (long)gridDim.x * 256, first = (long)blockIdx.x * 256 + threadIdx.x;
+    double s = 0.0;
+    if (Ch >= 4 && ((uintptr_t)zc & 15) == 0) {
+        const int upr = Ch >> 2;                              // 16-byte pieces of log_s per row
+        const long n = keep * upr;
+        for (long i = first; i < n; i += stride) {
+            const long row = i / upr;
+            const int t0 = (int)(i - row * upr) * 4;
+            const float4 v = *(const float4*)(zc + (size_t)row * 2 * Ch + t0);
+            const float* e = ez + (t0 >> 5) * 64 + (t0 & 31);                         // four channels of one pair tile
+            s -= (double)v.x * (double)e[0] + (double)v.y * (double)e[1] + (double)v.z * (double)e[2] + (double)v.w * (double)e[3];
+        }
+    } else if (Ch == 2 && ((uintptr_t)zc & 15) == 0) {
+        const double e0 = ez[0], e1 = ez[1];
+        for (long i = first; i < keep; i += stride) {
+            const float4 v = *(const float4*)(zc + (size_t)i * 4);                    // log_s 0, log_s 1, t 0, t 1
+            s -= (double)v.x * e0 + (double)v.y * e1;
+        }
+    } else if (Ch == 1 && ((uintptr_t)zc & 15) == 0) {
+        const double e0 = ez[0];
+        for (long i = first; i < (keep >> 1); i += stride) {
+            const float4 v = *(const float4*)(zc + (size_t)i * 4);                    // two rows of (log_s, t)
+            s -= (double)v.x * e0 + (double)v.z * e0;
+        }
+        if ((keep & 1) && first == 0) s -= (double)zc[(size_t)(keep - 1) * 2] * e0;
+    } else {
+        const long n = keep * Ch;
+        for (long i = first; i < n; i += stride) {
+            const long row = i / Ch;
+            const int tau = (int)(i - row * Ch);
+            s -= (double)zc[(size_t)row * 2 * Ch + tau] * (double)ez_of(ez, tau);
+        }
+    }
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int st = 128; st > 0; st >>= 1) {
+        if (threadIdx.x < st) red[threadIdx.x] += red[threadIdx.x + st];
+        __syncthreads();
+    }
+    double* out = acc + (size_t)c * nslot;
+    if (threadIdx.x == 0) out[blockIdx.x] = red[0];
+    if (an && blockIdx.x == 0) {
+        double a = 0.0;
+        for (int tau = threadIdx.x; tau < Ch; tau += 256) a += (double)an[3 * Ch + tau] + (double)an[7 * Ch + tau];
+        __syncthreads();
+        red[threadIdx.x] = a;
+        __syncthreads();
+        for (int st = 128; st > 0; st >>= 1) {
+            if (threadIdx.x < st) red[threadIdx.x] += red[threadIdx.x + st];
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) out[nslot - 1] = red[0];
+    }
+}
+
+// ---- ragged forward: out[0][b] = log_p, out[1][b] = logdet of clip b ------------------------------------
+// One workgroup per clip.  acc [nflows][nclip][nslot] fp64: what ragged_logdet_kernel left for every flow, flow f of block
+// f / n_flow with Ch = 2^(f / n_flow) channels per plane.  A flow's term is mean_C(3 logs) + mean(-log_s) / 2 over the clip's
+// own rows (model.py:80,135): sum_an / (2 Ch) + sum(-log_s) / (2 rows Ch), and 2 rows Ch = len at every block.  The prior is
+// the mean of 0.5 (-log 2 pi - z^2) over [0, len / 2) of both planes (model.py:342-343): nothing past a clip's end is
+// loaded.  Everything is added in fp64 in an order the launch fixes.
+__global__ __launch_bounds__(256) void ragged_finish_kernel(const float* __restrict__ planes, long nclip, long T,
+                                                            const double* __restrict__ acc, int nflows, int n_flow, int nslot,
+                                                            const int* __restrict__ len, float* __restrict__ out) {
+    __shared__ double r1[256], r2[256];
+    const long c = blockIdx.x, hT = T >> 1;
+    long n = len[c];
+    n = n < 0 ? 0 : (n > T ? T : n);
+    const long hn = n >> 1;
+    double s = 0.0, ld = 0.0;
+    for (int q = 0; q < 2; ++q) {
+        const float* z = planes + ((size_t)q * nclip + c) * hT;
+        long i = 0;
+        if (((uintptr_t)z & 15) == 0) {
+            for (long k = threadIdx.x; k < (hn >> 2); k += 256) {
+                const float4 v = *(const float4*)(z + k * 4);
+                s += (double)v.x * v.x + (double)v.y * v.y + (double)v.z * v.z + (double)v.w * v.w;
+            }
+            i = hn & ~3L;
+        }
+        for (long k = i + threadIdx.x; k < hn; k += 256) s += (double)z[k] * z[k];
+    }
+    for (int f = 0; f < nflows; ++f) {
+        const double* a = acc + ((size_t)f * nclip + c) * nslot;
+        double raw = 0.0;
+        for (int k = threadIdx.x; k < nslot - 1; k += 256) raw += a[k];
+        ld += raw / (double)(n > 0 ? n : 1);
+        if (threadIdx.x == 0) ld += a[nslot - 1] / (double)(2 << (f / n_flow));
+    }
+    r1[threadIdx.x] = s;
+    r2[threadIdx.x] = ld;
+    __syncthreads();
+    for (int st = 128; st > 0; st >>= 1) {
+        if (threadIdx.x < st) { r1[threadIdx.x] += r1[threadIdx.x + st]; r2[threadIdx.x] += r2[threadIdx.x + st]; }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        out[c] = (float)(0.5 * (-1.8378770664093453 - r1[0] / (double)(n > 0 ? n : 1)));
+        out[nclip + c] = (float)r2[0];
+    }
+}
+
 // ---- ActNorm data-dependent init for one flow -----------------------------------------------
 // One workgroup per (plane role, channel).  an[role][0..3][tau] = shift b, scale exp(3 logs),
 // inverse scale, 3*logs.  model.py:55-56 (b = -mean), :65-71 (logs from mean((x+b)^2)).
@@ -724,6 +873,29 @@ void fwn_launch_mask_rows(void* base, long nclip, long rows, long row_bytes, con
     const long gx = want < 1 ? 1 : (want > cap ? cap : want);
     hipLaunchKernelGGL(mask_rows_kernel, dim3((unsigned)gx, (unsigned)nclip), dim3(256), 0, st, (char*)base, rows, row_bytes, len,
                        nlen, samples_per_row);
+}
+void fwn_launch_fill_neg_shift(float* plane, long nclip, long rows, int Ch, const float* shift, const int* len, int nlen,
+                               int samples_per_row, hipStream_t st) {
+    const long want = (rows * Ch * 4 + 16383) / 16384, cap = nclip < 2048 ? 2048 / nclip : 1;       // as fwn_launch_mask_rows
+    const long gx = want < 1 ? 1 : (want > cap ? cap : want);
+    hipLaunchKernelGGL(fill_neg_shift_kernel, dim3((unsigned)gx, (unsigned)nclip), dim3(256), 0, st, plane, rows, Ch, shift, len, nlen,
+                       samples_per_row);
+}
+// slots per clip and flow: up to 32 chunk sums (about 2048 workgroups over all clips at most) and the ActNorm term
+int fwn_ragged_logdet_nslot(long nclip) {
+    const long cap = nclip < 2048 ? 2048 / nclip : 1;
+    return (int)(cap > 32 ? 32 : cap) + 1;
+}
+void fwn_launch_ragged_logdet(const float* Z, long nclip, long rows, int Ch, const float* ez, const float* an, const int* len,
+                              int nlen, int samples_per_row, double* acc, hipStream_t st) {
+    const int nslot = fwn_ragged_logdet_nslot(nclip);
+    hipLaunchKernelGGL(ragged_logdet_kernel, dim3((unsigned)(nslot - 1), (unsigned)nclip), dim3(256), 0, st, Z, rows, Ch, ez, an, len,
+                       nlen, samples_per_row, acc, nslot);
+}
+void fwn_launch_ragged_finish(const float* planes, long nclip, long T, const double* acc, int nflows, int n_flow, const int* len,
+                              float* out2B, hipStream_t st) {
+    hipLaunchKernelGGL(ragged_finish_kernel, dim3((unsigned)nclip), dim3(256), 0, st, planes, nclip, T, acc, nflows, n_flow,
+                       fwn_ragged_logdet_nslot(nclip), len, out2B);
 }
 void fwn_launch_ddi_moments(const float* xa, const float* xb, int M, int Ch, double* mom, hipStream_t st) {
     hipLaunchKernelGGL(ddi_moments_kernel, dim3(2 * Ch), dim3(256), 0, st, xa, xb, M, Ch, mom);

@@ -137,6 +137,19 @@ void fwn_launch_merge(const float* planes, long B, long T, float* x, hipStream_t
 // rows past a clip's own length); len is read on the device and clamped to the buffer.  base and row_bytes: multiples of 4.
 void fwn_launch_mask_rows(void* base, long nclip, long rows, long row_bytes, const int* len, int nlen, int samples_per_row,
                           hipStream_t st);
+// ragged forward (aux_kernels.hip).  -shift[tau] into rows [len / samples_per_row, rows) of every clip of a [nclip][rows][Ch]
+// fp32 plane: the front conv's on-the-fly ActNorm then gives exact zeros there.  Clamped like fwn_launch_mask_rows.
+void fwn_launch_fill_neg_shift(float* plane, long nclip, long rows, int Ch, const float* shift, const int* len, int nlen,
+                               int samples_per_row, hipStream_t st);
+// One flow's log-det terms per clip from the tail's saved Z [nclip][rows][2 Ch]: acc[clip][0 .. nslot - 1) = fp64 chunk sums of
+// -log_s over the clip's own rows, acc[clip][nslot - 1] = sum_tau of the ActNorm's 3 logs (both planes; an may be NULL);
+// nslot = fwn_ragged_logdet_nslot(nclip).  fwn_launch_ragged_finish turns acc [nflows][nclip][nslot] and the planes into
+// out2B [2][nclip] = per-clip (log_p, logdet).
+int fwn_ragged_logdet_nslot(long nclip);
+void fwn_launch_ragged_logdet(const float* Z, long nclip, long rows, int Ch, const float* ez, const float* an, const int* len,
+                              int nlen, int samples_per_row, double* acc, hipStream_t st);
+void fwn_launch_ragged_finish(const float* planes, long nclip, long T, const double* acc, int nflows, int n_flow, const int* len,
+                              float* out2B, hipStream_t st);
 void fwn_launch_ddi(const float* xa, const float* xb, int M, int Ch, float* an, hipStream_t st);
 void fwn_launch_ddi_moments(const float* xa, const float* xb, int M, int Ch, double* mom, hipStream_t st);
 void fwn_launch_ddi_from_moments(const double* mom, int Ch, float* an, hipStream_t st);

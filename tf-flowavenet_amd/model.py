@@ -130,15 +130,17 @@ class FloWaveNet:
     def _workspace(self, b, t, ragged=False):
         """Scratch for one pass.  One workspace per (B, T, HIP stream): passes issued on different
         streams (e.g. a forward and an inverse overlapping on the chip) never share scratch.  A ragged inverse
-        (``reverse(..., lengths=)``) keeps a workspace of its own: it also holds the masked copy of the mel."""
+        (``reverse(..., lengths=)``) keeps a workspace of its own: it also holds the masked copy of the mel.  So does a
+        ragged forward (``ragged="forward"``): one flow's ZeroConv output and the per-clip log-det sums on top of that."""
         import torch
-        key = (b, t, self._stream()) + (("ragged",) if ragged else ())
+        key = (b, t, self._stream()) + ((("ragged", ragged) if ragged == "forward" else ("ragged",)) if ragged else ())
         ws = self._ws.get(key)
         if ws is None:
-            size = self._lib.fwn_ragged_workspace_bytes if ragged else self._lib.fwn_workspace_bytes
-            n = size(C.byref(self._packed.model_desc), b, t)
+            name = ("fwn_ragged_forward_workspace_bytes" if ragged == "forward" else "fwn_ragged_workspace_bytes") if ragged \
+                else "fwn_workspace_bytes"
+            n = getattr(self._lib, name)(C.byref(self._packed.model_desc), b, t)
             if n == 0:
-                _lib.check(-1, "fwn_ragged_workspace_bytes" if ragged else "fwn_workspace_bytes")
+                _lib.check(-1, name)
             for k in [k for k in self._ws if k[:2] != (b, t)]:
                 del self._ws[k]   # keep only the current shape's workspaces
             ws = torch.empty(n + 256, dtype=torch.uint8, device=self._device)
@@ -162,11 +164,20 @@ class FloWaveNet:
         return int(self._lib.fwn_model_persist_status(C.byref(self._packed.model_desc), b, t, ws, self._stream()))
 
     # ------------------------------------------------------------------ reference surface
-    def forward(self, x, c, g=None, return_z=False):
-        """x [B,T,1], c [B,T/hop,num_mels] -> (log_p, logdet) fp32 0-dim tensors (model.py:317-347)."""
+    def forward(self, x, c, g=None, return_z=False, lengths=None):
+        """x [B,T,1], c [B,T/hop,num_mels] -> (log_p, logdet) fp32 0-dim tensors (model.py:317-347).
+
+        lengths (a list, NumPy array or tensor of B sample counts, the rules of ``reverse``): a ragged batch.  ``log_p`` and
+        ``logdet`` are then fp32 tensors of shape [B]: entry ``b`` is what ``forward(x[b:b+1, :lengths[b]], c[b:b+1,
+        :lengths[b] // hop])`` returns for that clip alone (to rounding) - the prior mean over the clip's own samples, the
+        coupling means over its own rows.  Whatever (finite) ``x`` and ``c`` hold past a clip's length reaches no output
+        bit; with ``return_z`` the planes are exactly 0 there, and ``reverse(z, c, lengths=lengths)`` inverts them.
+        ``init=True`` (the data-dependent init is defined on a full batch) and ``gate_fp8`` models raise ``ValueError``."""
         import torch
         self._check_g(g)
         b, t, x32, c32 = self._prep(x, c, "x")
+        if lengths is not None:
+            return self._forward_ragged(b, t, x32, c32, return_z, lengths)
         wsp, wsn = self._workspace(b, t)
         out2 = torch.empty(2, dtype=torch.float32, device=self._device)
         zp = torch.empty(2, b, t // 2, dtype=torch.float32, device=self._device) if return_z else None
@@ -181,6 +192,22 @@ class FloWaveNet:
         if return_z:
             return out2[0], out2[1], zp
         return out2[0], out2[1]
+
+    def _forward_ragged(self, b, t, x32, c32, return_z, lengths):
+        import torch
+        if self._gate_fp8:
+            raise ValueError("a gate_fp8 model takes no lengths: the e4m3 copies of h are not masked")
+        if self._init:
+            raise ValueError("init=True takes no lengths: the data-dependent ActNorm init is defined on a full batch")
+        lens = torch.tensor(self._check_lengths(lengths, b, t), dtype=torch.int32).to(self._device)
+        wsp, wsn = self._workspace(b, t, ragged="forward")
+        out = torch.empty(2, b, dtype=torch.float32, device=self._device)
+        zp = torch.empty(2, b, t // 2, dtype=torch.float32, device=self._device) if return_z else None
+        rc = self._lib.fwn_model_forward_ragged(C.byref(self._packed.model_desc), b, t, x32.data_ptr(), c32.data_ptr(),
+                                                lens.data_ptr(), wsp, wsn, out.data_ptr(), zp.data_ptr() if return_z else None,
+                                                self._stream())
+        _lib.check(rc, "fwn_model_forward_ragged")
+        return (out[0], out[1], zp) if return_z else (out[0], out[1])
 
     def _dp_world(self):
         import torch.distributed as dist
@@ -215,7 +242,7 @@ class FloWaveNet:
         _lib.check(rc, "fwn_model_forward_init")
 
     def _check_lengths(self, lengths, b, t):
-        """``lengths`` of a ragged ``reverse`` -> list of B ints, validated on the host before anything is launched."""
+        """``lengths`` of a ragged ``reverse`` / ``forward`` -> list of B ints, validated on the host before anything is launched."""
         import math
         vals = lengths.detach().cpu().tolist() if hasattr(lengths, "detach") else np.asarray(lengths).tolist()
         if not isinstance(vals, list) or len(vals) != b:
