@@ -41,9 +41,10 @@ def adam_step(theta, g, m, v, step, lr, b1=0.9, b2=0.999, eps=1e-8):
     return theta - lr_t * m / (np.sqrt(v) + eps), m, v
 
 
-def data_parallel_update(theta, tower_grads_scaled, m, v, step, scale=64.0):
-    """One train.py:75-81 update on flat vectors: tower gradients of (scale * loss)."""
+def data_parallel_update(theta, tower_grads_scaled, m, v, step, scale=64.0, clip=1.0):
+    """One train.py:75-81 update on flat vectors: tower gradients of (scale * loss); clip: the global-norm
+    threshold (the reference's is 1)."""
     g = np.mean(np.stack(tower_grads_scaled, 0), 0) / scale
-    (g,), gn = clip_by_global_norm([g], 1.0)
+    (g,), gn = clip_by_global_norm([g], clip)
     theta, m, v = adam_step(theta, g, m, v, step, learning_rate(step - 1))
     return theta, m, v, gn

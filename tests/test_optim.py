@@ -98,25 +98,33 @@ def test_bucketed_allreduce_is_the_tower_mean():
 
 
 @pytest.mark.gpu
-def test_fused_clip_adam_matches_oracle_and_repacks():
+@pytest.mark.parametrize("clip", [1.0, 0.25])
+def test_fused_clip_adam_matches_oracle_and_repacks(clip):
+    """clip: DataParallelAdam's global-norm threshold - the kernel scales by it twice (g gscale / max(norm, clip), then
+    times clip); the reference's 1.0 hides a slip in either place."""
     from tf_flowavenet_amd.model import FloWaveNet
     hp = small_hparams(n_block=2, n_flow=2)
     params = W.synthetic_params(hp, 11, actnorm="random")
-    opt = optim.DataParallelAdam(hp, params)
+    opt = optim.DataParallelAdam(hp, params, clip=clip)
     lay = opt.layout
     rng = np.random.default_rng(5)
     theta = lay.flatten(params).astype(np.float64)
     m = np.zeros_like(theta)
     v = np.zeros_like(theta)
-    for step, amp in enumerate([1e-4, 3.0, 0.05], start=1):          # below / above / below the clip threshold
+    # global norms amp sqrt(size) / 64 = 0.003, 100, 1.7, 0.5 and 0.1 at this layout (4.5 M elements): both sides of each
+    # threshold, 0.5 between the two
+    norms = []
+    for step, amp in enumerate([1e-4, 3.0, 0.05, 0.015, 0.003], start=1):
         g = (amp * rng.standard_normal(lay.size)).astype(np.float32)
         opt.g.copy_(torch.from_numpy(g))
         gn = float(opt.step(loss_scale=64.0))
-        theta, m, v, gn0 = O.data_parallel_update(theta, [g.astype(np.float64)], m, v, step, scale=64.0)
+        theta, m, v, gn0 = O.data_parallel_update(theta, [g.astype(np.float64)], m, v, step, scale=64.0, clip=clip)
+        norms.append(gn0)
         assert gn == pytest.approx(gn0, rel=1e-5)
         np.testing.assert_allclose(opt.w.cpu().numpy(), theta, rtol=2e-5, atol=1e-7)
         np.testing.assert_allclose(opt.m.cpu().numpy(), m, rtol=1e-5, atol=1e-9)
         np.testing.assert_allclose(opt.v.cpu().numpy(), v, rtol=1e-5, atol=1e-12)
+    assert min(norms) < 0.25 < norms[3] < 1.0 < max(norms) and norms[4] < 0.25 and norms[2] > 1.0
     # fp32 masters -> bf16 MFMA layouts straight from the device buffer (utils.py:3-31 analogue)
     inp = W.synthetic_inputs(hp, 2, 128)
     x, c = torch.from_numpy(inp["x"]).cuda(), torch.from_numpy(inp["c"]).cuda()
