@@ -347,7 +347,13 @@ int fwn_clip_adam_dev(float* w, const float* g, float* m, float* v, int64_t n, c
  * gate_aux != NULL (bf16 output only): the 256 output columns from gate_col0 (a multiple of 256) are a gradient d with
  * respect to a gated layer's output o = tanh(f) sigmoid(g); they are not stored in Y but, rounded to bf16 like Y, go
  * through the gate's derivative with gate_aux = [tanh f | sigmoid g] (bf16 [M][512], kept by fwn_gate_train):
- * gate_out[M][512] (bf16) = [d sg (1 - tf^2) | d tf sg (1 - sg)] - what fwn_gate_bwd computes from a stored d. */
+ * gate_out[M][512] (bf16) = [d sg (1 - tf^2) | d tf sg (1 - sg)] - what fwn_gate_bwd computes from a stored d.
+ * row_len != NULL (ragged batches; additive, FWN_VERSION unchanged: a host that zero-fills the descriptor keeps today's bits):
+ * DEVICE int32 [M / Ti] lengths in samples, one per clip of Ti rows, a row holding len_spr samples.  Output rows
+ * [row_len[b] / len_spr, Ti) of clip b are stored as exact 0 whatever the product gives there (in Y, or through the gate
+ * derivative in gate_out) - the data-gradient form of a forward pass that overwrote those rows with a constant: a forward fill
+ * of rows becomes a backward drop of the gradient at those rows.  Needs Ti > 0, M a multiple of Ti, len_spr > 0, nsplit == 1;
+ * refused together with accumulate (what is already in Y at those rows is not a product of this call). */
 #define FWN_GEMM_MAXSEG 8
 typedef struct fwn_gemm_seg { const void* x; int32_t rows, ld, k, shift, koff, pad_; } fwn_gemm_seg;
 typedef struct fwn_gemm_desc {
@@ -362,6 +368,7 @@ typedef struct fwn_gemm_desc {
     int64_t split_stride;
     float oscale;       int32_t gate_col0;
     const void* gate_aux; void* gate_out;
+    const int32_t* row_len; int32_t len_spr, pad1_;
 } fwn_gemm_desc;
 int fwn_gemm(const fwn_gemm_desc* g, void* stream);
 /* For tap z < ntap (shift = shift0 + z*dshift): dst[z*C + c][m] = src[m + shift][c] (zero where the tap
@@ -401,6 +408,15 @@ int fwn_coupling_fwd(float* yb, const float* Z, const float* ez, int64_t M, int 
                      void* stream);
 int fwn_coupling_bwd(float* g, float* out_b, const float* Z, const float* ez, int64_t M, int Ch, float cls, void* dZ,
                      int ldz, float* dzz, void* stream);
+/* fwn_coupling_bwd of a ragged batch: M = B rows, clip b holds len[b] samples (DEVICE int32 [B], clamped to [0, rows
+ * samples_per_row] on the device) = its first len[b] / samples_per_row rows.  Inside a clip the log-det term is per clip,
+ * cls = (float)(1 / ((double)B len[b])) - with len[b] = rows samples_per_row = 2 rows Ch the bits of fwn_coupling_bwd's 1 / (2 M Ch).
+ * Rows past a clip's end: g, out_b, both halves of dZ and of dzz are written as exact 0 (the forward pass zeroed out_b there,
+ * so whatever gradient arrives at those rows is dropped).  ya / ya_bf (both or neither): also ya_bf [M][ldya] (bf16, ldya >= Ch,
+ * zero padded) = the other plane, 0 in the rows past a clip's end, and the zero padding of dZ's columns [2 Ch, ldz). */
+int fwn_coupling_bwd_ragged(float* g, float* out_b, const float* Z, const float* ez, int64_t B, int64_t rows, int Ch,
+                            const int32_t* len, int32_t samples_per_row, void* dZ, int ldz, float* dzz, const float* ya,
+                            void* ya_bf, int ldya, void* stream);
 int fwn_gate_bwd(const void* d_o, int ld_do, const void* aux, int64_t M, void* dpre, void* stream);
 int fwn_colsum_partials(int64_t M, int C);
 int fwn_colsum_prod(const float* A, const float* B, int64_t M, int C, float scale, float* partial, float* out,
@@ -415,6 +431,13 @@ int64_t fwn_flow_small_grads_partials(int64_t M, int Ch);
 int fwn_flow_small_grads(float* ga, float* ya, float* gb, float* yb, const float* dzz, const float* an, int64_t M, int Ch,
                          const int64_t* br, const int64_t* zc, double* partial, float* db, float* dlogs, float* dzscale,
                          void* stream);
+/* fwn_flow_small_grads of a ragged batch (M = B rows; len, samples_per_row as in fwn_coupling_bwd_ragged): the rows past a
+ * clip's end are left out of the five sums and written back as exact 0 in all four planes (the flow before this one saw 0
+ * there in the forward pass, not the -shift that ActNorm's inverse gives).  The other rows are summed in fwn_flow_small_grads'
+ * order: with every length = rows samples_per_row the same bits. */
+int fwn_flow_small_grads_ragged(float* ga, float* ya, float* gb, float* yb, const float* dzz, const float* an, int64_t B,
+                                int64_t rows, int Ch, const int32_t* len, int32_t samples_per_row, const int64_t* br,
+                                const int64_t* zc, double* partial, float* db, float* dlogs, float* dzscale, void* stream);
 
 /* Backward of one up-sampling stage (fwn_upsample_stage with fp32 output): y, dy [B][H*s][W], x [B][H][W].
  * dy <- dy * LeakyReLU'(y) in place; dx (may be NULL) <- gradient wrt x; dwk_bias [6s + 1] <- gradients of
@@ -612,6 +635,26 @@ size_t fwn_train_workspace_bytes(const fwn_train_desc* t, int64_t B, int64_t T);
 int fwn_train_loss_and_grads(const fwn_train_desc* t, int64_t B, int64_t T, const float* x, const float* mel,
                              void* workspace, size_t workspace_bytes, float* out3, fwn_block_done_fn on_block_done,
                              void* user, void* stream);
+/* ---- ragged training step (additive; FWN_VERSION unchanged): clips of len_dev[b] <= T samples each (DEVICE int32 [B], every
+ * length a multiple of hop and of 2^n_block, validated by the caller; only kernels read it, so the call stays asynchronous and
+ * graph-capturable).  loss = -(1/B) sum_b (log_p[b] + logdet[b]) with the per-clip scalars of fwn_model_forward_ragged, and
+ * every gradient is the mean over b of clip b's own gradient (every length = T: the gradients of fwn_train_loss_and_grads bit
+ * for bit).  out3 = (loss, mean log_p, mean logdet); out2B (may be NULL) [2][B] as in fwn_model_forward_ragged.  Nothing past a
+ * clip's end in x or mel reaches an output bit and neither is written.
+ * The same sequencer as fwn_train_loss_and_grads.  Forward half: fwn_model_forward_ragged's fills - a masked copy of the mel and
+ * masked inner up-sampling stages (the buffers the up-sampling backward reads), -shift in x_a's padding in front of each front
+ * conv, h zeroed behind the front conv and every res conv before it is kept, the planes zeroed after every flow; the per-clip
+ * scalars come from fwn_ragged_logdet_rows over the Z each tail keeps for the backward.  Backward half: the adjoint of those
+ * fills - a forward fill of rows becomes a backward drop of the gradient at those rows: d loss / d z = z / (B len[b]) inside a
+ * clip and 0 past it; fwn_coupling_bwd_ragged; the dilated data-gradient GEMMs store dh with fwn_gemm_desc.row_len;
+ * fwn_flow_small_grads_ragged; fwn_mask_rows on the dx of each inner up-sampling stage.  No launch is added to a flow's chain.
+ * A gate_fp8 descriptor is refused (FWN_ERR_ARG).  Workspace: fwn_train_ragged_workspace_bytes (0 for a bad descriptor).
+ * Speed (tools/bench_train.py --ragged, 8 x 6400 samples, one MI355X: profiles/ragged_training.json): 14.6 ms against the plain
+ * step's 12.8; not measured on more than one GPU. */
+size_t fwn_train_ragged_workspace_bytes(const fwn_train_desc* t, int64_t B, int64_t T);
+int fwn_train_loss_and_grads_ragged(const fwn_train_desc* t, int64_t B, int64_t T, const float* x, const float* mel,
+                                    const int32_t* len_dev, void* workspace, size_t workspace_bytes, float* out3, float* out2B,
+                                    fwn_block_done_fn on_block_done, void* user, void* stream);
 
 #ifdef __cplusplus
 }

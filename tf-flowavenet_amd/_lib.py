@@ -131,7 +131,8 @@ class GemmDesc(C.Structure):
                 ("accumulate", C.c_int32), ("nsplit", C.c_int32),
                 ("split_stride", C.c_int64),
                 ("oscale", C.c_float), ("gate_col0", C.c_int32),
-                ("gate_aux", C.c_void_p), ("gate_out", C.c_void_p)]
+                ("gate_aux", C.c_void_p), ("gate_out", C.c_void_p),
+                ("row_len", C.c_void_p), ("len_spr", C.c_int32), ("pad1_", C.c_int32)]
 
 
 SIGNATURES = {
@@ -204,6 +205,8 @@ SIGNATURES = {
     "fwn_actnorm_apply2": (C.c_int, [vp, vp, vp, i64, C.c_int, vp]),
     "fwn_coupling_fwd": (C.c_int, [vp, vp, vp, i64, C.c_int, vp, C.c_int, vp]),
     "fwn_coupling_bwd": (C.c_int, [vp, vp, vp, vp, i64, C.c_int, C.c_float, vp, C.c_int, vp, vp]),
+    "fwn_coupling_bwd_ragged": (C.c_int, [vp, vp, vp, vp, i64, i64, C.c_int, vp, i32, vp, C.c_int, vp, vp, vp, C.c_int, vp]),
+    "fwn_flow_small_grads_ragged": (C.c_int, [vp, vp, vp, vp, vp, vp, i64, i64, C.c_int, vp, i32, vp, vp, vp, vp, vp, vp, vp]),
     "fwn_gate_bwd": (C.c_int, [vp, C.c_int, vp, i64, vp, vp]),
     "fwn_colsum_partials": (C.c_int, [i64, C.c_int]),
     "fwn_colsum_prod": (C.c_int, [vp, vp, i64, C.c_int, C.c_float, vp, vp, vp]),
@@ -229,6 +232,8 @@ SIGNATURES = {
     "fwn_model_forward_init": (C.c_int, [C.POINTER(ModelDesc), i64, i64, vp, vp, vp, C.c_size_t, vp, vp, vp, vp, vp]),
     "fwn_train_workspace_bytes": (C.c_size_t, [C.POINTER(TrainDesc), i64, i64]),
     "fwn_train_loss_and_grads": (C.c_int, [C.POINTER(TrainDesc), i64, i64, vp, vp, vp, C.c_size_t, vp, BLOCK_DONE_FN, vp, vp]),
+    "fwn_train_ragged_workspace_bytes": (C.c_size_t, [C.POINTER(TrainDesc), i64, i64]),
+    "fwn_train_loss_and_grads_ragged": (C.c_int, [C.POINTER(TrainDesc), i64, i64, vp, vp, vp, vp, C.c_size_t, vp, vp, BLOCK_DONE_FN, vp, vp]),
     "fwn_model_reverse": (C.c_int, [C.POINTER(ModelDesc), i64, i64, vp, vp, vp, C.c_size_t, vp, vp]),
     "fwn_model_persist_status": (C.c_int, [C.POINTER(ModelDesc), i64, i64, vp, vp]),
     "fwn_mask_rows": (C.c_int, [vp, i64, i64, i64, vp, i32, vp]),

@@ -666,6 +666,9 @@ int fwn_gemm(const fwn_gemm_desc* g, void* stream) {
     REQUIRE(!g->gate_aux || (g->gate_out && !g->out_f32 && g->gate_col0 >= 0 && g->gate_col0 % 256 == 0 && g->gate_col0 + 256 <= g->N &&
                              (int64_t)g->M * 512 * 2 < ((int64_t)1 << 31)),
             "fwn_gemm: gate_aux needs gate_out, a bf16 output and 256 columns from gate_col0 (a multiple of 256) inside N");
+    REQUIRE(!g->row_len || (g->Ti > 0 && g->M % g->Ti == 0 && g->len_spr > 0 && g->nsplit == 1),
+            "fwn_gemm: row_len needs clips (Ti > 0, M a multiple of Ti), len_spr > 0 and no split-K");
+    REQUIRE(!g->row_len || !g->accumulate, "fwn_gemm: row_len is refused together with accumulate");
     fwn_gemm_launch(g, (hipStream_t)stream);
     return check_launch("fwn_gemm");
 }
@@ -705,6 +708,15 @@ int fwn_coupling_bwd(float* g, float* out_b, const float* Z, const float* ez, in
     fwn_ew_coupling_bwd(g, out_b, Z, ez, (long)M * Ch, Ch, cls, dZ, ldz, dzz, (hipStream_t)stream);
     return check_launch("fwn_coupling_bwd");
 }
+int fwn_coupling_bwd_ragged(float* g, float* out_b, const float* Z, const float* ez, int64_t B, int64_t rows, int Ch, const int32_t* len,
+                            int32_t samples_per_row, void* dZ, int ldz, float* dzz, const float* ya, void* ya_bf, int ldya, void* stream) {
+    REQUIRE(g && out_b && Z && ez && dZ && dzz && len && B > 0 && rows > 0 && Ch >= 1 && ldz >= 2 * Ch && samples_per_row > 0,
+            "fwn_coupling_bwd_ragged: bad argument");
+    REQUIRE((ya != nullptr) == (ya_bf != nullptr) && (!ya_bf || ldya >= Ch), "fwn_coupling_bwd_ragged: ya and ya_bf go together, ldya >= Ch");
+    REQUIRE(rows <= ((int64_t)1 << 31) / samples_per_row && B * rows * ldz < ((int64_t)1 << 40), "fwn_coupling_bwd_ragged: shape too large");
+    fwn_ew_coupling_bwd_ragged(g, out_b, Z, ez, (long)B, (long)rows, Ch, len, samples_per_row, dZ, ldz, dzz, ya, ya_bf, ldya, (hipStream_t)stream);
+    return check_launch("fwn_coupling_bwd_ragged");
+}
 int fwn_gate_bwd(const void* d_o, int ld_do, const void* aux, int64_t M, void* dpre, void* stream) {
     REQUIRE(d_o && aux && dpre && M > 0 && ld_do >= 256, "fwn_gate_bwd: bad argument");
     fwn_ew_gate_bwd(d_o, ld_do, aux, (long)M * 256, dpre, (hipStream_t)stream);
@@ -734,6 +746,16 @@ int fwn_flow_small_grads(float* ga, float* ya, float* gb, float* yb, const float
     fwn_small_grads_launch(ga, ya, gb, yb, dzz, an, (long)M, Ch, (const long long*)br, (const long long*)zc, partial, db, dlogs,
                            dzscale, (hipStream_t)stream);
     return check_launch("fwn_flow_small_grads");
+}
+int fwn_flow_small_grads_ragged(float* ga, float* ya, float* gb, float* yb, const float* dzz, const float* an, int64_t B, int64_t rows,
+                                int Ch, const int32_t* len, int32_t samples_per_row, const int64_t* br, const int64_t* zc, double* partial,
+                                float* db, float* dlogs, float* dzscale, void* stream) {
+    REQUIRE(ga && ya && gb && yb && dzz && an && len && br && zc && partial && db && dlogs && dzscale, "fwn_flow_small_grads_ragged: null pointer");
+    REQUIRE(B > 0 && rows > 0 && samples_per_row > 0 && Ch >= 1 && Ch <= 128 && (Ch & (Ch - 1)) == 0,
+            "fwn_flow_small_grads_ragged: Ch must be a power of two <= 128");
+    fwn_small_grads_main_ragged(ga, ya, gb, yb, dzz, an, (long)B, (long)rows, Ch, len, samples_per_row, partial, (hipStream_t)stream);
+    fwn_small_grads_final(an, (long)(B * rows), Ch, (const long long*)br, (const long long*)zc, partial, db, dlogs, dzscale, (hipStream_t)stream);
+    return check_launch("fwn_flow_small_grads_ragged");
 }
 static bool wn_job_ok(const fwn_wn_job& q) {
     return q.part && q.dV && q.K > 0 && q.N > 0 && q.nsplit >= 1 && q.col0 >= 0 && q.ldp >= q.col0 + q.N && (!q.g || (q.V && q.dg));

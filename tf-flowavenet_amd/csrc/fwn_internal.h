@@ -178,6 +178,9 @@ void fwn_ew_coupling_bwd(float* g, float* ob, const float* Z, const float* ez, l
                          int ldz, float* dzz, hipStream_t st);
 void fwn_ew_coupling_bwd_ex(float* g, float* ob, const float* Z, const float* ez, long n, int Ch, float cls, void* dZ,
                             int ldz, float* dzz, const float* ya, void* ya_bf, int ldya, hipStream_t st);
+// ragged batch (nclip clips of `rows` rows, clip b keeps len[b] / spr): per-clip log-det term, zeros past a clip's end
+void fwn_ew_coupling_bwd_ragged(float* g, float* ob, const float* Z, const float* ez, long nclip, long rows, int Ch, const int* len,
+                                int spr, void* dZ, int ldz, float* dzz, const float* ya, void* ya_bf, int ldya, hipStream_t st);
 void fwn_ew_gate_bwd(const void* do_, int ld_do, const void* aux, long n, void* dpre, hipStream_t st);
 int fwn_colsum_blocks(long M, int C);
 void fwn_ew_colsum_prod(const float* A, const float* B, long M, int C, float scale, float* partial, float* out,
@@ -186,6 +189,8 @@ void fwn_ew_actnorm_bwd(float* dy, float* y, const float* an, long n, int Ch, hi
 int fwn_small_grads_blocks(long M, int Ch);
 void fwn_small_grads_main(float* ga, float* ya, float* gb, float* yb, const float* dzz, const float* an, long M, int Ch,
                           double* partial, hipStream_t st);
+void fwn_small_grads_main_ragged(float* ga, float* ya, float* gb, float* yb, const float* dzz, const float* an, long nclip, long rows,
+                                 int Ch, const int* len, int spr, double* partial, hipStream_t st);
 void fwn_small_grads_final(const float* an, long M, int Ch, const long long* br, const long long* zc, const double* partial, float* db,
                            float* dlogs, float* dzscale, hipStream_t st);
 void fwn_small_grads_launch(float* ga, float* ya, float* gb, float* yb, const float* dzz, const float* an, long M, int Ch,

@@ -61,6 +61,30 @@ __global__ void finish_loss_kernel(const float* __restrict__ out2, float* __rest
         out3[2] = logdet;
     }
 }
+// ragged step: d loss / d z of clip b = z / (nclip len[b]) inside the clip (log_p[b] is the mean over the clip's own samples,
+// the loss the mean over the clips) and 0 past its end, where the forward pass zeroed the planes.  planes [2][nclip][hT];
+// a clip of len samples holds len / 2 elements of either plane.  With len = 2 hT the bits of scale_copy_kernel.
+__global__ __launch_bounds__(256) void dz_init_ragged_kernel(float* __restrict__ dst, const float* __restrict__ src, long nclip, long hT,
+                                                             const int* __restrict__ len) {
+    const long n = 2 * nclip * hT;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+        const long r = i / hT, b = r % nclip, k = i - r * hT;
+        long L = len[b];
+        L = L < 0 ? 0 : (L > 2 * hT ? 2 * hT : L);
+        dst[i] = k < L / 2 ? (src[i] + 0.0f) * (float)(1.0 / ((double)nclip * (double)L)) : 0.0f;
+    }
+}
+// out2B [2][nclip] = per-clip (log_p, logdet) -> out3 = (loss, mean log_p, mean logdet), loss = -(1/nclip) sum_b (log_p + logdet);
+// fp64 sums in clip order
+__global__ void finish_loss_ragged_kernel(const float* __restrict__ out2B, long nclip, float* __restrict__ out3) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) {
+        double lp = 0.0, ld = 0.0;
+        for (long b = 0; b < nclip; ++b) { lp += (double)out2B[b]; ld += (double)out2B[nclip + b]; }
+        out3[0] = (float)(-(lp + ld) / (double)nclip);
+        out3[1] = (float)(lp / (double)nclip);
+        out3[2] = (float)(ld / (double)nclip);
+    }
+}
 inline unsigned grid_of(long n) { long b = (n + 255) / 256; return (unsigned)(b > 4096 ? 4096 : (b < 1 ? 1 : b)); }
 
 // ---- workspace carving (the same walk sizes the workspace and hands out the pointers) ------------------------------
@@ -157,6 +181,9 @@ struct Plan {               // every buffer of one call
     // gradients run on the side stream while the main stream goes on differentiating
     std::vector<BwdSet> sets;
     float* up_dy; float* up_y; float* up_dx[2]; float* up_dwb; float* up_scr; float* up_g3; float* up_dv; float* up_dg3;
+    // ragged step only (behind everything else: the plain call's layout is untouched): the masked copy of the mel, every
+    // flow's per-clip log-det sums, and the per-clip scalars where the caller wants none
+    float* melc; double* acc; float* out2B;
     size_t total;
     int npart;
 };
@@ -182,7 +209,7 @@ long tn_partial_floats(const fwn_model_desc* md, int i, long m) {
     return tot * md->n_flow;
 }
 
-void plan(const fwn_train_desc* t, long B, long T, void* ws, Plan& pl) {
+void plan(const fwn_train_desc* t, long B, long T, void* ws, Plan& pl, bool ragged = false) {
     const fwn_model_desc* md = t->model;
     const int L = md->n_layer, half = md->num_mels / 2, nmel = 2 * half;
     Bump b(ws);
@@ -290,6 +317,11 @@ void plan(const fwn_train_desc* t, long B, long T, void* ws, Plan& pl) {
     pl.up_g3 = (float*)b.take(16);
     pl.up_dv = (float*)b.take((size_t)2 * smax * 3 * 4);
     pl.up_dg3 = (float*)b.take(16);
+    if (ragged) {
+        pl.melc = (float*)b.take((size_t)B * (T / hop_of(md)) * nmel * 4);
+        pl.acc = (double*)b.take((size_t)md->n_block * md->n_flow * B * fwn_ragged_logdet_nslot(B) * 8);
+        pl.out2B = (float*)b.take((size_t)2 * B * 4);
+    }
     pl.total = b.off;
 }
 
@@ -324,9 +356,7 @@ struct WnItem { int tn; const float* part_direct; int part_nsplit; long part_str
 
 }  // namespace
 
-extern "C" {
-
-size_t fwn_train_workspace_bytes(const fwn_train_desc* t, int64_t B, int64_t T) {
+static size_t train_workspace(const fwn_train_desc* t, int64_t B, int64_t T, bool ragged) {
     if (!t || !t->model || !t->flows || B <= 0 || T <= 0) return 0;
     const fwn_model_desc* md = t->model;
     if (md->n_block < 1 || md->n_block > 16 || md->n_flow < 1 || md->n_layer < 1 || md->n_layer > FWN_MAX_LAYERS) return 0;
@@ -335,12 +365,16 @@ size_t fwn_train_workspace_bytes(const fwn_train_desc* t, int64_t B, int64_t T) 
     FlowSaved saved[256];
     Plan pl{};
     pl.saved = saved;
-    plan(t, (long)B, (long)T, nullptr, pl);
+    plan(t, (long)B, (long)T, nullptr, pl, ragged);
     return pl.total;
 }
 
-int fwn_train_loss_and_grads(const fwn_train_desc* t, int64_t B_, int64_t T_, const float* x, const float* mel, void* workspace,
-                             size_t workspace_bytes, float* out3, fwn_block_done_fn on_block_done, void* user, void* stream) {
+// The one sequencer of both entry points.  len (ragged step): the clips' lengths on the device - the forward half then runs
+// the fills of the ragged forward pass (api.hip flow_run_impl / model_pass with len) and the backward half their adjoint: where
+// the forward overwrote rows with a constant, the gradient arriving at those rows is dropped.  out2B: per-clip scalars (NULL: kept
+// in the workspace).
+static int train_impl(const fwn_train_desc* t, int64_t B_, int64_t T_, const float* x, const float* mel, const int32_t* len, void* workspace,
+                      size_t workspace_bytes, float* out3, float* out2B, fwn_block_done_fn on_block_done, void* user, void* stream) {
     TREQUIRE(t && t->model && t->flows && t->model->flows, "fwn_train_loss_and_grads: null descriptor");
     TREQUIRE(x && mel && workspace && out3, "fwn_train_loss_and_grads: null pointer");
     TREQUIRE((((uintptr_t)workspace) & 255) == 0, "fwn_train_loss_and_grads: workspace must be 256-byte aligned");
@@ -356,24 +390,44 @@ int fwn_train_loss_and_grads(const fwn_train_desc* t, int64_t B_, int64_t T_, co
     FlowSaved saved[256];
     Plan pl{};
     pl.saved = saved;
-    plan(t, B, T, workspace, pl);
+    TREQUIRE(!len || !md->gate_fp8, "fwn_train_loss_and_grads_ragged: per-clip lengths go with a model without fp8 gates (its e4m3 copies of h are not masked)");
+    TREQUIRE(!len || B < 32768, "fwn_train_loss_and_grads_ragged: B=%ld clips (at most 32767 per call)", B);
+    plan(t, B, T, workspace, pl, len != nullptr);
     if (workspace_bytes < pl.total) return fwn_set_error(FWN_ERR_WORKSPACE, "workspace %zu < required %zu bytes", workspace_bytes, pl.total);
     hipStream_t st = (hipStream_t)stream;
 
     // ---------------- forward, keeping what the backward needs ----------------
+    // ragged: rows [len / samples per row, rows) of every clip of a [B][rows][row_bytes] buffer are zeroed
+    auto mask = [&](void* base, long nclip, long rows, long row_bytes, int spr) {
+        if (len) fwn_launch_mask_rows(base, nclip, rows, row_bytes, len, (int)B, spr, st);
+    };
     {
         long H = T / hop_of(md);
+        int spr = hop_of(md);                // samples per row of the current stage's input
         const float* in = mel;
+        if (len) {      // the stages run on a copy of the mel with the frames past each clip's end zeroed, and so is every inner
+                        // stage's output (api.hip run_upsample); the up-sampling backward reads these very buffers
+            if (hipMemcpyAsync(pl.melc, mel, (size_t)B * H * nmel * 4, hipMemcpyDeviceToDevice, st) != hipSuccess)
+                return fwn_set_error(FWN_ERR_HIP, "fwn_train_loss_and_grads_ragged: mel copy failed");
+            mask(pl.melc, B, H, (long)nmel * 4, spr);
+            in = pl.melc;
+        }
         for (int n = 0; n < md->n_up; ++n) {
             const bool last = n == md->n_up - 1;
             TREQUIRE(t->up_bias_dev[n], "fwn_train_loss_and_grads: up_bias_dev[%d] is null", n);
             fwn_launch_upsample(in, (int)B, (int)H, nmel, md->up_w[n], 0.0f, t->up_bias_dev[n], md->up_scale[n], last ? nullptr : pl.ups[n],
                                 last ? pl.cplanes : nullptr, st);
             H *= md->up_scale[n];
+            spr /= md->up_scale[n];
+            if (!last) mask(pl.ups[n], B, H, (long)nmel * 4, spr);
             in = pl.ups[n];
         }
     }
     fwn_launch_split(x, B, T, pl.planes, st);
+    // ragged: both planes hold clip b's samples at [b][0, len / 2) at every block; the rest is zeroed here and behind every flow
+    auto mask_planes = [&]() { mask(pl.planes, 2 * B, T / 2, 4, 2); };
+    mask_planes();
+    const int nslot = len ? fwn_ragged_logdet_nslot(B) : 0;
     const size_t plane_elems = (size_t)B * T / 2, cplane_elems = (size_t)B * T * half;
     int p = 0;
     for (int i = 0; i < md->n_block; ++i) {
@@ -395,12 +449,19 @@ int fwn_train_loss_and_grads(const fwn_train_desc* t, int64_t B_, int64_t T_, co
             // the inference kernels, keeping what the backward needs: the front conv applies the flow's ActNorm on the fly, the
             // tail (skip sum -> final conv -> ZeroConv -> coupling + ActNorm of both planes, csrc/tail_chain.h) leaves
             // y_a / out_b in the planes - the state the backward starts from - and writes S, U and Z on its way
+            // ragged: -shift in x_a's rows past a clip's end, so that the front conv's on-the-fly ActNorm reads exact zeros there;
+            // h zeroed in those rows behind every kernel that writes it, BEFORE it is kept (the weight gradients read it)
+            if (len) fwn_launch_fill_neg_shift(xa, B, ti, ch, d->an, len, (int)B, 2 * ch, st);
             fwn_launch_front(xa, d->an, d->Wfront, d->Wfront2, d->bfront, s.h[0], ch >= 32 ? pl.xhl : nullptr, (int)m, (int)ti, ch, d->kfpad, 1, nullptr, st);
+            mask(s.h[0], B, ti, 512, 2 * ch);
             for (int l = 0; l < L; ++l) {
                 const float* Pl = hoist ? pl.P + ((size_t)j * L + l) * m * 512 : nullptr;
                 fwn_launch_gate(s.h[l], hoist ? nullptr : ca, Pl, d->Wd[l], d->Wc[l], nullptr, d->bgate[l], s.o[l], (int)m, (int)ti, dilation_of(l), d->cin,
                                 d->kcpad, s.aux[l], st);
-                if (l + 1 < L) fwn_launch_res(s.o[l], s.h[l], d->Wres[l], d->bres[l], s.h[l + 1], (int)m, nullptr, st);
+                if (l + 1 < L) {
+                    fwn_launch_res(s.o[l], s.h[l], d->Wres[l], d->bres[l], s.h[l + 1], (int)m, nullptr, st);
+                    mask(s.h[l + 1], B, ti, 512, 2 * ch);
+                }
             }
             {
                 const long o_stride = L > 1 ? (long)(((const char*)s.o[1] - (const char*)s.o[0]) / 2) : 0;
@@ -414,11 +475,21 @@ int fwn_train_loss_and_grads(const fwn_train_desc* t, int64_t B_, int64_t T_, co
                 fwn_launch_tail(s.o[0], o_stride, L, d->Wskip, d->bskip, d->Wfinal, d->bfinal, d->Wzero, d->bzero, d->ezero, d->an, xa, xb, s.part,
                                 (int)m, ch, d->npt, 0, nullptr, nullptr, &tc, d->Wts, st);
             }
+            if (len) {      // per-clip log-det sums from the Z the tail keeps for the backward (its own whole-batch partials are ignored)
+                fwn_launch_ragged_logdet(s.z, B, ti, ch, d->ezero, d->an, len, (int)B, 2 * ch, pl.acc + (size_t)(i * NF + j) * B * nslot, st);
+                mask_planes();
+            }
             p ^= 1;
         }
     }
-    fwn_launch_prior(pl.planes, B * T, pl.partial_all, pl.npart, 1.0 / (double)(B * T), pl.out2, st);
-    hipLaunchKernelGGL(finish_loss_kernel, dim3(1), dim3(64), 0, st, pl.out2, out3);
+    if (len) {
+        float* o2 = out2B ? out2B : pl.out2B;
+        fwn_launch_ragged_finish(pl.planes, B, T, pl.acc, md->n_block * NF, NF, len, o2, st);
+        hipLaunchKernelGGL(finish_loss_ragged_kernel, dim3(1), dim3(64), 0, st, (const float*)o2, B, out3);
+    } else {
+        fwn_launch_prior(pl.planes, B * T, pl.partial_all, pl.npart, 1.0 / (double)(B * T), pl.out2, st);
+        hipLaunchKernelGGL(finish_loss_kernel, dim3(1), dim3(64), 0, st, pl.out2, out3);
+    }
 
     // ---------------- backward ----------------
     // The data gradients of a flow are one dependent chain of small launches; its weight gradients (grouped TN GEMM,
@@ -583,7 +654,8 @@ int fwn_train_loss_and_grads(const fwn_train_desc* t, int64_t B_, int64_t T_, co
         return FWN_OK;
     };
     // d loss / d z = z / (B T)   (log_p = mean 0.5 (-log 2 pi - z^2))
-    hipLaunchKernelGGL(scale_copy_kernel, dim3(grid_of(B * T)), dim3(256), 0, st, pl.gplanes, pl.planes, B * T, (float)(1.0 / (double)(B * T)));
+    if (len) hipLaunchKernelGGL(dz_init_ragged_kernel, dim3(grid_of(B * T)), dim3(256), 0, st, pl.gplanes, (const float*)pl.planes, B, T / 2, len);
+    else hipLaunchKernelGGL(scale_copy_kernel, dim3(grid_of(B * T)), dim3(256), 0, st, pl.gplanes, pl.planes, B * T, (float)(1.0 / (double)(B * T)));
     if (hipMemsetAsync(pl.dcplanes, 0, (size_t)2 * B * T * half * 4, st) != hipSuccess) return fwn_set_error(FWN_ERR_HIP, "hipMemsetAsync failed");
     for (int i = md->n_block - 1; i >= 0; --i) {
         const int ch = 1 << i;
@@ -604,7 +676,8 @@ int fwn_train_loss_and_grads(const fwn_train_desc* t, int64_t B_, int64_t T_, co
             float* dca = pl.dcplanes + (size_t)pp * cplane_elems;
             // coupling
             // (also: the bf16 copy of y_a for the front conv's weight gradient, and the zero padding of dZ's rows)
-            fwn_ew_coupling_bwd_ex(gb, xb, s.z, td->ez, m * ch, ch, (float)(1.0 / (2.0 * (double)m * ch)), w.dz, ldz, pl.dzz, xa, w.ya_bf, ch < 8 ? 8 : ch, st);
+            if (len) fwn_ew_coupling_bwd_ragged(gb, xb, s.z, td->ez, B, ti, ch, len, 2 * ch, w.dz, ldz, pl.dzz, xa, w.ya_bf, ch < 8 ? 8 : ch, st);
+            else fwn_ew_coupling_bwd_ex(gb, xb, s.z, td->ez, m * ch, ch, (float)(1.0 / (2.0 * (double)m * ch)), w.dz, ldz, pl.dzz, xa, w.ya_bf, ch < 8 ? 8 : ch, st);
             {
                 Seg a{w.dz, m, ldz, ldz, 0, 0};
                 fwn_gemm_desc g = gemm_desc(&a, 1, td->WzT, ldz, 256, m, 0, w.du, 256, false);
@@ -671,6 +744,8 @@ int fwn_train_loss_and_grads(const fwn_train_desc* t, int64_t B_, int64_t T_, co
                     fwn_gemm_desc g = gemm_desc(sg, 3, td->WdT[l], 1536, 256, m, (int)ti, w.dh[l], 256, false);
                     if (dh_next) { g.R = dh_next; g.ldr = 256; g.rscale = SQH; }
                     if (l == 0) { g.mask = s.h[0]; g.ldmask = 256; }
+                    // ragged: the forward zeroed h_l past each clip's end, so dh_l is stored as 0 there (in this launch's epilogue)
+                    if (len) { g.row_len = len; g.len_spr = 2 * ch; }
                     fwn_gemm_launch(&g, st);
                 }
                 dh_next = w.dh[l];
@@ -705,7 +780,8 @@ int fwn_train_loss_and_grads(const fwn_train_desc* t, int64_t B_, int64_t T_, co
             }
             // ActNorm of both planes back to the flow's inputs, with its b / logs gradients and the ZeroConv scale gradient
             TREQUIRE(td->d_an_b && td->d_an_logs && td->d_zscale, "fwn_train_loss_and_grads: flow (%d,%d): missing small gradient pointers", i, j);
-            fwn_small_grads_main(ga, xa, gb, xb, pl.dzz, d->an, m, ch, w.sg, st);
+            if (len) fwn_small_grads_main_ragged(ga, xa, gb, xb, pl.dzz, d->an, B, ti, ch, len, 2 * ch, w.sg, st);
+            else fwn_small_grads_main(ga, xa, gb, xb, pl.dzz, d->an, m, ch, w.sg, st);
             if (!side) fwn_small_grads_final(d->an, m, ch, (const long long*)t->br[i], (const long long*)t->zcol[i], w.sg, td->d_an_b, td->d_an_logs,
                                              td->d_zscale, st);
             if (!side && j == 0 && on_block_done && on_block_done(user, i) != 0) hook_failed = true;
@@ -738,11 +814,14 @@ int fwn_train_loss_and_grads(const fwn_train_desc* t, int64_t B_, int64_t T_, co
             const int s_ = md->up_scale[n];
             long hh = T / hop_of(md);
             for (int k = 0; k < n; ++k) hh *= md->up_scale[k];                 // rows of the stage's input
-            const float* xin = n == 0 ? mel : pl.ups[n - 1];
+            const float* xin = n == 0 ? (len ? pl.melc : mel) : pl.ups[n - 1];      // ragged: the masked buffers of the forward half
             float* dx = n > 0 ? pl.up_dx[n & 1] : nullptr;
             const fwn_conv_grad& c = t->up[n];
             TREQUIRE(c.V && c.g && c.dV && c.dg && c.db, "fwn_train_loss_and_grads: up-sampling stage %d: missing pointer", n);
             fwn_up_bwd_launch(dy, y, xin, (int)B, (int)hh, nmel, s_, md->up_w[n], dx, pl.up_dwb, pl.up_scr, st);
+            // ragged: the forward zeroed this stage's input past each clip's end - its gradient is dropped there before the
+            // stage below reads it
+            if (dx) mask(dx, B, hh, (long)nmel * 4, (int)(T / hh));
             hipLaunchKernelGGL(up_prepare_kernel, dim3(1), dim3(64), 0, st, c.g, pl.up_g3);
             fwn_wn_job q;
             memset(&q, 0, sizeof(q));
@@ -761,6 +840,24 @@ int fwn_train_loss_and_grads(const fwn_train_desc* t, int64_t B_, int64_t T_, co
     if (e != hipSuccess) return fwn_set_error(FWN_ERR_HIP, "fwn_train_loss_and_grads: %s", hipGetErrorString(e));
     side_guard.armed = false;             // every block was joined on the way (join_pending)
     return FWN_OK;
+}
+
+extern "C" {
+
+size_t fwn_train_workspace_bytes(const fwn_train_desc* t, int64_t B, int64_t T) { return train_workspace(t, B, T, false); }
+size_t fwn_train_ragged_workspace_bytes(const fwn_train_desc* t, int64_t B, int64_t T) {
+    if (B >= 32768 || (t && t->model && t->model->gate_fp8)) return 0;
+    return train_workspace(t, B, T, true);
+}
+int fwn_train_loss_and_grads(const fwn_train_desc* t, int64_t B, int64_t T, const float* x, const float* mel, void* workspace,
+                             size_t workspace_bytes, float* out3, fwn_block_done_fn on_block_done, void* user, void* stream) {
+    return train_impl(t, B, T, x, mel, nullptr, workspace, workspace_bytes, out3, nullptr, on_block_done, user, stream);
+}
+int fwn_train_loss_and_grads_ragged(const fwn_train_desc* t, int64_t B, int64_t T, const float* x, const float* mel, const int32_t* len_dev,
+                                    void* workspace, size_t workspace_bytes, float* out3, float* out2B, fwn_block_done_fn on_block_done,
+                                    void* user, void* stream) {
+    TREQUIRE(len_dev, "fwn_train_loss_and_grads_ragged: null lengths");
+    return train_impl(t, B, T, x, mel, len_dev, workspace, workspace_bytes, out3, out2B, on_block_done, user, stream);
 }
 
 }  // extern "C"

@@ -8,6 +8,9 @@
 #include "fwn_internal.h"
 #include "../../include/fwn.h"
 
+// RL: the launch carries per-clip lengths (fwn_gemm_desc.row_len).  A separate instantiation, so that the kernels of a launch
+// without lengths are the code they were before the field existed.
+template <bool RL>
 struct LinProb {
     static constexpr bool A_DMA = true;
     static constexpr bool ALLOW_256 = false;
@@ -44,6 +47,12 @@ struct LinProb {
         return (n < g.N && kk < cc.k) ? (uint32_t)(n * g.ldw + cc.koff + kk) * 2u : FWN_OOB;
     }
     __device__ float acc_init(int) const { return 0.0f; }
+    // ragged batches (g.row_len): row (< M) lies past the end of its clip of Ti rows - its output is stored as exact 0.
+    // Epilogue only: the K loop never sees the lengths.
+    __device__ bool row_padded(int row) const {
+        const int b = row / g.Ti, t = row - b * g.Ti;
+        return t >= g.row_len[b] / g.len_spr;
+    }
     // ---- row-major epilogue (gemm_ring.h LDS_EPI): 8 consecutive columns of one row per lane, 16-byte loads / stores ----
     // With one column per lane the direct epilogue below issues up to 64 two- / four-byte VMEM instructions per lane and
     // operand (absent operands included: their zero-sized descriptors still cost the issue); the training GEMMs with 256-row
@@ -98,6 +107,14 @@ struct LinProb {
             ok[it] = cok && row < g.M;
             rowc[it] = row < g.M ? row : 0;
         }
+        bool pad[NIT];
+        if constexpr (RL) {
+#pragma unroll
+            for (int it = 0; it < NIT; ++it) pad[it] = row_padded(rowc[it]);
+        } else {
+#pragma unroll
+            for (int it = 0; it < NIT; ++it) pad[it] = false;
+        }
         // one uniform branch per operand, not one per load: the loads inside issue back to back
         if (g.R) {
 #pragma unroll
@@ -151,6 +168,7 @@ struct LinProb {
                 v = ((float)mv[it].e[e] + mdef) > 0.0f ? v : 0.0f;
                 v = relu_on ? fmaxf(v, 0.0f) : v;
                 out[e] = v * g.oscale + yv[e];
+                if constexpr (RL) out[e] = pad[it] ? 0.0f : out[e];
             }
             const int row = mrow0 + it * 8 + (lane >> 3);
             if (!GATED && g.out_f32) {
@@ -217,6 +235,14 @@ struct LinProb {
 #pragma unroll
             for (int mi = 0; mi < MI; ++mi) {
                 float rv[16], mv[16], yv[16], out[16];
+                unsigned padm = 0u;                     // bit r: row r of this lane lies past its clip's end (g.row_len)
+                if constexpr (RL) {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int row = rbase + mi * 32 + acc_row_c(r);
+                        if (row < g.M && row_padded(row)) padm |= 1u << r;
+                    }
+                }
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int ro = mi * 32 + acc_row_c(r);
@@ -230,6 +256,7 @@ struct LinProb {
                     v = (mv[r] + mdef) > 0.0f ? v : 0.0f;
                     v = relu_on ? fmaxf(v, 0.0f) : v;       // off: v untouched, so a NaN stays a NaN (fmaxf(NaN, -inf) would be -inf)
                     out[r] = v * g.oscale + yv[r];
+                    if constexpr (RL) out[r] = ((padm >> r) & 1u) ? 0.0f : out[r];
                 }
                 if (g.out_f32) {
 #pragma unroll
@@ -260,14 +287,14 @@ struct LinProb {
     }
 };
 
-template <int BM, int BN, int WM, int WN, int D, int KSP = 1, int BK = 64>
+template <bool RL, int BM, int BN, int WM, int WN, int D, int KSP = 1, int BK = 64>
 __global__ __launch_bounds__(64 * WM * WN * KSP) void lin_kernel(const fwn_gemm_desc g, int ntn, int nq_all) {
     const int per = (nq_all + g.nsplit - 1) / g.nsplit;
     const int q0 = (int)blockIdx.z * per;
     const int nq = max(0, min(per, nq_all - q0));      // an empty split still writes its zero partial
-    const LinProb p{g, q0, nq, (float*)g.Y + (size_t)blockIdx.z * g.split_stride};
+    const LinProb<RL> p{g, q0, nq, (float*)g.Y + (size_t)blockIdx.z * g.split_stride};
     const int wg = xcd_remap(blockIdx.x, gridDim.x);
-    gemm_ring_body<BM, BN, WM, WN, BK, D, LinProb, KSP>(p, wg / ntn, wg % ntn);
+    gemm_ring_body<BM, BN, WM, WN, BK, D, LinProb<RL>, KSP>(p, wg / ntn, wg % ntn);
 }
 
 int fwn_gemm_launch(const fwn_gemm_desc* g, hipStream_t st) {
@@ -282,11 +309,17 @@ int fwn_gemm_launch(const fwn_gemm_desc* g, hipStream_t st) {
     // conditioning-gradient GEMMs of the late blocks: N = cin up to 10240 against a few hundred rows).
     const int w256 = ((M + 255) / 256) * n128 * ns, w128 = ((M + 127) / 128) * n128 * ns, w64 = ((M + 63) / 64) * n128 * ns;
     const int c256 = ((w256 + 255) / 256) * 384, c128 = ((w128 + 255) / 256) * 256, c64 = ((w64 + 255) / 256) * 192;
-    if (c256 <= c128 && c256 <= c64)
-        hipLaunchKernelGGL((lin_kernel<256, 128, 8, 2, 3>), dim3(((M + 255) / 256) * n128, 1, ns), dim3(1024), 0, st, p, n128, nq_all);
-    else if (c128 <= c64)
-        hipLaunchKernelGGL((lin_kernel<128, 128, 4, 2, 3>), dim3(((M + 127) / 128) * n128, 1, ns), dim3(512), 0, st, p, n128, nq_all);
-    else {   // small M: 128-wide K chunks (256-byte LDS rows) - a third less time per unit of K on these latency chains
+    // with lengths (g->row_len) the same tile from the instantiation whose epilogue reads them
+#define FWN_LIN_LAUNCH(grid, block, ntn_, nq_, ...)                                                                  \
+    do {                                                                                                             \
+        if (g->row_len) hipLaunchKernelGGL((lin_kernel<true, __VA_ARGS__>), grid, dim3(block), 0, st, p, ntn_, nq_); \
+        else hipLaunchKernelGGL((lin_kernel<false, __VA_ARGS__>), grid, dim3(block), 0, st, p, ntn_, nq_);           \
+    } while (0)
+    if (c256 <= c128 && c256 <= c64) {
+        FWN_LIN_LAUNCH(dim3(((M + 255) / 256) * n128, 1, ns), 1024, n128, nq_all, 256, 128, 8, 2, 3);
+    } else if (c128 <= c64) {
+        FWN_LIN_LAUNCH(dim3(((M + 127) / 128) * n128, 1, ns), 512, n128, nq_all, 128, 128, 4, 2, 3);
+    } else {   // small M: 128-wide K chunks (256-byte LDS rows) - a third less time per unit of K on these latency chains
         int nq128 = 0;
         for (int s = 0; s < g->nseg; ++s) nq128 += (g->seg[s].k + 127) / 128;
         // A workgroup streams (BM + BN) K 2 bytes through ONE CU at ~50 GB/s: a launch of a few dozen 64 x 128 tiles is
@@ -295,10 +328,12 @@ int fwn_gemm_launch(const fwn_gemm_desc* g, hipStream_t st) {
         constexpr int FWN_LIN_TINY = 40;
         if (((M + 63) / 64) * n128 * ns < FWN_LIN_TINY) {
             const int n64 = (g->N + 63) / 64;
-            hipLaunchKernelGGL((lin_kernel<32, 64, 1, 1, 6, 4, 128>), dim3(((M + 31) / 32) * n64, 1, ns), dim3(256), 0, st, p, n64, nq128);
-        } else
-            hipLaunchKernelGGL((lin_kernel<64, 128, 2, 2, 3, 1, 128>), dim3(((M + 63) / 64) * n128, 1, ns), dim3(256), 0, st, p, n128, nq128);
+            FWN_LIN_LAUNCH(dim3(((M + 31) / 32) * n64, 1, ns), 256, n64, nq128, 32, 64, 1, 1, 6, 4, 128);
+        } else {
+            FWN_LIN_LAUNCH(dim3(((M + 63) / 64) * n128, 1, ns), 256, n128, nq128, 64, 128, 2, 2, 3, 1, 128);
+        }
     }
+#undef FWN_LIN_LAUNCH
     return 0;
 }
 
@@ -406,22 +441,44 @@ __global__ __launch_bounds__(256) void coupling_fwd_kernel(float* __restrict__ y
 // coupling backward.  In: g = dL/d out_b (fp32, becomes dL/d y_b in place), ob = out_b (becomes y_b in
 // place), Z.  Out: dZ bf16 [M][ldz] = gradient wrt Z (already times ez), dzz fp32 [M][2Ch] = d(log_s|t) * (log_s|t)
 // (ZeroConv scale gradient = 3 * column sums).  cls = d(-logdet)/dlog_s = +1 / (2 M Ch)   (model.py:135: mean(-log_s)/2).
+// RG (ragged batch: clips of `rows` rows, clip b keeps its first len[b] / spr): cls is per clip, 1 / (nclip len[b]); the rows
+// past a clip's end leave as exact zeros in g, ob, dZ, dzz and ya_bf - the forward pass overwrote out_b (and y_a) with 0
+// there, so the gradient that arrives at those rows is dropped.
+template <bool RG>
 __global__ __launch_bounds__(256) void coupling_bwd_kernel(float* __restrict__ g, float* __restrict__ ob,
                                                            const float* __restrict__ Z, const float* __restrict__ ez,
                                                            long n, int Ch, float cls, bf16* __restrict__ dZ, int ldz,
                                                            float* __restrict__ dzz, const float* __restrict__ ya,
-                                                           bf16* __restrict__ ya_bf, int ldya) {
+                                                           bf16* __restrict__ ya_bf, int ldya, const int* __restrict__ len,
+                                                           long rows, int spr, double nclip) {
     // ya / ya_bf (optional): also the bf16 copy of the other plane that the front conv's weight gradient reads, and the
     // zero padding of dZ's rows (ldz > 2 Ch) - two launches less per flow
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
         const long m = i / Ch;
         const int c = (int)(i - m * Ch);
+        bool padded = false;
+        if constexpr (RG) {
+            const long b = m / rows;
+            long L = len[b];
+            L = L < 0 ? 0 : (L > rows * spr ? rows * spr : L);
+            padded = m - b * rows >= L / spr;
+            cls = (float)(1.0 / (nclip * (double)L));          // (unused where padded: L = 0 gives inf, never stored)
+        }
         if (ya_bf) {        // rows of ldya >= Ch channels, zero padded (16-byte rows for the TN GEMM)
-            ya_bf[m * ldya + c] = (bf16)ya[i];
+            ya_bf[m * ldya + c] = padded ? (bf16)0.0f : (bf16)ya[i];
             if (c == 0) {
                 for (int k = Ch; k < ldya; ++k) ya_bf[m * ldya + k] = (bf16)0.0f;
                 for (int k = 2 * Ch; k < ldz; ++k) dZ[m * ldz + k] = (bf16)0.0f;
             }
+        }
+        if (padded) {
+            g[i] = 0.0f;
+            ob[i] = 0.0f;
+            dZ[m * ldz + c] = (bf16)0.0f;
+            dZ[m * ldz + Ch + c] = (bf16)0.0f;
+            dzz[m * 2 * Ch + c] = 0.0f;
+            dzz[m * 2 * Ch + Ch + c] = 0.0f;
+            continue;
         }
         const float ls = Z[m * 2 * Ch + c] * ez[c], t = Z[m * 2 * Ch + Ch + c] * ez[Ch + c];
         const float e = __expf(-ls), gb = g[i], o = ob[i];
@@ -487,10 +544,15 @@ __global__ __launch_bounds__(256) void actnorm_bwd_kernel(float* __restrict__ dy
 // scale).  Pass 1: a workgroup owns a contiguous row range; 256 is a multiple of Ch and 2 Ch, so a thread stays on
 // one column; fp64 sums, fixed order.  Pass 2 totals the row ranges and scatters into the parameters' order:
 // db[role Ch + br[c]] = s1 scale[c], dlogs[role Ch + br[c]] = 3 s2 - 3 / (2 Ch), dzscale[zc[j]] = 3 z[j].
+// RG (ragged batch: clips of `rows` rows, clip b keeps its first len[b] / spr): the rows past a clip's end are left out of the
+// five sums and written back as 0 in all four planes - y_a / y_b would otherwise hold -shift there, where the flow before this
+// one saw 0 in the forward pass.  The other rows are added in the same order.
+template <bool RG>
 __global__ __launch_bounds__(256) void flow_small_grads_kernel(float* __restrict__ ga, float* __restrict__ ya,
                                                                float* __restrict__ gb, float* __restrict__ yb,
                                                                const float* __restrict__ dzz, const float* __restrict__ an,
-                                                               long M, int Ch, double* __restrict__ partial) {
+                                                               long M, int Ch, double* __restrict__ partial,
+                                                               const int* __restrict__ len, long rows, int spr) {
     __shared__ double red[5][256];
     const int t = threadIdx.x;
     const long per = (M + gridDim.x - 1) / gridDim.x;
@@ -499,14 +561,31 @@ __global__ __launch_bounds__(256) void flow_small_grads_kernel(float* __restrict
     const float sh_a = an[c], sc_a = an[Ch + c], is_a = an[2 * Ch + c];
     const float sh_b = an[4 * Ch + c], sc_b = an[5 * Ch + c], is_b = an[6 * Ch + c];
     double s1a = 0.0, s2a = 0.0, s1b = 0.0, s2b = 0.0, sz = 0.0;
+    auto padded = [&](long m) {
+        const long b = m / rows;
+        long L = len[b];
+        L = L < 0 ? 0 : L;
+        return m - b * rows >= L / spr;
+    };
     for (long i = r0 * Ch + t; i < r1 * Ch; i += 256) {
+        if constexpr (RG) {
+            if (padded(i / Ch)) {
+                ga[i] = 0.0f; ya[i] = 0.0f; gb[i] = 0.0f; yb[i] = 0.0f;
+                continue;
+            }
+        }
         const float g0 = ga[i], y0 = ya[i], g1 = gb[i], y1 = yb[i];
         s1a += g0; s2a += (double)g0 * y0;
         s1b += g1; s2b += (double)g1 * y1;
         ga[i] = g0 * sc_a; ya[i] = y0 * is_a - sh_a;
         gb[i] = g1 * sc_b; yb[i] = y1 * is_b - sh_b;
     }
-    for (long i = r0 * 2 * Ch + t; i < r1 * 2 * Ch; i += 256) sz += dzz[i];
+    for (long i = r0 * 2 * Ch + t; i < r1 * 2 * Ch; i += 256) {
+        if constexpr (RG) {
+            if (padded(i / (2 * Ch))) continue;
+        }
+        sz += dzz[i];
+    }
     red[0][t] = s1a; red[1][t] = s2a; red[2][t] = s1b; red[3][t] = s2b; red[4][t] = sz;
     __syncthreads();
     // thread k holds the sums of channel k mod Ch (k mod 2 Ch for the ZeroConv scale): fold the 256 entries down to one
@@ -564,7 +643,13 @@ void fwn_small_grads_launch(float* ga, float* ya, float* gb, float* yb, const fl
 // parameter gradients and may run elsewhere
 void fwn_small_grads_main(float* ga, float* ya, float* gb, float* yb, const float* dzz, const float* an, long M, int Ch,
                           double* partial, hipStream_t st) {
-    hipLaunchKernelGGL(flow_small_grads_kernel, dim3(fwn_small_grads_blocks(M, Ch)), dim3(256), 0, st, ga, ya, gb, yb, dzz, an, M, Ch, partial);
+    hipLaunchKernelGGL(flow_small_grads_kernel<false>, dim3(fwn_small_grads_blocks(M, Ch)), dim3(256), 0, st, ga, ya, gb, yb, dzz, an, M, Ch, partial,
+                       (const int*)nullptr, 1L, 1);
+}
+void fwn_small_grads_main_ragged(float* ga, float* ya, float* gb, float* yb, const float* dzz, const float* an, long nclip, long rows,
+                                 int Ch, const int* len, int spr, double* partial, hipStream_t st) {
+    hipLaunchKernelGGL(flow_small_grads_kernel<true>, dim3(fwn_small_grads_blocks(nclip * rows, Ch)), dim3(256), 0, st, ga, ya, gb, yb, dzz, an,
+                       nclip * rows, Ch, partial, len, rows, spr);
 }
 void fwn_small_grads_final(const float* an, long M, int Ch, const long long* br, const long long* zc, const double* partial, float* db,
                            float* dlogs, float* dzscale, hipStream_t st) {
@@ -792,13 +877,19 @@ void fwn_ew_coupling_fwd(float* yb, const float* Z, const float* ez, long n, int
 }
 void fwn_ew_coupling_bwd(float* g, float* ob, const float* Z, const float* ez, long n, int Ch, float cls, void* dZ,
                          int ldz, float* dzz, hipStream_t st) {
-    hipLaunchKernelGGL(coupling_bwd_kernel, dim3(ew_grid(n)), dim3(256), 0, st, g, ob, Z, ez, n, Ch, cls, (bf16*)dZ, ldz, dzz,
-                       (const float*)nullptr, (bf16*)nullptr, 0);
+    hipLaunchKernelGGL(coupling_bwd_kernel<false>, dim3(ew_grid(n)), dim3(256), 0, st, g, ob, Z, ez, n, Ch, cls, (bf16*)dZ, ldz, dzz,
+                       (const float*)nullptr, (bf16*)nullptr, 0, (const int*)nullptr, 1L, 1, 1.0);
 }
 void fwn_ew_coupling_bwd_ex(float* g, float* ob, const float* Z, const float* ez, long n, int Ch, float cls, void* dZ,
                             int ldz, float* dzz, const float* ya, void* ya_bf, int ldya, hipStream_t st) {
-    hipLaunchKernelGGL(coupling_bwd_kernel, dim3(ew_grid(n)), dim3(256), 0, st, g, ob, Z, ez, n, Ch, cls, (bf16*)dZ, ldz, dzz, ya,
-                       (bf16*)ya_bf, ldya);
+    hipLaunchKernelGGL(coupling_bwd_kernel<false>, dim3(ew_grid(n)), dim3(256), 0, st, g, ob, Z, ez, n, Ch, cls, (bf16*)dZ, ldz, dzz, ya,
+                       (bf16*)ya_bf, ldya, (const int*)nullptr, 1L, 1, 1.0);
+}
+void fwn_ew_coupling_bwd_ragged(float* g, float* ob, const float* Z, const float* ez, long nclip, long rows, int Ch, const int* len,
+                                int spr, void* dZ, int ldz, float* dzz, const float* ya, void* ya_bf, int ldya, hipStream_t st) {
+    const long n = nclip * rows * Ch;
+    hipLaunchKernelGGL(coupling_bwd_kernel<true>, dim3(ew_grid(n)), dim3(256), 0, st, g, ob, Z, ez, n, Ch, 0.0f, (bf16*)dZ, ldz, dzz, ya,
+                       (bf16*)ya_bf, ldya, len, rows, spr, (double)nclip);
 }
 void fwn_ew_gate_bwd(const void* do_, int ld_do, const void* aux, long n, void* dpre, hipStream_t st) {
     hipLaunchKernelGGL(gate_bwd_kernel, dim3(ew_grid(n)), dim3(256), 0, st, (const bf16*)do_, ld_do, (const bf16*)aux, n, (bf16*)dpre);

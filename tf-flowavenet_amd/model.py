@@ -243,20 +243,7 @@ class FloWaveNet:
 
     def _check_lengths(self, lengths, b, t):
         """``lengths`` of a ragged ``reverse`` / ``forward`` -> list of B ints, validated on the host before anything is launched."""
-        import math
-        vals = lengths.detach().cpu().tolist() if hasattr(lengths, "detach") else np.asarray(lengths).tolist()
-        if not isinstance(vals, list) or len(vals) != b:
-            raise ValueError("lengths must hold one length per clip (B=%d), got %r" % (b, vals))
-        unit = math.lcm(self.hop, 1 << self._hparams.n_block)
-        for v in vals:
-            if int(v) != v:
-                raise ValueError("lengths must be integers (samples), got %r" % (v,))
-            if not unit <= v <= t:
-                raise ValueError("length %d outside [%d, T=%d]" % (v, unit, t))
-            if v % unit:
-                raise ValueError("length %d must be a multiple of lcm(hop_size=%d, 2^n_block=%d) = %d"
-                                 % (v, self.hop, 1 << self._hparams.n_block, unit))
-        return [int(v) for v in vals]
+        return check_lengths(lengths, b, t, self.hop, self._hparams.n_block)
 
     def reverse(self, z, c, g=None, dtype=None, lengths=None):
         """z [B,T,1], c [B,T/hop,num_mels] -> x [B,T,1] (model.py:350-396).  fp32 unless ``dtype`` is given: a torch dtype, or
@@ -306,6 +293,25 @@ class FloWaveNet:
         return cur
 
     __call__ = forward
+
+
+def check_lengths(lengths, b, t, hop, n_block):
+    """The lengths of a ragged batch (``FloWaveNet.forward`` / ``reverse``, ``training.GradEngine``) -> list of B ints, validated
+    on the host before anything is launched: one integer per clip, a multiple of lcm(hop, 2^n_block), at least that, at most t."""
+    import math
+    vals = lengths.detach().cpu().tolist() if hasattr(lengths, "detach") else np.asarray(lengths).tolist()
+    if not isinstance(vals, list) or len(vals) != b:
+        raise ValueError("lengths must hold one length per clip (B=%d), got %r" % (b, vals))
+    unit = math.lcm(hop, 1 << n_block)
+    for v in vals:
+        if int(v) != v:
+            raise ValueError("lengths must be integers (samples), got %r" % (v,))
+        if not unit <= v <= t:
+            raise ValueError("length %d outside [%d, T=%d]" % (v, unit, t))
+        if v % unit:
+            raise ValueError("length %d must be a multiple of lcm(hop_size=%d, 2^n_block=%d) = %d"
+                             % (v, hop, 1 << n_block, unit))
+    return [int(v) for v in vals]
 
 
 def z_planes_to_squeezed(zp, n_block, n_flow=2):

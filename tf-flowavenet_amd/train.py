@@ -5,7 +5,7 @@
         -m tf_flowavenet_amd.train --base_dir data/            # one process per GPU, RCCL gradient all-reduce
 
 Same flags as the reference (``--base_dir --input --restore --summary_interval --checkpoint_interval
---eval_interval --train_steps``) plus ``--log_dir`` / ``--seed``.  Input is the output of
+--eval_interval --train_steps``) plus ``--log_dir`` / ``--seed`` / ``--ragged``.  Input is the output of
 ``preprocessing.preprocess``: ``train.txt`` with ``audios/*.npy`` and ``mels/*.npy`` beside it.
 
 Differences (deliberate): the TFRecord round trip (tfrecord.py, dataset.py:20-44) is skipped - the
@@ -15,6 +15,13 @@ train / test split is the reference's ``train_test_split(test_size, random_state
 summaries are JSON lines (``<log_dir>/train/summary.jsonl``, ``test/summary.jsonl``) and evaluation
 audio is written as wav files instead of TensorBoard events; checkpoints are ``.npz`` files that
 ``synthesize.py`` loads (parameters in the reference's layouts, plus the Adam slots and global step).
+
+``--ragged``: utterances shorter than ``max_time_steps`` train too.  Every utterance of at least lcm(hop_size, 2^n_block)
+samples is kept; longer ones are cropped to ``max_time_steps`` at a random start as before, shorter ones go in whole (floored
+to that unit) with their length, and the step takes the lengths (``Trainer.step(x, c, lengths=)``: loss and gradients are means
+over the clips of each clip's own, padding reaches neither).  The batch shape stays ``max_time_steps``, so the step is recorded
+once.  The held-out loss follows the same rule (per-clip ``log_p`` / ``logdet``, what ``score`` reports per utterance); the
+data-dependent init batch is still drawn from full-length crops.
 """
 from __future__ import annotations
 
@@ -29,23 +36,34 @@ import numpy as np
 
 
 class Dataset:
-    """Random fixed-length crops of (mel, audio) pairs (dataset.py:47-85)."""
+    """Random fixed-length crops of (mel, audio) pairs (dataset.py:47-85).
+
+    ragged: utterances of at least lcm(hop_size, 2^n_block) samples are kept; one longer than ``max_time_steps`` is cropped as
+    before, a shorter one goes in whole, floored to that unit and zero-padded to ``max_time_steps``; ``next_train`` /
+    ``next_test`` then return ``(mels, audios, lengths)`` with ``lengths`` the clips' sample counts (int32 [B])."""
     # memory-mapped utterances kept open per rank (_load).  Every numpy memmap pins a dup'd file descriptor, two per
     # utterance: 64 pairs = 128 descriptors, far below the usual soft RLIMIT_NOFILE of 1024 that the GPU runtime, RCCL
     # and the log files also draw on.
     MAX_OPEN = 64
 
-    def __init__(self, metadata_path, hparams, seed=None, rank=0):
+    def __init__(self, metadata_path, hparams, seed=None, rank=0, ragged=False):
         self._hp = hparams
+        self._ragged = bool(ragged)
         self._basedir = os.path.dirname(metadata_path)
         with open(metadata_path, "rt", encoding="utf-8") as f:
             meta = [m.split("|") for m in f.read().strip().split("\n") if m]
         self._frames = hparams.max_time_steps // hparams.hop_size            # dataset.py:13-14
         self._steps = self._frames * hparams.hop_size
         # dataset.py:73 draws the crop start from [0, frames - max_time_frames): needs strictly longer clips
-        meta = [m for m in meta if int(m[2]) // hparams.hop_size > self._frames]
-        if not meta:
-            raise ValueError("no utterance longer than max_time_steps=%d in %s" % (hparams.max_time_steps, metadata_path))
+        if self._ragged:
+            meta = [m for m in meta if int(m[2]) // hparams.hop_size >= self._unit_frames()]
+            if not meta:
+                raise ValueError("no utterance of at least lcm(hop_size, 2^n_block)=%d samples in %s"
+                                 % (self._unit_frames() * hparams.hop_size, metadata_path))
+        else:
+            meta = [m for m in meta if int(m[2]) // hparams.hop_size > self._frames]
+            if not meta:
+                raise ValueError("no utterance longer than max_time_steps=%d in %s" % (hparams.max_time_steps, metadata_path))
         idx = np.arange(len(meta))
         if len(meta) > hparams.test_size:                                    # tfrecord.py:81-82
             from sklearn.model_selection import train_test_split
@@ -57,12 +75,18 @@ class Dataset:
         self._rng = np.random.RandomState(base + 7919 * rank)
         self._cache, self._lru = {}, collections.OrderedDict()
 
+    def _unit_frames(self):
+        """lcm(hop_size, 2^n_block) in frames: the unit a ragged clip's length is a multiple of."""
+        import math
+        return math.lcm(self._hp.hop_size, 1 << self._hp.n_block) // self._hp.hop_size
+
     @classmethod
-    def from_tfrecords(cls, train_path, test_path, hparams, seed=None, rank=0):
+    def from_tfrecords(cls, train_path, test_path, hparams, seed=None, rank=0, ragged=False):
         """The reference's own data files (tfrecord.py:76-88): ``train.tfrecord`` / ``test.tfrecord``."""
         from . import tfrecord
         self = cls.__new__(cls)
         self._hp, self._basedir = hparams, os.path.dirname(train_path)
+        self._ragged = bool(ragged)
         self._frames = hparams.max_time_steps // hparams.hop_size
         self._steps = self._frames * hparams.hop_size
         self._cache, self._lru = {}, collections.OrderedDict()      # TFRecord samples stay resident (not in the LRU)
@@ -70,7 +94,7 @@ class Dataset:
         def load(path, tag):
             metas = []
             for k, (audio, mel, spk) in enumerate(tfrecord.read_samples(path)):
-                if mel.shape[0] > self._frames:
+                if mel.shape[0] >= self._unit_frames() if self._ragged else mel.shape[0] > self._frames:
                     key = "%s-%d" % (tag, k)
                     self._cache[key] = (audio, mel)
                     metas.append([key, key, str(len(audio)), str(spk), ""])
@@ -79,7 +103,8 @@ class Dataset:
         self.train_meta = load(train_path, "train")
         self.test_meta = load(test_path, "test") if test_path and os.path.exists(test_path) else self.train_meta
         if not self.train_meta:
-            raise ValueError("no utterance longer than max_time_steps=%d in %s" % (hparams.max_time_steps, train_path))
+            raise ValueError(("no utterance of at least lcm(hop_size, 2^n_block) samples in %s" % train_path) if self._ragged else
+                             "no utterance longer than max_time_steps=%d in %s" % (hparams.max_time_steps, train_path))
         base = hparams.shuffle_random_seed if seed is None else seed
         self._rng = np.random.RandomState(base + 7919 * rank)
         return self
@@ -107,19 +132,37 @@ class Dataset:
 
     def _batch(self, metas):
         hp = self._hp
-        mels = np.empty((len(metas), self._frames, hp.num_mels), dtype=np.float32)
-        audios = np.empty((len(metas), self._steps), dtype=np.float32)
+        ragged = self._ragged
+        mels = (np.zeros if ragged else np.empty)((len(metas), self._frames, hp.num_mels), dtype=np.float32)
+        audios = (np.zeros if ragged else np.empty)((len(metas), self._steps), dtype=np.float32)
+        lengths = np.full(len(metas), self._steps, dtype=np.int32)
         for k, m in enumerate(metas):
             audio, mel = self._load(m)
-            start = self._rng.randint(0, mel.shape[0] - self._frames)        # dataset.py:73-76
-            mels[k] = mel[start:start + self._frames]
-            audios[k] = audio[start * hp.hop_size:start * hp.hop_size + self._steps]
+            if ragged and mel.shape[0] <= self._frames:                      # a short utterance: whole, floored to the unit
+                u = self._unit_frames()
+                frames = min(mel.shape[0], len(audio) // hp.hop_size) // u * u
+                mels[k, :frames] = mel[:frames]
+                audios[k, :frames * hp.hop_size] = audio[:frames * hp.hop_size]
+                lengths[k] = frames * hp.hop_size
+            else:
+                start = self._rng.randint(0, mel.shape[0] - self._frames)    # dataset.py:73-76
+                mels[k] = mel[start:start + self._frames]
+                audios[k] = audio[start * hp.hop_size:start * hp.hop_size + self._steps]
             del audio, mel              # the batch holds copies: no view outlives this iteration (see _load's close)
-        return mels, audios
+        return (mels, audios, lengths) if ragged else (mels, audios)
 
     def next_train(self):
         pick = self._rng.randint(0, len(self.train_meta), size=self._hp.batch_size)
         return self._batch([self.train_meta[i] for i in pick])
+
+    def next_full(self):
+        """A batch of full-length crops ``(mels, audios)`` whatever the mode: the data-dependent init takes no lengths."""
+        full = [m for m in self.train_meta if int(m[2]) // self._hp.hop_size > self._frames]
+        if not full:
+            raise ValueError("--ragged: the ActNorm data-dependent init needs a batch of full-length crops (init=True takes no "
+                             "lengths), and no training utterance is longer than max_time_steps=%d" % self._hp.max_time_steps)
+        pick = self._rng.randint(0, len(full), size=self._hp.batch_size)
+        return self._batch([full[i] for i in pick])[:2]
 
     def next_test(self):
         pick = self._rng.randint(0, len(self.test_meta), size=self._hp.batch_size)
@@ -252,11 +295,12 @@ def train(log_dir, args, hparams, input_path, device="cuda", params=None):
         print("Checkpoint_path: {}".format(checkpoint_path))
         print("Loading training data from: {}".format(metadata_filename))
     seed = getattr(args, "seed", None)
+    ragged = bool(getattr(args, "ragged", False))
     if metadata_filename.endswith(".tfrecord"):       # the reference's own files (train.py:161-162)
         dataset = Dataset.from_tfrecords(metadata_filename, os.path.join(os.path.dirname(metadata_filename), "test.tfrecord"),
-                                         hparams, seed=seed, rank=rank)
+                                         hparams, seed=seed, rank=rank, ragged=ragged)
     else:
-        dataset = Dataset(metadata_filename, hparams, seed=seed, rank=rank)
+        dataset = Dataset(metadata_filename, hparams, seed=seed, rank=rank, ragged=ragged)
     if params is None:     # the reference's initialisers: he-uniform convs, g = 1, ZeroConv1d all zeros (modules.py:21-22,47-49)
         params = weights.synthetic_params(hparams, hparams.tf_random_seed if seed is None else seed, zero_conv="zeros")
     trainer = Trainer(hparams, params, device=device)
@@ -267,7 +311,7 @@ def train(log_dir, args, hparams, input_path, device="cuda", params=None):
         if rank == 0:
             print("Starting new training!" if not args.restore else "No checkpoint found.")
             print("Init ActNorm layer...", end="")
-        mels, audios = dataset.next_train()
+        mels, audios = dataset.next_full() if ragged else dataset.next_train()
         trainer.ddi(audios, mels)                                             # train.py:221,229 (init=True)
         init_loss = float(trainer.step(audios, mels)[0])                     # ... which also applies an update
         step = trainer.opt.global_step
@@ -282,8 +326,12 @@ def train(log_dir, args, hparams, input_path, device="cuda", params=None):
 
     while step < args.train_steps:
         start_time = time.time()
-        mels, audios = dataset.next_train()
-        loss, log_p, logdet, gnorm = trainer.step(audios, mels)
+        if ragged:
+            mels, audios, lens = dataset.next_train()
+            loss, log_p, logdet, gnorm = trainer.step(audios, mels, lengths=lens)
+        else:
+            mels, audios = dataset.next_train()
+            loss, log_p, logdet, gnorm = trainer.step(audios, mels)
         step = trainer.opt.global_step
         total_loss = float(loss)                                             # synchronises: the step time is real
         step_duration = time.time() - start_time
@@ -292,14 +340,25 @@ def train(log_dir, args, hparams, input_path, device="cuda", params=None):
                 step, step_duration, total_loss, float(log_p), float(logdet)), end="\r")
         if rank == 0 and step % args.summary_interval == 0:
             print("\nWriting summary at step {}".format(step))
-            log(train_logdir, {"step": step, "losses/total_loss": total_loss, "losses/log_p": float(log_p),
-                               "losses/logdet": float(logdet), "learning_rate": learning_rate(step - 1),
-                               "gradient_global_norm": float(gnorm)})
-            tm, ta = dataset.next_test()                                     # get_test_losses, train.py:85-91
+            rec = {"step": step, "losses/total_loss": total_loss, "losses/log_p": float(log_p),
+                   "losses/logdet": float(logdet), "learning_rate": learning_rate(step - 1),
+                   "gradient_global_norm": float(gnorm)}
+            if ragged:
+                rec["mean_clip_length"] = float(np.mean(lens))
+            log(train_logdir, rec)
             model = FloWaveNet(hparams, device=device, cond_mode=1).load_params(trainer.opt.master_views())
-            tlp, tld = model.forward(torch.from_numpy(ta).reshape(ta.shape[0], -1, 1), torch.from_numpy(tm))
-            log(test_logdir, {"step": step, "losses/total_loss": -(float(tlp) + float(tld)),
-                              "losses/log_p": float(tlp), "losses/logdet": float(tld)})
+            if ragged:      # per-clip scalars, each over the clip's own samples: the numbers `score` reports per utterance
+                tm, ta, tl = dataset.next_test()
+                tlp, tld = model.forward(torch.from_numpy(ta).reshape(ta.shape[0], -1, 1), torch.from_numpy(tm), lengths=tl)
+                tlp, tld = tlp.double().mean(), tld.double().mean()
+            else:
+                tm, ta = dataset.next_test()                                 # get_test_losses, train.py:85-91
+                tlp, tld = model.forward(torch.from_numpy(ta).reshape(ta.shape[0], -1, 1), torch.from_numpy(tm))
+            rec = {"step": step, "losses/total_loss": -(float(tlp) + float(tld)),
+                   "losses/log_p": float(tlp), "losses/logdet": float(tld)}
+            if ragged:
+                rec["mean_clip_length"] = float(np.mean(tl))
+            log(test_logdir, rec)
         if rank == 0 and (step % args.checkpoint_interval == 0 or step == args.train_steps):
             save_checkpoint("%s-%d.npz" % (checkpoint_path, step), trainer)
         if rank == 0 and step % args.eval_interval == 0:
@@ -327,6 +386,8 @@ def main(argv=None):
     parser.add_argument("--train_steps", type=int, default=2000000, help="total number of model training steps")
     parser.add_argument("--log_dir", default="logs")
     parser.add_argument("--seed", type=int, default=None)
+    parser.add_argument("--ragged", action="store_true",
+                        help="also train on utterances shorter than max_time_steps, whole, with per-clip lengths")
     args = parser.parse_args(argv)
     import torch
     import torch.distributed as dist

@@ -25,12 +25,14 @@ def _stream(t):
 
 
 def gemm(segs, w, n, m, *, ti=0, bias=None, res=None, rscale=1.0, mask=None, relu=False, oscale=1.0,
-         out=None, out_f32=False, accumulate=False, nsplit=1, split_stride=0, gate=None):
+         out=None, out_f32=False, accumulate=False, nsplit=1, split_stride=0, gate=None, row_len=None):
     """``out[m, n] = oscale * relu?(mask?(sum_s shift(x_s)[:, :k_s] @ w[:, koff_s:koff_s+k_s].T + bias + rscale*res))``.
 
     segs: list of ``(x, k, shift, koff)`` with ``x`` a bf16 2-D tensor (rows, ld); ``w`` bf16 (n, ldw).
     gate: ``(aux, dpre, col0)`` - the 256 output columns from ``col0`` go through the gate derivative into ``dpre``
-    (bf16 [m, 512]) instead of ``out`` (fwn.h ``fwn_gemm_desc.gate_aux``)."""
+    (bf16 [m, 512]) instead of ``out`` (fwn.h ``fwn_gemm_desc.gate_aux``).
+    row_len: ``(lengths, samples_per_row)`` with ``lengths`` an int32 device tensor [m / ti] - a ragged batch: the output rows
+    past each clip's end are stored as exact 0 (fwn.h ``fwn_gemm_desc.row_len``; refused together with ``accumulate``)."""
     import torch
     lib = _lib.load()
     d = _lib.GemmDesc()
@@ -61,6 +63,11 @@ def gemm(segs, w, n, m, *, ti=0, bias=None, res=None, rscale=1.0, mask=None, rel
                 or not (aux.is_contiguous() and dpre.is_contiguous()):
             raise ValueError("gate: aux and dpre must be contiguous bf16 (m, 512)")
         d.gate_aux, d.gate_out, d.gate_col0 = aux.data_ptr(), dpre.data_ptr(), int(col0)
+    if row_len is not None:
+        lens, spr = row_len
+        if lens.dtype != torch.int32 or not lens.is_contiguous() or ti <= 0 or lens.numel() * ti != m:
+            raise ValueError("row_len: a contiguous int32 tensor of m / ti lengths (ti > 0)")
+        d.row_len, d.len_spr = lens.data_ptr(), int(spr)
     _lib.check(lib.fwn_gemm(C.byref(d), _stream(w)), "fwn_gemm")
     return out
 
@@ -351,6 +358,15 @@ class _TrainPack:
         return self.params[name]
 
 
+class DeviceLengths:
+    """Lengths of a ragged batch that are already on the device and already validated: an int32 tensor [B] that
+    ``GradEngine.loss_and_grads`` hands to the kernels as it is, without reading it on the host (the recorded step's static
+    buffer: only kernels read it, at replay)."""
+
+    def __init__(self, tensor):
+        self.tensor = tensor
+
+
 class GradEngine:
     """``loss_and_grads(params, x, c)``: one training forward + backward on the current device.
 
@@ -358,7 +374,13 @@ class GradEngine:
     fp32 device vector (the optimiser's masters) are read in place, anything else is copied into a flat vector the
     engine owns, on every call.
     Returns ``(loss, log_p, logdet, grads)`` with grads a dict name -> fp32 device tensor of the
-    parameter's shape (``d loss / d param``, loss = -(log_p + logdet), train.py:60)."""
+    parameter's shape (``d loss / d param``, loss = -(log_p + logdet), train.py:60).
+
+    ``loss_and_grads(params, x, c, lengths=[...])``: a ragged batch (the rules of ``FloWaveNet.forward(..., lengths=)``).  Clip
+    ``b`` is ``x[b, :lengths[b]]`` with ``c[b, :lengths[b] // hop]``; loss = -(1/B) sum_b (log_p[b] + logdet[b]) with every
+    clip's scalars taken over its own samples, and each gradient is the mean over the clips of that clip's own gradient -
+    whatever (finite) ``x`` and ``c`` hold past a clip's end reaches no bit of either.  log_p / logdet are the batch means;
+    ``per_clip`` then holds the fp32 tensors ``(log_p [B], logdet [B])`` of that call (None after a plain call)."""
 
     def __init__(self, hparams, device="cuda", side_stream=True):
         """side_stream: each block's weight gradients run on a second stream under the next block's backward chain
@@ -372,6 +394,7 @@ class GradEngine:
         self._own_flat = None
         self.side_stream = bool(side_stream)
         self._side = None
+        self.per_clip = None
 
     # ------------------------------------------------------------------ helpers
     def _side_stream(self, dev):
@@ -386,25 +409,38 @@ class GradEngine:
     def _call(self, name, *args):
         _lib.check(getattr(self.lib, name)(*args), name)
 
-    def loss_and_grads(self, params, x, c, grad_out=None, on_block_done=None):
+    def loss_and_grads(self, params, x, c, grad_out=None, on_block_done=None, lengths=None):
         """grad_out: optional dict name -> fp32 tensor (e.g. views of a flat gradient buffer): gradients are
         written there (the large ones in place) and returned as those very tensors.  on_block_done(i) is
         called when every gradient of block i is in grad_out (blocks finish last to first; -1 = the
         up-sampling convs, at the end) - the hook a data-parallel step uses to start that block's
-        all-reduce under the rest of the backward pass."""
+        all-reduce under the rest of the backward pass.
+        lengths: a list, NumPy array or tensor of B sample counts (a ragged batch, see the class) - validated on the host
+        by ``model.check_lengths`` before anything is launched; or ``DeviceLengths`` (already validated, read at run time)."""
         self._gout = grad_out
         self._on_block = on_block_done
         try:
-            return self._loss_and_grads(params, x, c)
+            return self._loss_and_grads(params, x, c, lengths)
         finally:
             _STREAMS.clear()
             self._gout = None
             self._on_block = None
 
-    def _loss_and_grads(self, params, x, c):
+    def check_lengths(self, lengths, b, t):
+        """The host-side validation of a ragged batch: ``FloWaveNet``'s own (``model.check_lengths``) -> list of B ints."""
+        from . import model
+        if getattr(self.hp, "gate_fp8", False):
+            raise ValueError("gate_fp8 hparams take no lengths: the e4m3 copies of h are not masked")
+        return model.check_lengths(lengths, b, t, int(np.prod(self.hp.upsample_scales)), self.hp.n_block)
+
+    def _loss_and_grads(self, params, x, c, lengths=None):
         import torch
         hp, lib = self.hp, self.lib
         dev = torch.device(self.device)
+        if lengths is not None and not isinstance(lengths, DeviceLengths):      # validated on the host before anything is launched
+            shape = tuple(torch.as_tensor(x).shape)
+            b_ = int(shape[0]) if shape else 0
+            lengths = self.check_lengths(lengths, b_, int(np.prod(shape[1:])) if shape else 0)
         st = torch.cuda.current_stream(dev).cuda_stream
         _STREAMS.clear()
         _STREAMS[torch.zeros(0, device=dev).device] = st
@@ -425,9 +461,16 @@ class GradEngine:
         B, T = int(x.shape[0]), int(x.shape[1])
         if T % (1 << hp.n_block) or int(c.shape[1]) * hp.hop_size != T:
             raise ValueError("bad shapes")
-        return self._run(tp, params, x.reshape(B, T), c, B, T, st)
+        lens = None
+        if isinstance(lengths, DeviceLengths):
+            lens = lengths.tensor
+            if lens.dtype != torch.int32 or lens.device != x.device or tuple(lens.shape) != (B,) or not lens.is_contiguous():
+                raise ValueError("DeviceLengths must hold a contiguous int32 tensor [B=%d] on %s" % (B, x.device))
+        elif lengths is not None:
+            lens = torch.tensor(lengths, dtype=torch.int32).to(dev)
+        return self._run(tp, params, x.reshape(B, T), c, B, T, st, lens)
 
-    def _run(self, tp, params, x, c, B, T, st):
+    def _run(self, tp, params, x, c, B, T, st, lens=None):
         """One call of ``fwn_train_loss_and_grads`` (csrc/train_api.hip sequences forward and backward): this method only
         fills the descriptors - packed copies, masters, gradient destinations, per-step tables - and lends a workspace."""
         import torch
@@ -496,11 +539,12 @@ class GradEngine:
         # the weight gradients of a block run on a second stream under the next block's chain (fwn.h fwn_train_desc.side_stream)
         side = self._side_stream(dev)
         td.side_stream = side.cuda_stream if side is not None else None
-        wkey = (B, T, str(dev), bool(td.side_stream))
+        wkey = (B, T, str(dev), bool(td.side_stream), lens is not None)
         if getattr(self, "_ws_key", None) != wkey:
-            need = int(lib.fwn_train_workspace_bytes(C.byref(td), B, T))
+            wname = "fwn_train_ragged_workspace_bytes" if lens is not None else "fwn_train_workspace_bytes"
+            need = int(getattr(lib, wname)(C.byref(td), B, T))
             if need == 0:
-                _lib.check(-1, "fwn_train_workspace_bytes")
+                _lib.check(-1, wname)
             self._ws = torch.empty(need + 256, dtype=torch.uint8, device=dev)
             self._ws_key = wkey
         ws = self._ws
@@ -521,13 +565,20 @@ class GradEngine:
                 return 1
 
         cb = _lib.BLOCK_DONE_FN(block_done)
-        rc = lib.fwn_train_loss_and_grads(C.byref(td), B, T, x.data_ptr(), c.data_ptr(), ws.data_ptr() + off, ws.numel() - off,
-                                          out3.data_ptr(), cb, None, st)
+        if lens is None:
+            self.per_clip = None
+            rc = lib.fwn_train_loss_and_grads(C.byref(td), B, T, x.data_ptr(), c.data_ptr(), ws.data_ptr() + off, ws.numel() - off,
+                                              out3.data_ptr(), cb, None, st)
+        else:
+            out2b = torch.empty(2, B, dtype=torch.float32, device=dev)
+            self.per_clip = (out2b[0], out2b[1])
+            rc = lib.fwn_train_loss_and_grads_ragged(C.byref(td), B, T, x.data_ptr(), c.data_ptr(), lens.data_ptr(), ws.data_ptr() + off,
+                                                     ws.numel() - off, out3.data_ptr(), out2b.data_ptr(), cb, None, st)
         if failure:
             raise failure[0]
-        _lib.check(rc, "fwn_train_loss_and_grads")
+        _lib.check(rc, "fwn_train_loss_and_grads_ragged" if lens is not None else "fwn_train_loss_and_grads")
         td.zero_dead_res = 0
-        self._alive = (masters, x, c)           # until the stream has consumed them
+        self._alive = (masters, x, c, lens)     # until the stream has consumed them
         return out3[0], out3[1], out3[2], {k: go[k] for k in shp}
 
 
@@ -548,6 +599,7 @@ class Trainer:
         self.engine = GradEngine(hparams, device)
         self.graph = bool(graph)
         self._recorded = {}
+        self.per_clip = None
         # False: skip the gradient exchange (bench.py's compute-only step time, to price the overlap)
         self.exchange = True
 
@@ -571,16 +623,24 @@ class Trainer:
             raise RuntimeError("Trainer.ddi: the ranks hold different master weights after the data-dependent init "
                                "(different initial parameters or checkpoints per rank?)")
 
-    def step(self, x, c):
-        """-> (loss, log_p, logdet, grad_norm) device scalars; the masters are updated in place."""
+    def step(self, x, c, lengths=None):
+        """-> (loss, log_p, logdet, grad_norm) device scalars; the masters are updated in place.
+        lengths: a ragged batch (``GradEngine.loss_and_grads``): loss, log_p and logdet are then the means over the clips of
+        the per-clip values, which ``per_clip`` holds afterwards as ``(log_p [B], logdet [B])`` (None after a plain step).
+        The recorded step keeps the lengths in a static device buffer beside x and c - one recording per shape serves every
+        batch, whatever its lengths."""
+        if lengths is not None:
+            import torch
+            xs = torch.as_tensor(x)
+            lengths = self.engine.check_lengths(lengths, int(xs.shape[0]), int(xs.numel() // max(1, int(xs.shape[0]))))
         if self.graph and self.opt.exchange == "allreduce":     # (the sharded exchange is eager only: optim.record_update)
-            return self._step_recorded(x, c)
-        return self._step_eager(x, c)
+            return self._step_recorded(x, c, lengths)
+        return self._step_eager(x, c, lengths)
 
     def _ranges(self):
         return {("upsample" if key == "upsample" else int(key.split("_")[1])): (lo, hi) for key, lo, hi in self.opt.block_ranges()}
 
-    def _step_recorded(self, x, c):
+    def _step_recorded(self, x, c, lengths=None):
         """First call at a shape: eager (creates the packing plan, fills every cache).  Second: record.  The
         recording is a chain of hipGraphs cut where a block's gradients are final, so that with more than one
         rank each block's all-reduce still starts between two replays, under the rest of the backward pass;
@@ -590,11 +650,12 @@ class Trainer:
         dev = torch.device(self.device)
         x = torch.as_tensor(x)
         c = torch.as_tensor(c)
-        key = (tuple(x.shape), tuple(c.shape))
+        # the shapes, not the lengths: one recording serves every ragged batch (the plain step keeps its own key)
+        key = (tuple(x.shape), tuple(c.shape)) + (("ragged",) if lengths is not None else ())
         rec = self._recorded.get(key)
         if rec is None:
             self._recorded[key] = "warm"
-            return self._step_eager(x, c)
+            return self._step_eager(x, c, lengths)
         world = dist.get_world_size(self.opt.group) if dist.is_available() and dist.is_initialized() else 1
         if rec == "warm":
             # cut(-1) below holds for the side-stream sequence only: one stream enqueues the up-sampling backward between
@@ -603,6 +664,7 @@ class Trainer:
                 raise RuntimeError("Trainer: the recorded step needs a GradEngine with side_stream=True")
             xs = torch.empty(tuple(x.shape), dtype=torch.float32, device=dev)
             cs = torch.empty(tuple(c.shape), dtype=torch.float32, device=dev)
+            ls = torch.empty(len(lengths), dtype=torch.int32, device=dev) if lengths is not None else None
             params, gv = self.opt.master_views(), self.opt.grad_views()
             segs, pool = [], torch.cuda.graph_pool_handle()
             side = torch.cuda.Stream(dev)
@@ -630,7 +692,9 @@ class Trainer:
                         cur[0] = torch.cuda.CUDAGraph()
                         cur[0].capture_begin(pool=pool, capture_error_mode="thread_local")
 
-                    loss, log_p, logdet, _ = self.engine.loss_and_grads(params, xs, cs, grad_out=gv, on_block_done=cut)
+                    loss, log_p, logdet, _ = self.engine.loss_and_grads(params, xs, cs, grad_out=gv, on_block_done=cut,
+                                                                        lengths=DeviceLengths(ls) if ls is not None else None)
+                    per_clip = self.engine.per_clip
                     gnorm = self.opt.record_update()
                     cur[0].capture_end()
                     segs.append((cur[0], None))
@@ -644,11 +708,14 @@ class Trainer:
                 torch.cuda.synchronize(dev)
                 warnings.warn("recording the training step failed (%s: %s); continuing with eager steps" % (type(e).__name__, e))
                 self.graph = False
-                return self._step_eager(x, c)
+                return self._step_eager(x, c, lengths)
             torch.cuda.current_stream(dev).wait_stream(side)
-            rec = self._recorded[key] = dict(xs=xs, cs=cs, segs=segs, out=(loss, log_p, logdet, gnorm))
+            rec = self._recorded[key] = dict(xs=xs, cs=cs, ls=ls, segs=segs, out=(loss, log_p, logdet, gnorm), per_clip=per_clip)
         rec["xs"].copy_(x.reshape(rec["xs"].shape), non_blocking=True)
         rec["cs"].copy_(c, non_blocking=True)
+        if rec["ls"] is not None:
+            rec["ls"].copy_(torch.tensor(lengths, dtype=torch.int32), non_blocking=False)
+        self.per_clip = rec["per_clip"]
         self.opt.advance()
         ranges, works = self._ranges(), []
         for g, i in rec["segs"]:
@@ -663,7 +730,7 @@ class Trainer:
                 works.append(self.opt.allreduce_range(lo, hi))
         return rec["out"]
 
-    def _step_eager(self, x, c):
+    def _step_eager(self, x, c, lengths=None):
         params = self.opt.master_views()
         gv = self.opt.grad_views()
         ranges = {("upsample" if key == "upsample" else int(key.split("_")[1])): (lo, hi) for key, lo, hi in self.opt.block_ranges()}
@@ -674,6 +741,7 @@ class Trainer:
                 lo, hi = ranges["upsample" if i < 0 else i]
                 works.append(self.opt.allreduce_range(lo, hi))
 
-        loss, log_p, logdet, grads = self.engine.loss_and_grads(params, x, c, grad_out=gv, on_block_done=block_done)
+        loss, log_p, logdet, grads = self.engine.loss_and_grads(params, x, c, grad_out=gv, on_block_done=block_done, lengths=lengths)
+        self.per_clip = self.engine.per_clip
         gnorm = self.opt.step(works=works)
         return loss, log_p, logdet, gnorm
