@@ -576,6 +576,32 @@ int fwn_ragged_logdet_slots(int64_t B);
 int fwn_ragged_logdet_rows(const float* Z, int64_t B, int64_t rows, int Ch, const float* ez, const float* an,
                            const int32_t* len, int32_t samples_per_row, double* acc, void* stream);
 
+/* ---- ragged batches: the ActNorm data-dependent init (additive; FWN_VERSION unchanged) ----
+ * fwn_actnorm_moments over the clips' own rows.  xa, xb [B][rows][Ch] fp32 (4-byte aligned, Ch a power of two); len: DEVICE
+ * int32 [B], read and clamped on the device as in fwn_mask_rows - clip b counts rows [0, len[b] / samples_per_row) and no row
+ * past that is loaded.  mom[4 Ch + 1] doubles in the layout fwn_actnorm_from_moments reads: per plane (sum | sum of squares)
+ * per channel over the counted rows, then the NUMBER of counted rows, sum_b clamp(len[b], 0, rows samples_per_row) /
+ * samples_per_row, as the last double - so an all-reduce of the buffer weights ranks with different amounts of data
+ * correctly.  The rows of a channel are split over several workgroups whose fp64 partial sums (scratch, at least
+ * fwn_actnorm_moments_ragged_scratch_bytes(B, rows, Ch) bytes, 8-byte aligned; 0 for a bad shape) a second launch adds in a
+ * fixed order: no atomics, two identical calls give identical bits. */
+int64_t fwn_actnorm_moments_ragged_scratch_bytes(int64_t B, int64_t rows, int Ch);
+int fwn_actnorm_moments_ragged(const float* xa, const float* xb, int64_t B, int64_t rows, int Ch, const int32_t* len,
+                               int32_t samples_per_row, double* mom, double* scratch, int64_t scratch_bytes, void* stream);
+/* fwn_model_forward_init for B clips of len_dev[b] <= T samples each (DEVICE int32 [B], validated by the caller as for
+ * fwn_model_reverse_ragged): flow by flow in forward order, b = -mean and logs = log(1 / (sqrt(mean((x + b)^2)) + 1e-7)) / 3 per
+ * channel with the means over the union of the clips' own rows, then the flow as fwn_model_forward_ragged runs it.  Per flow:
+ * fwn_actnorm_moments_ragged; `reduce` (may be NULL: single rank) over the 4 Ch + 1 doubles as in fwn_model_forward_init - the
+ * row count is summed with the moments; fwn_actnorm_from_moments into the flow's table; fwn_fill_neg_shift with that table;
+ * the stages.  out2B [2][B] and z_planes (may be NULL) as in fwn_model_forward_ragged; nothing past a clip's length in x or mel
+ * reaches a table or an output bit.  Null lengths and a gate_fp8 descriptor are refused (FWN_ERR_ARG).  Workspace:
+ * fwn_ragged_init_workspace_bytes (0 for a bad or gate_fp8 descriptor).  fwn_model_forward_ragged and fwn_model_forward[_init]
+ * are unchanged.  Speed: not measured - the pass runs once per training run. */
+size_t fwn_ragged_init_workspace_bytes(const fwn_model_desc* m, int64_t B, int64_t T);
+int fwn_model_forward_init_ragged(const fwn_model_desc* m, int64_t B, int64_t T, const float* x, const float* mel,
+                                  const int32_t* len_dev, void* workspace, size_t workspace_bytes, float* out2B, float* z_planes,
+                                  fwn_reduce_fn reduce, void* user, void* stream);
+
 /* ---- training: loss = -(log_p + logdet) (train.py:56-60) and its gradient with respect to every trainable tensor
  * (the one tf.gradients call of train.py:63-66) for one batch, in ONE call: training forward with what the backward
  * needs kept per flow, then the flows in reverse (coupling, ZeroConv / final / skip / res, the gated layers with their

@@ -244,6 +244,10 @@ SIGNATURES = {
     "fwn_fill_neg_shift": (C.c_int, [vp, i64, i64, C.c_int, vp, vp, i32, vp]),
     "fwn_ragged_logdet_slots": (C.c_int, [i64]),
     "fwn_ragged_logdet_rows": (C.c_int, [vp, i64, i64, C.c_int, vp, vp, vp, i32, vp, vp]),
+    "fwn_actnorm_moments_ragged_scratch_bytes": (i64, [i64, i64, C.c_int]),
+    "fwn_actnorm_moments_ragged": (C.c_int, [vp, vp, i64, i64, C.c_int, vp, i32, vp, vp, i64, vp]),
+    "fwn_ragged_init_workspace_bytes": (C.c_size_t, [C.POINTER(ModelDesc), i64, i64]),
+    "fwn_model_forward_init_ragged": (C.c_int, [C.POINTER(ModelDesc), i64, i64, vp, vp, vp, vp, C.c_size_t, vp, vp, vp, vp, vp]),
 }
 
 _lib = None

@@ -182,6 +182,24 @@ int fwn_actnorm_from_moments(const double* mom, int Ch, float* an, void* stream)
     return check_launch("fwn_actnorm_from_moments");
 }
 
+int64_t fwn_actnorm_moments_ragged_scratch_bytes(int64_t B, int64_t rows, int Ch) {
+    if (B <= 0 || B >= 65536 || rows <= 0 || Ch < 1 || (Ch & (Ch - 1)) != 0 || B * rows > ((int64_t)1 << 40) / Ch) return 0;
+    return (int64_t)fwn_ragged_moments_nslot((long)B, (long)rows, Ch) * 4 * Ch * 8;
+}
+int fwn_actnorm_moments_ragged(const float* xa, const float* xb, int64_t B, int64_t rows, int Ch, const int32_t* len,
+                               int32_t samples_per_row, double* mom, double* scratch, int64_t scratch_bytes, void* stream) {
+    REQUIRE(xa && xb && len && mom && scratch && B > 0 && B < 65536 && rows > 0 && samples_per_row > 0, "fwn_actnorm_moments_ragged: bad argument");
+    REQUIRE(Ch >= 1 && (Ch & (Ch - 1)) == 0, "fwn_actnorm_moments_ragged: Ch=%d must be a power of two", Ch);
+    REQUIRE(((((uintptr_t)xa) | ((uintptr_t)xb)) & 3) == 0 && ((((uintptr_t)mom) | ((uintptr_t)scratch)) & 7) == 0,
+            "fwn_actnorm_moments_ragged: misaligned buffer");
+    REQUIRE(rows <= ((int64_t)1 << 31) / samples_per_row && B * rows <= ((int64_t)1 << 40) / Ch, "fwn_actnorm_moments_ragged: shape too large");
+    const int64_t need = fwn_actnorm_moments_ragged_scratch_bytes(B, rows, Ch);
+    REQUIRE(scratch_bytes >= need, "fwn_actnorm_moments_ragged: scratch of %lld bytes, %lld needed (fwn_actnorm_moments_ragged_scratch_bytes)",
+            (long long)scratch_bytes, (long long)need);
+    fwn_launch_ddi_moments_ragged(xa, xb, (long)B, (long)rows, Ch, len, samples_per_row, mom, scratch, (hipStream_t)stream);
+    return check_launch("fwn_actnorm_moments_ragged");
+}
+
 static int check_desc(const fwn_flow_desc* d) {
     REQUIRE(d, "flow desc is null");
     REQUIRE(d->Ch >= 1 && (d->Ch & (d->Ch - 1)) == 0, "flow desc: Ch=%d must be a power of two", d->Ch);
@@ -473,9 +491,11 @@ struct FlowChain {
 };
 // A flow of a ragged forward pass (fwn_model_forward_ragged): where its tail keeps Z = (log_s | t) [M][2 Ch] fp32 and where
 // the per-clip sums of -log_s go ([B][fwn_ragged_logdet_nslot(B)] fp64).
+// mom_part: a ragged init pass (fwn_model_forward_init_ragged) - scratch of the masked moments, fwn_ragged_moments_nslot chunks.
 struct FlowRagged {
     float* z;
     double* acc;
+    double* mom_part;
 };
 
 static int flow_run_impl(const fwn_flow_desc* d, int64_t B, int64_t T, float* xa, float* xb, const void* ca,
@@ -496,13 +516,18 @@ static int flow_run_impl(const fwn_flow_desc* d, int64_t B, int64_t T, float* xa
     const int M = (int)(B * Ti);
     // ragged batch (len: the clips' lengths in samples, on the device): h rows past a clip's end are zeroed behind every
     // kernel that writes h, so that the taps of the next one read what they read at the end of a clip on its own
-    REQUIRE(!len || (!sync && !h8a && !ddi && !(chain && (chain->xb_out || chain->have_h0)) && (inverse ? !rg : rg && rg->z && rg->acc)),
-            "fwn_flow_run: lengths go with the plain stages only (forward: with the buffers of the per-clip log-det, no init)");
+    REQUIRE(!len || (!sync && !h8a && !(chain && (chain->xb_out || chain->have_h0)) && (inverse ? !rg : rg && rg->z && rg->acc)),
+            "fwn_flow_run: lengths go with the plain stages only (forward: with the buffers of the per-clip log-det)");
+    REQUIRE(!len || !ddi || (ddi == 2 && rg && rg->mom_part),
+            "fwn_flow_run: with lengths the data-dependent init is the one of fwn_model_forward_init_ragged (masked moments)");
     auto mask_h = [&](void* h) { if (len) fwn_launch_mask_rows(h, (long)B, Ti, 512, len, (int)B, 2 * d->Ch, st); };
     if (ddi == 1) fwn_launch_ddi(xa, xb, M, d->Ch, d->an, st);
     if (ddi == 2) {
         REQUIRE(mom, "fwn_flow_run: no moment buffer");
-        fwn_launch_ddi_moments(xa, xb, M, d->Ch, mom, st);
+        // ragged: the clips' own rows only, and their number as the count - the planes hold zeros past a clip's end
+        // (mask_planes), which the plain kernel would add to the count
+        if (len) fwn_launch_ddi_moments_ragged(xa, xb, (long)B, Ti, d->Ch, len, 2 * d->Ch, mom, rg->mom_part, st);
+        else fwn_launch_ddi_moments(xa, xb, M, d->Ch, mom, st);
         rc = check_launch("fwn_actnorm_moments");
         if (rc) return rc;
         if (reduce && reduce(user, mom, 4 * d->Ch + 1, stream) != 0)
@@ -953,7 +978,7 @@ static int planes_go_home(Planes& pl, size_t plane_bytes, hipStream_t st) {   //
 }
 
 struct Carve {
-    size_t cplanes, up0, up1, planes, plane3, h0, h1, o, P, Ppart, partial, mom, h8a, h8b, sync, mel, zsave, acc, total;
+    size_t cplanes, up0, up1, planes, plane3, h0, h1, o, P, Ppart, partial, mom, h8a, h8b, sync, mel, zsave, acc, mompart, total;
     size_t sync_stride, sync_bytes;       // one block of counters per flow (flow_persist.h), zeroed once per pass
     BlockPlan blk[16];
 };
@@ -961,7 +986,8 @@ struct Carve {
 // ragged: a pass with per-clip lengths - every flow a launch per stage (the zero-fills of model_pass run between the
 // stages; the chained front conv reads out_b rows inside the launch that writes them), plus a copy of the mel to mask
 // ragged_fwd: a ragged forward pass - also one flow's Z (reused by the next flow) and every flow's per-clip log-det sums
-static Carve carve(const fwn_model_desc* m, int64_t B, int64_t T, bool ragged = false, bool ragged_fwd = false) {
+// ragged_init: a ragged init pass - also the chunk sums of one flow's masked moments (reused by the next flow)
+static Carve carve(const fwn_model_desc* m, int64_t B, int64_t T, bool ragged = false, bool ragged_fwd = false, bool ragged_init = false) {
     Carve c;
     size_t off = 0;
     const size_t half = m->num_mels / 2;
@@ -1010,6 +1036,12 @@ static Carve carve(const fwn_model_desc* m, int64_t B, int64_t T, bool ragged = 
     c.mel = off; off = align_up(off + (ragged ? (size_t)B * (T / hop_of(m)) * m->num_mels * 4 : 0));
     c.zsave = off; off = align_up(off + (ragged_fwd ? (size_t)B * T * 4 : 0));          // [M][2 Ch] fp32 = B T floats at every block
     c.acc = off; off = align_up(off + (ragged_fwd ? (size_t)m->n_block * m->n_flow * B * fwn_ragged_logdet_nslot((long)B) * 8 : 0));
+    size_t mp = 0;
+    for (int i = 0; ragged_init && i < m->n_block; ++i) {
+        const size_t need = (size_t)fwn_ragged_moments_nslot((long)B, (long)(T >> (i + 1)), 1 << i) * (4 << i) * 8;
+        if (need > mp) mp = need;
+    }
+    c.mompart = off; off = align_up(off + mp);
     c.total = off;
     return c;
 }
@@ -1025,6 +1057,10 @@ size_t fwn_ragged_workspace_bytes(const fwn_model_desc* m, int64_t B, int64_t T)
 size_t fwn_ragged_forward_workspace_bytes(const fwn_model_desc* m, int64_t B, int64_t T) {
     if (check_model(m, B, T) != FWN_OK || B >= 32768) return 0;
     return carve(m, B, T, true, true).total;
+}
+size_t fwn_ragged_init_workspace_bytes(const fwn_model_desc* m, int64_t B, int64_t T) {
+    if (check_model(m, B, T) != FWN_OK || B >= 32768 || m->gate_fp8) return 0;
+    return carve(m, B, T, true, true, true).total;
 }
 
 // len (ragged batch): the stages run on a copy of the mel with the frames past each clip's end zeroed, and so is every inner
@@ -1119,19 +1155,22 @@ int fwn_model_persist_status(const fwn_model_desc* m, int64_t B, int64_t T, cons
 // a later stage reads across it: mel and inner up-sampling stages, planes, h (flow_run_impl), and x_out.  Forward with len:
 // no init; every flow's x_a plane gets -shift in those rows before its front conv and its tail keeps Z (flow_run_impl), the
 // per-clip log-det sums of all flows and the per-clip prior end in out2 [2][B] (the tails' own partials are ignored).
+// ragged_init (fwn_model_forward_init_ragged only): that pass with init 2 - every flow's moments over the clips' own rows.
 static int model_pass(const fwn_model_desc* m, int64_t B, int64_t T, const float* in, const float* mel, void* workspace,
                       size_t workspace_bytes, bool reverse, int init, fwn_reduce_fn reduce, void* user, float* out2, float* z_planes,
-                      float* x_out, void* stream, const int32_t* len = nullptr) {
-    const char* what = len ? (reverse ? "fwn_model_reverse_ragged" : "fwn_model_forward_ragged") : reverse ? "fwn_model_reverse" : "fwn_model_forward";
+                      float* x_out, void* stream, const int32_t* len = nullptr, bool ragged_init = false) {
+    const char* what = len ? (reverse ? "fwn_model_reverse_ragged" : ragged_init ? "fwn_model_forward_init_ragged" : "fwn_model_forward_ragged")
+                           : reverse ? "fwn_model_reverse" : "fwn_model_forward";
     int rc = check_model(m, B, T);
     if (rc) return rc;
     REQUIRE(in && mel && workspace && (reverse ? x_out : out2), "%s: null pointer", what);
     REQUIRE((((uintptr_t)workspace) & 255) == 0, "workspace must be 256-byte aligned");
     REQUIRE(!reverse || ((m->n_block * m->n_flow) & 1) == 0,
             "reverse with odd n_block*n_flow ends in swapped channel order (model.py:199,254); unsupported");
-    REQUIRE(!len || (!m->gate_fp8 && !init),
+    REQUIRE(!len || (!m->gate_fp8 && (ragged_init ? init == 2 && !reverse : !init)),
             "%s: per-clip lengths go with a model without fp8 gates (its e4m3 copies of h are not masked) and without the data-dependent init", what);
-    const Carve c = carve(m, B, T, len != nullptr, len && !reverse);
+    REQUIRE(len || !ragged_init, "%s: null lengths", what);
+    const Carve c = carve(m, B, T, len != nullptr, len && !reverse, ragged_init);
     if (workspace_bytes < c.total)
         return fail(FWN_ERR_WORKSPACE, "workspace %zu < required %zu bytes", workspace_bytes, c.total);
     hipStream_t st = (hipStream_t)stream;
@@ -1183,7 +1222,8 @@ static int model_pass(const fwn_model_desc* m, int64_t B, int64_t T, const float
             double* mom = (double*)(ws + c.mom) + (size_t)(i * nf + j) * mom_stride;
             unsigned* sync = (!init && b.one_launch) ? (unsigned*)(ws + c.sync + (size_t)(i * nf + j) * c.sync_stride) : nullptr;
             FlowChain ch = flow_chain(m, d, next, M, init != 0, pl.spare, have_h0, b.chained && !sync);
-            const FlowRagged rg{(float*)(ws + c.zsave), (double*)(ws + c.acc) + (size_t)(i * nf + j) * B * fwn_ragged_logdet_nslot((long)B)};
+            const FlowRagged rg{(float*)(ws + c.zsave), (double*)(ws + c.acc) + (size_t)(i * nf + j) * B * fwn_ragged_logdet_nslot((long)B),
+                                ragged_init ? (double*)(ws + c.mompart) : nullptr};
             rc = flow_run_impl(d, B, T, pl.at[p], pl.at[p ^ 1], ca, hA, hB, ws + c.o, P, reverse ? nullptr : partial + poff, reverse, init,
                                mom, reduce, user, m->gate_fp8 ? ws + c.h8a : nullptr, m->gate_fp8 ? ws + c.h8b : nullptr, &ch, stream, sync, len,
                                len && !reverse ? &rg : nullptr);
@@ -1239,6 +1279,14 @@ int fwn_model_forward_ragged(const fwn_model_desc* m, int64_t B, int64_t T, cons
     REQUIRE(len_dev, "fwn_model_forward_ragged: null lengths");
     REQUIRE(B < 32768, "fwn_model_forward_ragged: B=%lld clips (at most 32767 per call)", (long long)B);
     return model_pass(m, B, T, x, mel, workspace, workspace_bytes, false, 0, nullptr, nullptr, out2B, z_planes, nullptr, stream, len_dev);
+}
+
+int fwn_model_forward_init_ragged(const fwn_model_desc* m, int64_t B, int64_t T, const float* x, const float* mel, const int32_t* len_dev,
+                                  void* workspace, size_t workspace_bytes, float* out2B, float* z_planes, fwn_reduce_fn reduce, void* user,
+                                  void* stream) {
+    REQUIRE(len_dev, "fwn_model_forward_init_ragged: null lengths");
+    REQUIRE(B < 32768, "fwn_model_forward_init_ragged: B=%lld clips (at most 32767 per call)", (long long)B);
+    return model_pass(m, B, T, x, mel, workspace, workspace_bytes, false, 2, reduce, user, out2B, z_planes, nullptr, stream, len_dev, true);
 }
 
 }  // extern "C"

@@ -720,6 +720,79 @@ __global__ void ddi_from_moments_kernel(const double* __restrict__ mom, int Ch, 
     o[3 * Ch + tau] = (float)(-log(den));
 }
 
+// ---- ragged ActNorm init: one flow's moments over the clips' own rows -------------------------------------
+// xa, xb [nclip][rows][Ch] fp32; clip c counts rows [0, len[c] / spr), clamped to the plane here: no row past a clip's end is
+// loaded.  blockIdx.y = plane, blockIdx.x = chunk g of gridDim.x: the chunks stride over the rows of every clip, so a channel's
+// sum is spread over gridDim.x workgroups (the plain kernel above gives a channel one workgroup: two in all at Ch = 1).
+// part [gridDim.x][4 Ch] fp64 in mom's own layout; a chunk without a share leaves zeros.  Ch <= 256: a workgroup reads 256 / Ch
+// whole rows per step (256 consecutive floats), thread t always channel t % Ch, and the threads of a channel are added pairwise
+// in LDS.  Wider planes: one row per step, thread t channels t, t + 256, ...  Every order is fixed by the grid: no atomics.
+__global__ __launch_bounds__(256) void ddi_moments_ragged_kernel(const float* __restrict__ xa, const float* __restrict__ xb,
+                                                                 long nclip, long rows, int Ch, const int* __restrict__ len,
+                                                                 int spr, double* __restrict__ part) {
+    __shared__ double r1[256], r2[256];
+    const int tid = threadIdx.x, role = blockIdx.y;
+    const float* src = role ? xb : xa;
+    double* out = part + ((size_t)blockIdx.x * 4 + 2 * role) * Ch;
+    auto keep_of = [&](long c) {
+        const long k = (long)len[c] / spr;
+        return k < 0 ? 0 : (k > rows ? rows : k);
+    };
+    if (Ch <= 256) {
+        const int tau = tid & (Ch - 1), sub = tid / Ch, R = 256 / Ch;
+        double s = 0.0, s2 = 0.0;
+        for (long c = 0; c < nclip; ++c) {
+            const long keep = keep_of(c);
+            const float* p = src + (size_t)c * rows * Ch;
+            for (long r = (long)blockIdx.x * R + sub; r < keep; r += (long)gridDim.x * R) {
+                const double v = p[(size_t)r * Ch + tau];
+                s += v;
+                s2 += v * v;
+            }
+        }
+        r1[tid] = s;
+        r2[tid] = s2;
+        __syncthreads();
+        for (int st = 128; st >= Ch; st >>= 1) {             // tid and tid + st hold the same channel (st a multiple of Ch)
+            if (tid < st) { r1[tid] += r1[tid + st]; r2[tid] += r2[tid + st]; }
+            __syncthreads();
+        }
+        if (tid < Ch) { out[tau] = r1[tid]; out[Ch + tau] = r2[tid]; }
+    } else {
+        for (int tau = tid; tau < Ch; tau += 256) {
+            double s = 0.0, s2 = 0.0;
+            for (long c = 0; c < nclip; ++c) {
+                const long keep = keep_of(c);
+                const float* p = src + (size_t)c * rows * Ch;
+                for (long r = blockIdx.x; r < keep; r += gridDim.x) {
+                    const double v = p[(size_t)r * Ch + tau];
+                    s += v;
+                    s2 += v * v;
+                }
+            }
+            out[tau] = s;
+            out[Ch + tau] = s2;
+        }
+    }
+}
+// second stage: mom[i] = the chunks' part[g][i] added in index order, mom[4 Ch] = the number of rows counted
+__global__ void ddi_moments_ragged_finish_kernel(const double* __restrict__ part, int nslot, long nclip, long rows, int Ch,
+                                                 const int* __restrict__ len, int spr, double* __restrict__ mom) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < 4 * Ch) {
+        double s = 0.0;
+        for (int g = 0; g < nslot; ++g) s += part[(size_t)g * 4 * Ch + i];
+        mom[i] = s;
+    } else if (i == 4 * Ch) {
+        long n = 0;
+        for (long c = 0; c < nclip; ++c) {
+            const long k = (long)len[c] / spr;
+            n += k < 0 ? 0 : (k > rows ? rows : k);
+        }
+        mom[i] = (double)n;
+    }
+}
+
 // ---- prior + log-det finalisation: out2 = (log_p, logdet), model.py:342-347 -----------------
 __global__ __launch_bounds__(1024) void prior_kernel(const float* __restrict__ z, long n,
                                                      const float* __restrict__ partial, int n_partial,
@@ -905,6 +978,19 @@ void fwn_launch_ddi_from_moments(const double* mom, int Ch, float* an, hipStream
 }
 void fwn_launch_ddi(const float* xa, const float* xb, int M, int Ch, float* an, hipStream_t st) {
     hipLaunchKernelGGL(ddi_kernel, dim3(2 * Ch), dim3(256), 0, st, xa, xb, M, Ch, an);
+}
+// chunks of the ragged moments: about 4096 elements of a plane each, 64 at most (the shape decides, not the lengths)
+int fwn_ragged_moments_nslot(long nclip, long rows, int Ch) {
+    const long want = nclip * rows * Ch / 4096;
+    return (int)(want < 1 ? 1 : (want > 64 ? 64 : want));
+}
+void fwn_launch_ddi_moments_ragged(const float* xa, const float* xb, long nclip, long rows, int Ch, const int* len,
+                                   int samples_per_row, double* mom, double* part, hipStream_t st) {
+    const int nslot = fwn_ragged_moments_nslot(nclip, rows, Ch);
+    hipLaunchKernelGGL(ddi_moments_ragged_kernel, dim3((unsigned)nslot, 2), dim3(256), 0, st, xa, xb, nclip, rows, Ch, len,
+                       samples_per_row, part);
+    hipLaunchKernelGGL(ddi_moments_ragged_finish_kernel, dim3((4 * Ch + 1 + 63) / 64), dim3(64), 0, st, part, nslot, nclip, rows, Ch,
+                       len, samples_per_row, mom);
 }
 void fwn_launch_prior(const float* planes, long n, const float* partial, int n_partial, double inv_bt,
                       float* out2, hipStream_t st) {

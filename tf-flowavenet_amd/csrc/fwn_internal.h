@@ -153,6 +153,11 @@ void fwn_launch_ragged_finish(const float* planes, long nclip, long T, const dou
 void fwn_launch_ddi(const float* xa, const float* xb, int M, int Ch, float* an, hipStream_t st);
 void fwn_launch_ddi_moments(const float* xa, const float* xb, int M, int Ch, double* mom, hipStream_t st);
 void fwn_launch_ddi_from_moments(const double* mom, int Ch, float* an, hipStream_t st);
+// ragged ActNorm init (aux_kernels.hip): fwn_launch_ddi_moments over rows [0, len[c] / samples_per_row) of every clip c of
+// [nclip][rows][Ch] planes, mom[4 Ch] = the rows counted.  part: [fwn_ragged_moments_nslot(nclip, rows, Ch)][4 Ch] fp64 scratch.
+int fwn_ragged_moments_nslot(long nclip, long rows, int Ch);
+void fwn_launch_ddi_moments_ragged(const float* xa, const float* xb, long nclip, long rows, int Ch, const int* len,
+                                   int samples_per_row, double* mom, double* part, hipStream_t st);
 void fwn_launch_prior(const float* planes, long n, const float* partial, int n_partial, double inv_bt,
                       float* out2, hipStream_t st);
 

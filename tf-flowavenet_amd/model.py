@@ -38,7 +38,7 @@ class FloWaveNet:
         cond_stream=False leaves the fragment-order copy of the hoisted conditioning's weights unpacked (csrc/cond_rs.h): the
         ring-tile kernel then runs at every row count (same sums in the same order, other split counts).
         group: the ``torch.distributed`` process group a data-parallel job shards its batch over (None = the
-        default group when one is initialised; False: none - a model only one rank builds).  It only matters for ``init=True``: the ActNorm data-dependent
+        default group when one is initialised; False: none - a model only one rank builds).  It only matters for ``init=True`` and ``forward_init``: the ActNorm data-dependent
         init then uses the statistics of the GLOBAL batch (moments all-reduced flow by flow) so every rank ends
         with the same parameters - the reference's towers race on that assign (model.py:39, train.py:43-57)."""
         if not hparams.affine:
@@ -131,13 +131,14 @@ class FloWaveNet:
         """Scratch for one pass.  One workspace per (B, T, HIP stream): passes issued on different
         streams (e.g. a forward and an inverse overlapping on the chip) never share scratch.  A ragged inverse
         (``reverse(..., lengths=)``) keeps a workspace of its own: it also holds the masked copy of the mel.  So does a
-        ragged forward (``ragged="forward"``): one flow's ZeroConv output and the per-clip log-det sums on top of that."""
+        ragged forward (``ragged="forward"``): one flow's ZeroConv output and the per-clip log-det sums on top of that; and a
+        ragged init (``ragged="init"``): the chunk sums of the masked moments on top of those."""
         import torch
-        key = (b, t, self._stream()) + ((("ragged", ragged) if ragged == "forward" else ("ragged",)) if ragged else ())
+        key = self._ws_key(b, t, ragged)
         ws = self._ws.get(key)
         if ws is None:
-            name = ("fwn_ragged_forward_workspace_bytes" if ragged == "forward" else "fwn_ragged_workspace_bytes") if ragged \
-                else "fwn_workspace_bytes"
+            name = {"forward": "fwn_ragged_forward_workspace_bytes", "init": "fwn_ragged_init_workspace_bytes"}.get(
+                ragged, "fwn_ragged_workspace_bytes") if ragged else "fwn_workspace_bytes"
             n = getattr(self._lib, name)(C.byref(self._packed.model_desc), b, t)
             if n == 0:
                 _lib.check(-1, name)
@@ -147,6 +148,9 @@ class FloWaveNet:
             self._ws[key] = ws
         off = (-ws.data_ptr()) % 256
         return ws.data_ptr() + off, ws.numel() - off
+
+    def _ws_key(self, b, t, ragged=False):
+        return (b, t, self._stream()) + ((("ragged", ragged) if ragged in ("forward", "init") else ("ragged",)) if ragged else ())
 
     def _stream(self):
         import torch
@@ -172,7 +176,7 @@ class FloWaveNet:
         :lengths[b] // hop])`` returns for that clip alone (to rounding) - the prior mean over the clip's own samples, the
         coupling means over its own rows.  Whatever (finite) ``x`` and ``c`` hold past a clip's length reaches no output
         bit; with ``return_z`` the planes are exactly 0 there, and ``reverse(z, c, lengths=lengths)`` inverts them.
-        ``init=True`` (the data-dependent init is defined on a full batch) and ``gate_fp8`` models raise ``ValueError``."""
+        ``init=True`` (the data-dependent init of a ragged batch is ``forward_init``) and ``gate_fp8`` models raise ``ValueError``."""
         import torch
         self._check_g(g)
         b, t, x32, c32 = self._prep(x, c, "x")
@@ -198,7 +202,7 @@ class FloWaveNet:
         if self._gate_fp8:
             raise ValueError("a gate_fp8 model takes no lengths: the e4m3 copies of h are not masked")
         if self._init:
-            raise ValueError("init=True takes no lengths: the data-dependent ActNorm init is defined on a full batch")
+            raise ValueError("init=True takes no lengths: the data-dependent ActNorm init of a ragged batch is forward_init(x, c, lengths)")
         lens = torch.tensor(self._check_lengths(lengths, b, t), dtype=torch.int32).to(self._device)
         wsp, wsn = self._workspace(b, t, ragged="forward")
         out = torch.empty(2, b, dtype=torch.float32, device=self._device)
@@ -207,6 +211,35 @@ class FloWaveNet:
                                                 lens.data_ptr(), wsp, wsn, out.data_ptr(), zp.data_ptr() if return_z else None,
                                                 self._stream())
         _lib.check(rc, "fwn_model_forward_ragged")
+        return (out[0], out[1], zp) if return_z else (out[0], out[1])
+
+    def forward_init(self, x, c, lengths, g=None, return_z=False):
+        """The ActNorm data-dependent init from a ragged batch, whatever ``init=`` the constructor got: flow by flow, ``b`` and
+        ``logs`` from the per-channel mean and mean square over the union of the clips' own rows - nothing past a clip's length
+        is read or counted - and then the flow as ``forward(..., lengths=)`` runs it.  The tables stay in the packed model
+        (``export_actnorm()``), and the next ``forward`` is a plain one.  -> per-clip ``(log_p [B], logdet [B])`` (and the
+        planes [2][B][T/2], exactly 0 past each clip, with ``return_z``).  ``lengths``: the rules of ``forward``.  In a
+        data-parallel job (``group``) the moments AND the row count are all-reduced flow by flow, so ranks holding different
+        amounts of audio are weighted by it and every rank derives the same tables.  ``gate_fp8`` models raise ``ValueError``."""
+        import torch
+        self._check_g(g)
+        b, t, x32, c32 = self._prep(x, c, "x")
+        if self._gate_fp8:
+            raise ValueError("a gate_fp8 model takes no lengths: the e4m3 copies of h are not masked")
+        lens = torch.tensor(self._check_lengths(lengths, b, t), dtype=torch.int32).to(self._device)
+        wsp, wsn = self._workspace(b, t, ragged="init")
+        out = torch.empty(2, b, dtype=torch.float32, device=self._device)
+        zp = torch.empty(2, b, t // 2, dtype=torch.float32, device=self._device) if return_z else None
+        cb, failure = None, []
+        if self._dp_world() > 1:
+            cb = self._reduce_callback(self._ws[self._ws_key(b, t, "init")], failure)
+        rc = self._lib.fwn_model_forward_init_ragged(C.byref(self._packed.model_desc), b, t, x32.data_ptr(), c32.data_ptr(),
+                                                     lens.data_ptr(), wsp, wsn, out.data_ptr(), zp.data_ptr() if return_z else None,
+                                                     cb, None, self._stream())
+        if failure:
+            raise failure[0]
+        _lib.check(rc, "fwn_model_forward_init_ragged")
+        self._init = False
         return (out[0], out[1], zp) if return_z else (out[0], out[1])
 
     def _dp_world(self):
@@ -219,10 +252,21 @@ class FloWaveNet:
         """init=True on one rank of a data-parallel job: ``fwn_model_forward_init`` calls back before each flow's
         ActNorm tables are derived; the callback all-reduces that flow's 4 Ch + 1 moment doubles (RCCL; they live
         inside this pass's workspace tensor) in stream order."""
+        failure = []
+        cb = self._reduce_callback(self._ws[(b, t, self._stream())], failure)
+        rc = self._lib.fwn_model_forward_init(C.byref(self._packed.model_desc), b, t, x32.data_ptr(), c32.data_ptr(),
+                                              wsp, wsn, out2.data_ptr(), zp.data_ptr() if zp is not None else None,
+                                              cb, None, self._stream())
+        if failure:
+            raise failure[0]
+        _lib.check(rc, "fwn_model_forward_init")
+
+    def _reduce_callback(self, ws, failure):
+        """The ``fwn_reduce_fn`` of a data-parallel init pass running in the workspace tensor ``ws``: an in-place all-reduce of
+        the n doubles at ``buf`` (inside ``ws``) in stream order; what it raises lands in ``failure``."""
         import torch
         from . import distributed
-        ws = self._ws[(b, t, self._stream())]
-        base, failure = ws.data_ptr(), []
+        base = ws.data_ptr()
 
         def reduce(user, buf, n, stream):
             try:
@@ -233,13 +277,7 @@ class FloWaveNet:
                 failure.append(e)
                 return 1
 
-        cb = _lib.REDUCE_FN(reduce)
-        rc = self._lib.fwn_model_forward_init(C.byref(self._packed.model_desc), b, t, x32.data_ptr(), c32.data_ptr(),
-                                              wsp, wsn, out2.data_ptr(), zp.data_ptr() if zp is not None else None,
-                                              cb, None, self._stream())
-        if failure:
-            raise failure[0]
-        _lib.check(rc, "fwn_model_forward_init")
+        return _lib.REDUCE_FN(reduce)
 
     def _check_lengths(self, lengths, b, t):
         """``lengths`` of a ragged ``reverse`` / ``forward`` -> list of B ints, validated on the host before anything is launched."""

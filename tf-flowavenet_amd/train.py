@@ -5,7 +5,7 @@
         -m tf_flowavenet_amd.train --base_dir data/            # one process per GPU, RCCL gradient all-reduce
 
 Same flags as the reference (``--base_dir --input --restore --summary_interval --checkpoint_interval
---eval_interval --train_steps``) plus ``--log_dir`` / ``--seed`` / ``--ragged``.  Input is the output of
+--eval_interval --train_steps``) plus ``--log_dir`` / ``--seed`` / ``--ragged`` / ``--ragged_init``.  Input is the output of
 ``preprocessing.preprocess``: ``train.txt`` with ``audios/*.npy`` and ``mels/*.npy`` beside it.
 
 Differences (deliberate): the TFRecord round trip (tfrecord.py, dataset.py:20-44) is skipped - the
@@ -21,7 +21,10 @@ samples is kept; longer ones are cropped to ``max_time_steps`` at a random start
 to that unit) with their length, and the step takes the lengths (``Trainer.step(x, c, lengths=)``: loss and gradients are means
 over the clips of each clip's own, padding reaches neither).  The batch shape stays ``max_time_steps``, so the step is recorded
 once.  The held-out loss follows the same rule (per-clip ``log_p`` / ``logdet``, what ``score`` reports per utterance); the
-data-dependent init batch is still drawn from full-length crops.
+data-dependent init batch is drawn from full-length crops (``Dataset.next_full``) wherever the corpus has an utterance longer
+than ``max_time_steps``; where it has none - prompts, commands, digits - the init takes a ragged batch drawn like a training
+batch (``Dataset.next_init``, ``Trainer.ddi(x, c, lengths=)``: ActNorm statistics over the clips' own samples), and the
+init-step update runs with those lengths.  ``--ragged_init`` takes the ragged init batch on any corpus.
 """
 from __future__ import annotations
 
@@ -163,6 +166,15 @@ class Dataset:
                              "lengths), and no training utterance is longer than max_time_steps=%d" % self._hp.max_time_steps)
         pick = self._rng.randint(0, len(full), size=self._hp.batch_size)
         return self._batch([full[i] for i in pick])[:2]
+
+    def has_full(self):
+        """Whether ``next_full`` has anything to draw from: a training utterance longer than ``max_time_steps``."""
+        return any(int(m[2]) // self._hp.hop_size > self._frames for m in self.train_meta)
+
+    def next_init(self):
+        """The batch of a data-dependent init that takes lengths, drawn as ``next_train`` draws: ``(mels, audios, lengths)`` in
+        ragged mode, ``next_train``'s pair otherwise."""
+        return self.next_train()
 
     def next_test(self):
         pick = self._rng.randint(0, len(self.test_meta), size=self._hp.batch_size)
@@ -311,9 +323,14 @@ def train(log_dir, args, hparams, input_path, device="cuda", params=None):
         if rank == 0:
             print("Starting new training!" if not args.restore else "No checkpoint found.")
             print("Init ActNorm layer...", end="")
-        mels, audios = dataset.next_full() if ragged else dataset.next_train()
-        trainer.ddi(audios, mels)                                             # train.py:221,229 (init=True)
-        init_loss = float(trainer.step(audios, mels)[0])                     # ... which also applies an update
+        # --ragged: full-length crops where the corpus has any (no lengths); a ragged batch where it has none, or on request
+        lens = None
+        if ragged and (bool(getattr(args, "ragged_init", False)) or not dataset.has_full()):
+            mels, audios, lens = dataset.next_init()
+        else:
+            mels, audios = dataset.next_full() if ragged else dataset.next_train()
+        trainer.ddi(audios, mels, lengths=lens)                               # train.py:221,229 (init=True)
+        init_loss = float(trainer.step(audios, mels, lengths=lens)[0])       # ... which also applies an update
         step = trainer.opt.global_step
         if rank == 0:
             print(" OK. Init loss: {:.5f}".format(init_loss))
@@ -387,7 +404,12 @@ def main(argv=None):
     parser.add_argument("--log_dir", default="logs")
     parser.add_argument("--seed", type=int, default=None)
     parser.add_argument("--ragged", action="store_true",
-                        help="also train on utterances shorter than max_time_steps, whole, with per-clip lengths")
+                        help="also train on utterances shorter than max_time_steps, whole, with per-clip lengths; the ActNorm init "
+                             "batch is full-length crops where the corpus has an utterance longer than max_time_steps, a ragged batch "
+                             "where it has none")
+    parser.add_argument("--ragged_init", action="store_true",
+                        help="with --ragged: take the ActNorm init batch as a training batch is drawn (short utterances whole, with "
+                             "their lengths) on any corpus")
     args = parser.parse_args(argv)
     import torch
     import torch.distributed as dist

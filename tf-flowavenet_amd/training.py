@@ -603,17 +603,22 @@ class Trainer:
         # False: skip the gradient exchange (bench.py's compute-only step time, to price the overlap)
         self.exchange = True
 
-    def ddi(self, x, c):
+    def ddi(self, x, c, lengths=None):
         """ActNorm data-dependent init from the GLOBAL batch (train.py:221,229 with init=True): each rank pushes its
         shard through the flows and the per-channel moments are all-reduced flow by flow (``FloWaveNet`` with
         ``group``), so every rank derives bit-identical b / logs - the single-process result on the concatenated
-        batch up to summation order.  (The reference lets its towers race on this assign: SURVEY section 2.1 C2.)"""
+        batch up to summation order.  (The reference lets its towers race on this assign: SURVEY section 2.1 C2.)
+        lengths: a ragged batch (``FloWaveNet.forward_init``) - the statistics are those of the clips' own rows, and the ranks
+        are weighted by the rows they hold."""
         from .model import FloWaveNet
         import torch
         views = self.opt.master_views()
         m = FloWaveNet(self.hp, init=True, device=self.device, cond_mode=1, group=self.opt.group).load_params(views)
         xx = torch.as_tensor(x).to(self.device)
-        m.forward(xx.reshape(xx.shape[0], -1, 1), torch.as_tensor(c).to(self.device))
+        if lengths is not None:
+            m.forward_init(xx.reshape(xx.shape[0], -1, 1), torch.as_tensor(c).to(self.device), lengths)
+        else:
+            m.forward(xx.reshape(xx.shape[0], -1, 1), torch.as_tensor(c).to(self.device))
         for k, v in m.export_actnorm().items():
             views[k].copy_(torch.as_tensor(v).to(self.device).reshape(views[k].shape))
         # Only the ActNorm tables were made identical above (moment all-reduce).  Any other per-rank difference in the
