@@ -371,6 +371,10 @@ typedef struct fwn_gemm_desc {
     const int32_t* row_len; int32_t len_spr, pad1_;
 } fwn_gemm_desc;
 int fwn_gemm(const fwn_gemm_desc* g, void* stream);
+/* Host only: the tile fwn_gemm would launch for this descriptor as BM * 1000 + BN (256128, 128128, 64128, or 32064: the 32 x 64
+ * tile with a 4-way split-K inside the workgroup), -1 with fwn_last_error set for a descriptor fwn_gemm refuses.  The sibling of
+ * fwn_tn_gemm_tile; additive, FWN_VERSION unchanged. */
+int fwn_gemm_tile(const fwn_gemm_desc* g);
 /* For tap z < ntap (shift = shift0 + z*dshift): dst[z*C + c][m] = src[m + shift][c] (zero where the tap
  * leaves its clip / the matrix; columns m >= M zero), dst bf16 [ntap*C (+1)][ld_dst]; ones_row: the row after
  * the last tap = 1 for m < M (bias gradients ride the weight-gradient GEMM). */

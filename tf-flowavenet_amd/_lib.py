@@ -198,6 +198,7 @@ SIGNATURES = {
     "fwn_tn_gemm": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, i64, C.c_int, vp]),
     "fwn_colsum_bf16": (C.c_int, [vp, i64, C.c_int, C.c_int, C.c_float, vp, vp, vp]),
     "fwn_gemm": (C.c_int, [C.POINTER(GemmDesc), vp]),
+    "fwn_gemm_tile": (C.c_int, [C.POINTER(GemmDesc)]),
     "fwn_upsample_bwd_partials": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "fwn_upsample_bwd": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp]),
     "fwn_gate_train": (C.c_int, [C.POINTER(FlowDesc), C.c_int, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp]),

@@ -665,7 +665,8 @@ int fwn_mel_spectrogram(const float* wav, int64_t B, int64_t T, const float* win
 }
 
 // ---- training-side primitives --------------------------------------------------------------------
-int fwn_gemm(const fwn_gemm_desc* g, void* stream) {
+// what fwn_gemm accepts: shared with fwn_gemm_tile, so that the query refuses exactly the descriptors the launch refuses
+static int gemm_desc_check(const fwn_gemm_desc* g) {
     REQUIRE(g && g->W && g->Y, "fwn_gemm: null pointer");
     REQUIRE(g->nseg >= 1 && g->nseg <= FWN_GEMM_MAXSEG, "fwn_gemm: nseg=%d", g->nseg);
     REQUIRE(g->M > 0 && g->N > 0 && g->ldw > 0 && g->ldy >= g->N && g->Ti >= 0, "fwn_gemm: bad shape");
@@ -694,9 +695,15 @@ int fwn_gemm(const fwn_gemm_desc* g, void* stream) {
     REQUIRE(!g->row_len || (g->Ti > 0 && g->M % g->Ti == 0 && g->len_spr > 0 && g->nsplit == 1),
             "fwn_gemm: row_len needs clips (Ti > 0, M a multiple of Ti), len_spr > 0 and no split-K");
     REQUIRE(!g->row_len || !g->accumulate, "fwn_gemm: row_len is refused together with accumulate");
+    return FWN_OK;
+}
+int fwn_gemm(const fwn_gemm_desc* g, void* stream) {
+    const int rc = gemm_desc_check(g);
+    if (rc != FWN_OK) return rc;
     fwn_gemm_launch(g, (hipStream_t)stream);
     return check_launch("fwn_gemm");
 }
+int fwn_gemm_tile(const fwn_gemm_desc* g) { return gemm_desc_check(g) == FWN_OK ? fwn_gemm_tile_rule(g) : -1; }
 int fwn_transpose_shift(const void* src, int M, int C, int ld_src, int shift0, int dshift, int ntap, int Ti, void* dst,
                         int ld_dst, int ones_row, void* stream) {
     REQUIRE(src && dst && M > 0 && C > 0 && ld_src >= C && ld_dst >= M && Ti >= 0 && ntap >= 1 && ntap <= 64,

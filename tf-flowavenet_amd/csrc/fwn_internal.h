@@ -171,6 +171,7 @@ void fwn_launch_adam(float* w, const float* g, float* m, float* v, long n, const
 // train_kernels.hip
 struct fwn_gemm_desc;
 int fwn_gemm_launch(const fwn_gemm_desc* g, hipStream_t st);
+int fwn_gemm_tile_rule(const fwn_gemm_desc* g);      // BM * 1000 + BN of the tile fwn_gemm_launch runs
 void fwn_transpose_launch(const void* src, int M, int C, int ld_src, int shift0, int dshift, int ntap, int Ti, void* dst,
                           int ld_dst, int ones_row, hipStream_t st);
 void fwn_reduce_splits_launch(const float* partial, int nsplit, long stride, long n, float scale, float* out,

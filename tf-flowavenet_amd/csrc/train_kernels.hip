@@ -297,10 +297,8 @@ __global__ __launch_bounds__(64 * WM * WN * KSP) void lin_kernel(const fwn_gemm_
     gemm_ring_body<BM, BN, WM, WN, BK, D, LinProb<RL>, KSP>(p, wg / ntn, wg % ntn);
 }
 
-int fwn_gemm_launch(const fwn_gemm_desc* g, hipStream_t st) {
-    const fwn_gemm_desc& p = *g;
-    int nq_all = 0;
-    for (int s = 0; s < g->nseg; ++s) nq_all += (g->seg[s].k + 63) / 64;
+// The tile fwn_gemm_launch runs at (M, N, nsplit), as BM * 1000 + BN: what fwn_gemm_tile reports.
+int fwn_gemm_tile_rule(const fwn_gemm_desc* g) {
     const int M = g->M, ns = g->nsplit;
     const int n128 = (g->N + 127) / 128;
     // Tile by the operand-stream cost of the launch (one workgroup per CU pulls (BM + BN) K 2 bytes through it):
@@ -309,24 +307,36 @@ int fwn_gemm_launch(const fwn_gemm_desc* g, hipStream_t st) {
     // conditioning-gradient GEMMs of the late blocks: N = cin up to 10240 against a few hundred rows).
     const int w256 = ((M + 255) / 256) * n128 * ns, w128 = ((M + 127) / 128) * n128 * ns, w64 = ((M + 63) / 64) * n128 * ns;
     const int c256 = ((w256 + 255) / 256) * 384, c128 = ((w128 + 255) / 256) * 256, c64 = ((w64 + 255) / 256) * 192;
+    if (c256 <= c128 && c256 <= c64) return 256128;
+    if (c128 <= c64) return 128128;
+    // A workgroup streams (BM + BN) K 2 bytes through ONE CU at ~50 GB/s: a launch of a few dozen 64 x 128 tiles is
+    // bound by that, not by the chip.  Below FWN_LIN_TINY such workgroups, 32 x 64 tiles (4-way split-K inside the
+    // workgroup): four times the CUs, half the bytes each.
+    constexpr int FWN_LIN_TINY = 40;
+    return w64 < FWN_LIN_TINY ? 32064 : 64128;
+}
+
+int fwn_gemm_launch(const fwn_gemm_desc* g, hipStream_t st) {
+    const fwn_gemm_desc& p = *g;
+    int nq_all = 0;
+    for (int s = 0; s < g->nseg; ++s) nq_all += (g->seg[s].k + 63) / 64;
+    const int M = g->M, ns = g->nsplit;
+    const int n128 = (g->N + 127) / 128;
+    const int tile = fwn_gemm_tile_rule(g);
     // with lengths (g->row_len) the same tile from the instantiation whose epilogue reads them
 #define FWN_LIN_LAUNCH(grid, block, ntn_, nq_, ...)                                                                  \
     do {                                                                                                             \
         if (g->row_len) hipLaunchKernelGGL((lin_kernel<true, __VA_ARGS__>), grid, dim3(block), 0, st, p, ntn_, nq_); \
         else hipLaunchKernelGGL((lin_kernel<false, __VA_ARGS__>), grid, dim3(block), 0, st, p, ntn_, nq_);           \
     } while (0)
-    if (c256 <= c128 && c256 <= c64) {
+    if (tile == 256128) {
         FWN_LIN_LAUNCH(dim3(((M + 255) / 256) * n128, 1, ns), 1024, n128, nq_all, 256, 128, 8, 2, 3);
-    } else if (c128 <= c64) {
+    } else if (tile == 128128) {
         FWN_LIN_LAUNCH(dim3(((M + 127) / 128) * n128, 1, ns), 512, n128, nq_all, 128, 128, 4, 2, 3);
     } else {   // small M: 128-wide K chunks (256-byte LDS rows) - a third less time per unit of K on these latency chains
         int nq128 = 0;
         for (int s = 0; s < g->nseg; ++s) nq128 += (g->seg[s].k + 127) / 128;
-        // A workgroup streams (BM + BN) K 2 bytes through ONE CU at ~50 GB/s: a launch of a few dozen 64 x 128 tiles is
-        // bound by that, not by the chip.  Below FWN_LIN_TINY such workgroups, 32 x 64 tiles (4-way split-K inside the
-        // workgroup): four times the CUs, half the bytes each.
-        constexpr int FWN_LIN_TINY = 40;
-        if (((M + 63) / 64) * n128 * ns < FWN_LIN_TINY) {
+        if (tile == 32064) {
             const int n64 = (g->N + 63) / 64;
             FWN_LIN_LAUNCH(dim3(((M + 31) / 32) * n64, 1, ns), 256, n64, nq128, 32, 64, 1, 1, 6, 4, 128);
         } else {
