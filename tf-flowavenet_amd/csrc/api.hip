@@ -8,6 +8,7 @@
 
 #include "../../include/fwn.h"
 #include "fwn_internal.h"
+#include "fwn_sequence.h"
 
 static thread_local char g_err[512] = "";
 
@@ -60,6 +61,62 @@ void fwn_run_cond(const fwn_cond_plan& cp, const void* ca0, const void* ca1, con
             fwn_launch_cond(g ? ca1 : ca0, Wc0, P, (long)512 * kcpad, (long)M * 512, g, 2, (nflow - g + 1) / 2, L, M, cin, kcpad, Ppart,
                             pn, cp.nsplit, st);
     fwn_launch_cond_reduce(P, Ppart, pn, cp.nsplit, pn, st);
+}
+
+// ---- the ragged forward rules and the two stage walks of both sequencers (fwn_sequence.h) ----
+void ClipRows::zero(void* base, long rows, long row_bytes, int samples_per_row) const {
+    if (len) fwn_launch_mask_rows(base, B, rows, row_bytes, len, (int)B, samples_per_row, st);
+}
+void ClipRows::zero_planes(float* planes, long T) const { if (len) fwn_launch_mask_rows(planes, 2 * B, T / 2, 4, len, (int)B, 2, st); }
+void ClipRows::neg_shift(float* xa, long rows, int Ch, const float* shift) const {
+    if (len) fwn_launch_fill_neg_shift(xa, B, rows, Ch, shift, len, (int)B, 2 * Ch, st);
+}
+
+int fwn_run_upsample(const fwn_model_desc* m, long B, long T, const float* mel, const UpsampleBufs& u, const ClipRows& rows) {
+    const int nmel = 2 * (m->num_mels / 2);
+    int H = (int)(T / hop_of(m));
+    int spr = hop_of(m);                 // samples per row of the current stage's input
+    const float* in = mel;
+    if (rows.len) {
+        if (hipMemcpyAsync(u.mel_copy, mel, (size_t)B * H * nmel * 4, hipMemcpyDeviceToDevice, rows.st) != hipSuccess) return -1;
+        rows.zero(u.mel_copy, H, (long)nmel * 4, spr);
+        in = u.mel_copy;
+    }
+    for (int i = 0; i < m->n_up; ++i) {
+        const bool last = (i == m->n_up - 1);
+        float* outf = last ? nullptr : u.inner[i];
+        fwn_launch_upsample(in, (int)B, H, nmel, m->up_w[i], u.bias_dev ? 0.0f : m->up_bias[i], u.bias_dev ? u.bias_dev[i] : nullptr,
+                            m->up_scale[i], outf, last ? u.cplanes : nullptr, rows.st);
+        H *= m->up_scale[i];
+        spr /= m->up_scale[i];
+        if (!last) rows.zero(outf, H, (long)nmel * 4, spr);
+        in = outf;
+    }
+    return 0;
+}
+
+void fwn_run_stages(const fwn_flow_desc* d, const FlowStages& s, float* xa, const void* ca, const float* P, int M, int Ti, int inverse,
+                    const ClipRows& rows) {
+    hipStream_t st = rows.st;
+    // h rows past a clip's end are zeroed behind every kernel that writes h, so that the taps of the next one read what they
+    // read at the end of a clip on its own - and BEFORE h is kept (training's weight gradients read it)
+    if (!inverse) rows.neg_shift(xa, Ti, d->Ch, d->an);
+    if (!s.have_h0)
+        fwn_launch_front(xa, d->an, d->Wfront, d->Wfront2, d->bfront, s.h[0], s.front_scratch, M, Ti, d->Ch, d->kfpad, inverse ? 0 : 1,
+                         s.h8[0], st);
+    rows.zero(s.h[0], Ti, 512, 2 * d->Ch);
+    for (int l = 0; l < d->L; ++l) {
+        if (s.h8[l])
+            fwn_launch_gate_fp8(s.h8[l], ca, d->Wd8[l], d->wd8_exp[l], d->Wc[l], d->bgate[l], s.o[l], M, Ti, dilation_of(l), d->cin,
+                                d->kcpad, st);
+        else
+            fwn_launch_gate(s.h[l], ca, P ? P + (size_t)l * M * 512 : nullptr, d->Wd[l], d->Wc[l], s.gate_stream ? d->Wgs[l] : nullptr,
+                            d->bgate[l], s.o[l], M, Ti, dilation_of(l), d->cin, d->kcpad, s.aux[l], st);
+        if (l + 1 < d->L) {
+            fwn_launch_res(s.o[l], s.h[l], d->Wres[l], d->bres[l], s.h[l + 1], M, s.h8[l + 1], st);
+            rows.zero(s.h[l + 1], Ti, 512, 2 * d->Ch);
+        }
+    }
 }
 
 extern "C" {
@@ -238,12 +295,6 @@ int fwn_front(const fwn_flow_desc* d, const float* xa, void* h_out, void* scratc
     fwn_launch_front(xa, d->an, d->Wfront, d->Wfront2, d->bfront, h_out, scratch, M, Ti, d->Ch, d->kfpad, apply_an,
                      nullptr, (hipStream_t)stream);
     return check_launch("fwn_front");
-}
-
-static int dilation_of(int layer) {  // kernel_size ** n, modules.py:152
-    int dil = 1;
-    for (int i = 0; i < layer; ++i) dil *= 3;
-    return dil;
 }
 
 int fwn_gate(const fwn_flow_desc* d, int layer, const void* h, const void* ca, const float* P, void* o,
@@ -480,7 +531,6 @@ int fwn_tail_train(const fwn_flow_desc* d, const void* o, int64_t o_stride, floa
 
 int fwn_tail_partials(int M) { return M > 0 ? tail_partials_bound(M, false) : 0; }
 
-// ddi: 0 none, 1 local two-pass init, 2 moments -> reduce callback (may be NULL) -> tables
 // Chain context of one flow inside a whole-model call (NULL: a flow on its own, everything in place).
 struct FlowChain {
     float* xb_out;               // third plane buffer that receives out_b, or NULL (in place)
@@ -497,85 +547,82 @@ struct FlowRagged {
     double* acc;
     double* mom_part;
 };
+// One flow's run.  Zero-initialise, then set by name; what stays zero is absent.
+struct FlowRun {
+    const fwn_flow_desc* d;
+    int64_t B, T;
+    float* xa; float* xb;
+    const void* ca; const float* P;       // exactly one: fused conditioning plane / the flow's hoisted P
+    void* h0; void* h1; void* o;
+    float* partial;
+    int inverse;
+    int ddi;                               // 0 none, 1 local two-pass init, 2 moments -> reduce callback (may be NULL) -> tables
+    double* mom; fwn_reduce_fn reduce; void* user;
+    void* h8a; void* h8b;                  // e4m3 copies of h: the fp8 gate where the flow and the shape have one
+    FlowChain* chain;
+    unsigned* sync;                        // != NULL: the flow may run as ONE launch (flow_persist.h); zeroed by the caller
+    // ragged batch (whole-model passes only): the clips' lengths in samples, on the device; rg: forward passes
+    const int32_t* len;
+    const FlowRagged* rg;
+    void* stream;
+};
 
-static int flow_run_impl(const fwn_flow_desc* d, int64_t B, int64_t T, float* xa, float* xb, const void* ca,
-                         void* h0, void* h1, void* o, const float* P, float* partial, int inverse, int ddi,
-                         double* mom, fwn_reduce_fn reduce, void* user, void* h8a, void* h8b, FlowChain* chain, void* stream,
-                         unsigned* sync = nullptr, const int32_t* len = nullptr, const FlowRagged* rg = nullptr) {
+static int flow_run_impl(const FlowRun& a) {
+    const fwn_flow_desc* d = a.d;
+    FlowChain* chain = a.chain;
+    const int inverse = a.inverse;
     int rc = check_desc(d);
     if (rc) return rc;
-    REQUIRE(B > 0 && T > 0 && T % (2 * (int64_t)d->Ch) == 0, "fwn_flow_run: T=%lld not divisible by 2*Ch=%d",
-            (long long)T, 2 * d->Ch);
-    REQUIRE(B * T < ((int64_t)1 << 31) && (int64_t)d->L * (B * T / 2) * 512 < ((int64_t)1 << 31),
+    REQUIRE(a.B > 0 && a.T > 0 && a.T % (2 * (int64_t)d->Ch) == 0, "fwn_flow_run: T=%lld not divisible by 2*Ch=%d",
+            (long long)a.T, 2 * d->Ch);
+    REQUIRE(a.B * a.T < ((int64_t)1 << 31) && (int64_t)d->L * (a.B * a.T / 2) * 512 < ((int64_t)1 << 31),
             "fwn_flow_run: B*T too large (2 GiB per activation buffer)");
-    REQUIRE(xa && xb && h0 && h1 && o, "fwn_flow_run: null buffer");
-    REQUIRE((ca != nullptr) != (P != nullptr), "fwn_flow_run: exactly one of ca / P");
-    REQUIRE(!(ddi && inverse), "fwn_flow_run: data-dependent init runs in the forward direction only");
-    hipStream_t st = (hipStream_t)stream;
-    const int Ti = (int)(T / (2 * d->Ch));
-    const int M = (int)(B * Ti);
-    // ragged batch (len: the clips' lengths in samples, on the device): h rows past a clip's end are zeroed behind every
-    // kernel that writes h, so that the taps of the next one read what they read at the end of a clip on its own
-    REQUIRE(!len || (!sync && !h8a && !(chain && (chain->xb_out || chain->have_h0)) && (inverse ? !rg : rg && rg->z && rg->acc)),
-            "fwn_flow_run: lengths go with the plain stages only (forward: with the buffers of the per-clip log-det)");
-    REQUIRE(!len || !ddi || (ddi == 2 && rg && rg->mom_part),
-            "fwn_flow_run: with lengths the data-dependent init is the one of fwn_model_forward_init_ragged (masked moments)");
-    auto mask_h = [&](void* h) { if (len) fwn_launch_mask_rows(h, (long)B, Ti, 512, len, (int)B, 2 * d->Ch, st); };
-    if (ddi == 1) fwn_launch_ddi(xa, xb, M, d->Ch, d->an, st);
-    if (ddi == 2) {
-        REQUIRE(mom, "fwn_flow_run: no moment buffer");
+    REQUIRE(a.xa && a.xb && a.h0 && a.h1 && a.o, "fwn_flow_run: null buffer");
+    REQUIRE((a.ca != nullptr) != (a.P != nullptr), "fwn_flow_run: exactly one of ca / P");
+    REQUIRE(!(a.ddi && inverse), "fwn_flow_run: data-dependent init runs in the forward direction only");
+    hipStream_t st = (hipStream_t)a.stream;
+    const int Ti = (int)(a.T / (2 * d->Ch));
+    const int M = (int)(a.B * Ti);
+    const ClipRows rows{a.len, (long)a.B, st};
+    if (a.ddi == 1) fwn_launch_ddi(a.xa, a.xb, M, d->Ch, d->an, st);
+    if (a.ddi == 2) {
+        REQUIRE(a.mom, "fwn_flow_run: no moment buffer");
         // ragged: the clips' own rows only, and their number as the count - the planes hold zeros past a clip's end
-        // (mask_planes), which the plain kernel would add to the count
-        if (len) fwn_launch_ddi_moments_ragged(xa, xb, (long)B, Ti, d->Ch, len, 2 * d->Ch, mom, rg->mom_part, st);
-        else fwn_launch_ddi_moments(xa, xb, M, d->Ch, mom, st);
+        // (ClipRows::zero_planes), which the plain kernel would add to the count
+        if (a.len) fwn_launch_ddi_moments_ragged(a.xa, a.xb, (long)a.B, Ti, d->Ch, a.len, 2 * d->Ch, a.mom, a.rg->mom_part, st);
+        else fwn_launch_ddi_moments(a.xa, a.xb, M, d->Ch, a.mom, st);
         rc = check_launch("fwn_actnorm_moments");
         if (rc) return rc;
-        if (reduce && reduce(user, mom, 4 * d->Ch + 1, stream) != 0)
+        if (a.reduce && a.reduce(a.user, a.mom, 4 * d->Ch + 1, a.stream) != 0)
             return fail(FWN_ERR_ARG, "fwn_model_forward_init: the reduce callback failed");
-        fwn_launch_ddi_from_moments(mom, d->Ch, d->an, st);
+        fwn_launch_ddi_from_moments(a.mom, d->Ch, d->an, st);
     }
-    // fp8 dilated taps for layer l: e4m3 weights packed, the shape has an fp8 kernel, conditioning fused, and the
-    // producer of h (VALU front conv: Ch <= 16; res kernel) can write the e4m3 copy
-    auto fp8_layer = [&](int l) {
-        return h8a && h8b && ca && l < d->L && d->Wd8[l] && fwn_gate_fp8_ok(M, dilation_of(l)) && (l > 0 || d->Ch <= 16);
-    };
     // ---- the whole flow as ONE launch (flow_persist.h): small M, hoisted conditioning; `sync` zeroed by the caller ----
-    if (sync && P && !ddi && !(h8a && ca) && !(chain && (chain->have_h0 || chain->xb_out)) &&
-        fwn_flow_persist_ok(M, d->Ch, d->L, d->npt, d->Wfront2 != nullptr, ((uintptr_t)xa & 15) == 0)) {
+    if (a.sync && a.P && !a.ddi && !(a.h8a && a.ca) && !(chain && (chain->have_h0 || chain->xb_out)) &&
+        fwn_flow_persist_ok(M, d->Ch, d->L, d->npt, d->Wfront2 != nullptr, ((uintptr_t)a.xa & 15) == 0)) {
         const int inside = fwn_flow_persist_front_inside(d->Ch);
         if (!inside)
-            fwn_launch_front(xa, d->an, d->Wfront, d->Wfront2, d->bfront, h0, h1, M, Ti, d->Ch, d->kfpad, inverse ? 0 : 1, nullptr, st);
-        fwn_launch_flow_persist_desc(d, xa, xb, h0, h1, o, P, inverse ? nullptr : partial, sync, M, Ti, inverse, inside, st);
+            fwn_launch_front(a.xa, d->an, d->Wfront, d->Wfront2, d->bfront, a.h0, a.h1, M, Ti, d->Ch, d->kfpad, inverse ? 0 : 1, nullptr, st);
+        fwn_launch_flow_persist_desc(d, a.xa, a.xb, a.h0, a.h1, a.o, a.P, inverse ? nullptr : a.partial, a.sync, M, Ti, inverse, inside, st);
         if (chain) { chain->h0_next = nullptr; chain->n_partial = fwn_tail_slots(fwn_tail_form(M, d->L, d->Ch, d->npt, false), M, false); }
         return check_launch("fwn_flow_run_persist");
     }
-    void* h8c = h8a;
-    void* h8n = h8b;
-    // ragged forward: the front conv applies ActNorm on the fly, (v + shift) * scale - with -shift in the rows past a clip's
-    // end it reads exact zeros there, the padding a clip on its own gets behind ActNorm (the tail then leaves ActNorm(x_a) = 0
-    // in those rows by itself)
-    if (len && !inverse) fwn_launch_fill_neg_shift(xa, (long)B, Ti, d->Ch, d->an, len, (int)B, 2 * d->Ch, st);
-    if (!(chain && chain->have_h0))
-        fwn_launch_front(xa, d->an, d->Wfront, d->Wfront2, d->bfront, h0, h1, M, Ti, d->Ch, d->kfpad, inverse ? 0 : 1,
-                         fp8_layer(0) ? h8c : nullptr, st);
-    mask_h(h0);
-    void* hc = h0;
-    void* hn = h1;
+    // the stages up to the last gate over the h0 / h1 ping-pong and o [L][M][256]; the front conv's scratch is h1
+    FlowStages sg;
+    memset(&sg, 0, sizeof(sg));
     for (int l = 0; l < d->L; ++l) {
-        void* ol = (char*)o + (size_t)l * M * 256 * 2;
-        if (fp8_layer(l))
-            fwn_launch_gate_fp8(h8c, ca, d->Wd8[l], d->wd8_exp[l], d->Wc[l], d->bgate[l], ol, M, Ti, dilation_of(l), d->cin,
-                                d->kcpad, st);
-        else
-            fwn_launch_gate(hc, ca, P ? P + (size_t)l * M * 512 : nullptr, d->Wd[l], d->Wc[l], d->Wgs[l], d->bgate[l], ol, M,
-                            Ti, dilation_of(l), d->cin, d->kcpad, nullptr, st);
-        if (l + 1 < d->L) {
-            fwn_launch_res(ol, hc, d->Wres[l], d->bres[l], hn, M, fp8_layer(l + 1) ? h8n : nullptr, st);
-            mask_h(hn);
-            void* t = hc; hc = hn; hn = t;
-            t = h8c; h8c = h8n; h8n = t;
-        }
+        sg.h[l] = (l & 1) ? a.h1 : a.h0;
+        sg.o[l] = (char*)a.o + (size_t)l * M * 256 * 2;
+        // fp8 dilated taps for layer l: e4m3 weights packed, the shape has an fp8 kernel, conditioning fused, and the
+        // producer of h (VALU front conv: Ch <= 16; res kernel) can write the e4m3 copy
+        if (a.h8a && a.h8b && a.ca && d->Wd8[l] && fwn_gate_fp8_ok(M, dilation_of(l)) && (l > 0 || d->Ch <= 16)) sg.h8[l] = (l & 1) ? a.h8b : a.h8a;
     }
+    sg.gate_stream = true;
+    sg.front_scratch = a.h1;
+    sg.have_h0 = chain && chain->have_h0;
+    fwn_run_stages(d, sg, a.xa, a.ca, a.P, M, Ti, inverse, rows);
+    void* hc = sg.h[d->L - 1];                          // the last gate's input
+    void* hn = hc == a.h0 ? a.h1 : a.h0;
     // both h buffers are free once the last gate has run: the N-split tail (small M) keeps S and U there
     fwn_tail_chain tc;
     memset(&tc, 0, sizeof(tc));
@@ -591,26 +638,37 @@ static int flow_run_impl(const fwn_flow_desc* d, int64_t B, int64_t T, float* xa
         chain->n_partial = fwn_tail_slots(desc_tail(d, M), M, tc.h0_next != nullptr);
     }
     // ragged forward: the saving tail (fwn_tail_train's), S and U parked in the two free h buffers, Z kept for the per-clip sums
-    if (rg) { tc.save_s = hn; tc.save_u = hc; tc.save_z = rg->z; }
-    fwn_launch_tail(o, (long)M * 256, d->L, d->Wskip, d->bskip, d->Wfinal, d->bfinal, d->Wzero, d->bzero,
-                    d->ezero, d->an, xa, xb, inverse ? nullptr : partial, M, d->Ch, d->npt, inverse, hn, hc, (chain || rg) ? &tc : nullptr,
+    if (a.rg) { tc.save_s = hn; tc.save_u = hc; tc.save_z = a.rg->z; }
+    fwn_launch_tail(a.o, (long)M * 256, d->L, d->Wskip, d->bskip, d->Wfinal, d->bfinal, d->Wzero, d->bzero,
+                    d->ezero, d->an, a.xa, a.xb, inverse ? nullptr : a.partial, M, d->Ch, d->npt, inverse, hn, hc, (chain || a.rg) ? &tc : nullptr,
                     d->Wts, st);
-    if (rg) fwn_launch_ragged_logdet(rg->z, (long)B, Ti, d->Ch, d->ezero, d->an, len, (int)B, 2 * d->Ch, rg->acc, st);
+    if (a.rg) fwn_launch_ragged_logdet(a.rg->z, (long)a.B, Ti, d->Ch, d->ezero, d->an, a.len, (int)a.B, 2 * d->Ch, a.rg->acc, st);
     return check_launch("fwn_flow_run");
 }
 
+// the arguments the three single-flow entry points share
+static FlowRun flow_run_args(const fwn_flow_desc* d, int64_t B, int64_t T, float* xa, float* xb, void* h0, void* h1, void* o, const float* P,
+                             float* partial, int inverse, void* stream) {
+    FlowRun a;
+    memset(&a, 0, sizeof(a));
+    a.d = d; a.B = B; a.T = T; a.xa = xa; a.xb = xb; a.h0 = h0; a.h1 = h1; a.o = o; a.P = P; a.partial = partial; a.inverse = inverse;
+    a.stream = stream;
+    return a;
+}
 int fwn_flow_run(const fwn_flow_desc* d, int64_t B, int64_t T, float* xa, float* xb, const void* ca,
                  void* h0, void* h1, void* o, const float* P, float* partial, int inverse, int ddi,
                  void* stream) {
-    return flow_run_impl(d, B, T, xa, xb, ca, h0, h1, o, P, partial, inverse, ddi ? 1 : 0, nullptr, nullptr, nullptr, nullptr,
-                         nullptr, nullptr, stream);
+    FlowRun a = flow_run_args(d, B, T, xa, xb, h0, h1, o, P, partial, inverse, stream);
+    a.ca = ca; a.ddi = ddi ? 1 : 0;
+    return flow_run_impl(a);
 }
 int fwn_flow_run_fp8(const fwn_flow_desc* d, int64_t B, int64_t T, float* xa, float* xb, const void* ca,
                      void* h0, void* h1, void* o, const float* P, float* partial, int inverse, int ddi,
                      void* h8a, void* h8b, void* stream) {
     REQUIRE(h8a && h8b && ALIGNED16(h8a) && ALIGNED16(h8b), "fwn_flow_run_fp8: h8 scratch buffers (16-byte aligned) required");
-    return flow_run_impl(d, B, T, xa, xb, ca, h0, h1, o, P, partial, inverse, ddi ? 1 : 0, nullptr, nullptr, nullptr, h8a, h8b,
-                         nullptr, stream);
+    FlowRun a = flow_run_args(d, B, T, xa, xb, h0, h1, o, P, partial, inverse, stream);
+    a.ca = ca; a.ddi = ddi ? 1 : 0; a.h8a = h8a; a.h8b = h8b;
+    return flow_run_impl(a);
 }
 
 int fwn_flow_persist_supported(const fwn_flow_desc* d, int64_t B, int64_t T) {
@@ -625,8 +683,9 @@ int fwn_flow_run_persist(const fwn_flow_desc* d, int64_t B, int64_t T, float* xa
     REQUIRE(d && sync && P, "fwn_flow_run_persist: null pointer");
     REQUIRE(fwn_flow_persist_supported(d, B, T) && (((uintptr_t)xa) & 15) == 0,
             "fwn_flow_run_persist: this flow / shape has no one-launch form (fwn_flow_persist_supported)");
-    return flow_run_impl(d, B, T, xa, xb, nullptr, h0, h1, o, P, partial, inverse, 0, nullptr, nullptr, nullptr, nullptr, nullptr,
-                         nullptr, stream, (unsigned*)sync);
+    FlowRun a = flow_run_args(d, B, T, xa, xb, h0, h1, o, P, partial, inverse, stream);
+    a.sync = (unsigned*)sync;
+    return flow_run_impl(a);
 }
 int fwn_flow_persist_status(const void* sync, void* stream) {
     REQUIRE(sync, "fwn_flow_persist_status: null pointer");
@@ -921,12 +980,6 @@ static bool persist_block(const fwn_model_desc* m, const BlockPlan& b, const fwn
     return b.cond.hoist && fwn_flow_persist_ok((int)b.M, d->Ch, d->L, d->npt, d->Wfront2 != nullptr, true);
 }
 
-static int hop_of(const fwn_model_desc* m) {
-    int hop = 1;
-    for (int i = 0; i < m->n_up; ++i) hop *= m->up_scale[i];
-    return hop;
-}
-
 static int check_model(const fwn_model_desc* m, int64_t B, int64_t T) {
     REQUIRE(m && m->flows, "model desc is null");
     REQUIRE(m->n_block >= 1 && m->n_block <= 16 && m->n_flow >= 1 && m->n_layer >= 1 &&
@@ -990,11 +1043,10 @@ struct Carve {
     BlockPlan blk[16];
 };
 
-// ragged: a pass with per-clip lengths - every flow a launch per stage (the zero-fills of model_pass run between the
-// stages; the chained front conv reads out_b rows inside the launch that writes them), plus a copy of the mel to mask
-// ragged_fwd: a ragged forward pass - also one flow's Z (reused by the next flow) and every flow's per-clip log-det sums
-// ragged_init: a ragged init pass - also the chunk sums of one flow's masked moments (reused by the next flow)
-static Carve carve(const fwn_model_desc* m, int64_t B, int64_t T, bool ragged = false, bool ragged_fwd = false, bool ragged_init = false) {
+// The layout of a pass of kind k (pass_traits: what a pass with per-clip lengths adds, behind everything else - the plain
+// passes all share one layout).
+static Carve carve(const fwn_model_desc* m, int64_t B, int64_t T, PassKind k) {
+    const PassTraits pt = pass_traits(k);
     Carve c;
     size_t off = 0;
     const size_t half = m->num_mels / 2;
@@ -1016,8 +1068,8 @@ static Carve carve(const fwn_model_desc* m, int64_t B, int64_t T, bool ragged = 
         const fwn_flow_desc* f0 = &m->flows[i * m->n_flow];
         b.M = B * T / ((int64_t)2 << i);
         b.cond = fwn_plan_cond(hoist_cond(m, b.M, f0->cin), (int)b.M, m->n_flow, m->n_layer, f0->cin, f0->kcpad, m->cond_stream[i]);
-        b.one_launch = !ragged && persist_block(m, b, f0);
-        b.chained = !ragged && m->chain_mode != 1;
+        b.one_launch = !pt.ragged && persist_block(m, b, f0);
+        b.chained = !pt.ragged && m->chain_mode != 1;
         b.slots = fwn_tail_partials_chained((int)b.M, f0->Ch, 1);       // chained with a front conv: the most tiles
         if (b.cond.hoist) {
             const size_t need = (size_t)m->n_flow * m->n_layer * b.M * 512 * 4;
@@ -1040,11 +1092,11 @@ static Carve carve(const fwn_model_desc* m, int64_t B, int64_t T, bool ragged = 
     c.h8b = off; off = align_up(off + (m->gate_fp8 ? Mmax * 256 : 0));
     c.sync_bytes = c.sync_stride * (size_t)m->n_block * m->n_flow;
     c.sync = off; off = align_up(off + c.sync_bytes);
-    c.mel = off; off = align_up(off + (ragged ? (size_t)B * (T / hop_of(m)) * m->num_mels * 4 : 0));
-    c.zsave = off; off = align_up(off + (ragged_fwd ? (size_t)B * T * 4 : 0));          // [M][2 Ch] fp32 = B T floats at every block
-    c.acc = off; off = align_up(off + (ragged_fwd ? (size_t)m->n_block * m->n_flow * B * fwn_ragged_logdet_nslot((long)B) * 8 : 0));
+    c.mel = off; off = align_up(off + (pt.ragged ? (size_t)B * (T / hop_of(m)) * m->num_mels * 4 : 0));
+    c.zsave = off; off = align_up(off + (pt.logdet ? (size_t)B * T * 4 : 0));          // [M][2 Ch] fp32 = B T floats at every block
+    c.acc = off; off = align_up(off + (pt.logdet ? (size_t)m->n_block * m->n_flow * B * fwn_ragged_logdet_nslot((long)B) * 8 : 0));
     size_t mp = 0;
-    for (int i = 0; ragged_init && i < m->n_block; ++i) {
+    for (int i = 0; pt.mompart && i < m->n_block; ++i) {
         const size_t need = (size_t)fwn_ragged_moments_nslot((long)B, (long)(T >> (i + 1)), 1 << i) * (4 << i) * 8;
         if (need > mp) mp = need;
     }
@@ -1055,46 +1107,19 @@ static Carve carve(const fwn_model_desc* m, int64_t B, int64_t T, bool ragged = 
 
 size_t fwn_workspace_bytes(const fwn_model_desc* m, int64_t B, int64_t T) {
     if (check_model(m, B, T) != FWN_OK) return 0;
-    return carve(m, B, T).total;
+    return carve(m, B, T, PASS_FORWARD).total;
 }
 size_t fwn_ragged_workspace_bytes(const fwn_model_desc* m, int64_t B, int64_t T) {
     if (check_model(m, B, T) != FWN_OK) return 0;
-    return carve(m, B, T, true).total;
+    return carve(m, B, T, PASS_REVERSE_RAGGED).total;
 }
 size_t fwn_ragged_forward_workspace_bytes(const fwn_model_desc* m, int64_t B, int64_t T) {
     if (check_model(m, B, T) != FWN_OK || B >= 32768) return 0;
-    return carve(m, B, T, true, true).total;
+    return carve(m, B, T, PASS_FORWARD_RAGGED).total;
 }
 size_t fwn_ragged_init_workspace_bytes(const fwn_model_desc* m, int64_t B, int64_t T) {
     if (check_model(m, B, T) != FWN_OK || B >= 32768 || m->gate_fp8) return 0;
-    return carve(m, B, T, true, true, true).total;
-}
-
-// len (ragged batch): the stages run on a copy of the mel with the frames past each clip's end zeroed, and so is every inner
-// stage's output - the transposed conv of the next stage reads one row across a clip's end.  The last stage's rows past the
-// end stay as they come out: the conditioning is pointwise in time.
-static int run_upsample(const fwn_model_desc* m, int64_t B, int64_t T, const float* mel, char* ws,
-                        const Carve& c, hipStream_t st, const int32_t* len) {
-    int H = (int)(T / hop_of(m));
-    int spr = hop_of(m);                 // samples per row of the current stage's input
-    const float* in = mel;
-    if (len) {
-        float* mc = (float*)(ws + c.mel);
-        if (hipMemcpyAsync(mc, mel, (size_t)B * H * m->num_mels * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return -1;
-        fwn_launch_mask_rows(mc, (long)B, H, (long)m->num_mels * 4, len, (int)B, spr, st);
-        in = mc;
-    }
-    for (int i = 0; i < m->n_up; ++i) {
-        const bool last = (i == m->n_up - 1);
-        float* outf = last ? nullptr : (float*)(ws + ((i & 1) ? c.up1 : c.up0));
-        fwn_launch_upsample(in, (int)B, H, m->num_mels, m->up_w[i], m->up_bias[i], nullptr, m->up_scale[i], outf,
-                            last ? (void*)(ws + c.cplanes) : nullptr, st);
-        H *= m->up_scale[i];
-        spr /= m->up_scale[i];
-        if (len && !last) fwn_launch_mask_rows(outf, (long)B, H, (long)m->num_mels * 4, len, (int)B, spr, st);
-        in = outf;
-    }
-    return 0;
+    return carve(m, B, T, PASS_INIT_RAGGED).total;
 }
 
 static int check_block_contiguity(const fwn_model_desc* m, int blk) {
@@ -1139,7 +1164,7 @@ int fwn_model_persist_status(const fwn_model_desc* m, int64_t B, int64_t T, cons
     int rc = check_model(m, B, T);
     if (rc) return rc;
     REQUIRE(workspace, "fwn_model_persist_status: null workspace");
-    const Carve c = carve(m, B, T);
+    const Carve c = carve(m, B, T, PASS_FORWARD);
     if (!c.sync_bytes) return 0;
     const int nf = m->n_block * m->n_flow;
     unsigned w[1024];
@@ -1158,26 +1183,28 @@ int fwn_model_persist_status(const fwn_model_desc* m, int64_t B, int64_t T, cons
 // moments -> reduce callback), and ends in the prior.  Reverse: both orders backwards, the parity flipped before each flow
 // (model.py:199); it ends in the merge of the planes into x_out.  A block's plan (carve) decides its conditioning launch and
 // whether its flows run as one launch each; the init pass runs no flow as one launch, but zeroes the sync region all the same.
-// len: a ragged batch - the same stages under the plan of carve(.., ragged), with the rows past each clip's end zeroed wherever
-// a later stage reads across it: mel and inner up-sampling stages, planes, h (flow_run_impl), and x_out.  Forward with len:
-// no init; every flow's x_a plane gets -shift in those rows before its front conv and its tail keeps Z (flow_run_impl), the
-// per-clip log-det sums of all flows and the per-clip prior end in out2 [2][B] (the tails' own partials are ignored).
-// ragged_init (fwn_model_forward_init_ragged only): that pass with init 2 - every flow's moments over the clips' own rows.
-static int model_pass(const fwn_model_desc* m, int64_t B, int64_t T, const float* in, const float* mel, void* workspace,
-                      size_t workspace_bytes, bool reverse, int init, fwn_reduce_fn reduce, void* user, float* out2, float* z_planes,
-                      float* x_out, void* stream, const int32_t* len = nullptr, bool ragged_init = false) {
-    const char* what = len ? (reverse ? "fwn_model_reverse_ragged" : ragged_init ? "fwn_model_forward_init_ragged" : "fwn_model_forward_ragged")
-                           : reverse ? "fwn_model_reverse" : "fwn_model_forward";
+// kind (fwn_sequence.h) names the entry point; pass_traits gives its direction, its init and what per-clip lengths add.
+// A ragged pass (len): the same stages under the plan of carve(.., kind), with the rows past each clip's end zeroed wherever
+// a later stage reads across it: mel and inner up-sampling stages (fwn_run_upsample), planes, h (fwn_run_stages), and x_out.
+// Forward with len: every flow's x_a plane gets -shift in those rows before its front conv and its tail keeps Z (flow_run_impl),
+// the per-clip log-det sums of all flows and the per-clip prior end in out2 [2][B] (the tails' own partials are ignored).
+// PASS_INIT_RAGGED: that pass with init 2 - every flow's moments over the clips' own rows.
+static int model_pass(PassKind kind, const fwn_model_desc* m, int64_t B, int64_t T, const float* in, const float* mel, const int32_t* len,
+                      void* workspace, size_t workspace_bytes, fwn_reduce_fn reduce, void* user, float* out2, float* z_planes, float* x_out,
+                      void* stream) {
+    const PassTraits pt = pass_traits(kind);
+    const char* what = pt.what;
+    const bool reverse = pt.reverse;
+    const int init = pt.init;
     int rc = check_model(m, B, T);
     if (rc) return rc;
     REQUIRE(in && mel && workspace && (reverse ? x_out : out2), "%s: null pointer", what);
     REQUIRE((((uintptr_t)workspace) & 255) == 0, "workspace must be 256-byte aligned");
     REQUIRE(!reverse || ((m->n_block * m->n_flow) & 1) == 0,
             "reverse with odd n_block*n_flow ends in swapped channel order (model.py:199,254); unsupported");
-    REQUIRE(!len || (!m->gate_fp8 && (ragged_init ? init == 2 && !reverse : !init)),
+    REQUIRE(!pt.ragged || !m->gate_fp8,
             "%s: per-clip lengths go with a model without fp8 gates (its e4m3 copies of h are not masked) and without the data-dependent init", what);
-    REQUIRE(len || !ragged_init, "%s: null lengths", what);
-    const Carve c = carve(m, B, T, len != nullptr, len && !reverse, ragged_init);
+    const Carve c = carve(m, B, T, kind);
     if (workspace_bytes < c.total)
         return fail(FWN_ERR_WORKSPACE, "workspace %zu < required %zu bytes", workspace_bytes, c.total);
     hipStream_t st = (hipStream_t)stream;
@@ -1189,13 +1216,20 @@ static int model_pass(const fwn_model_desc* m, int64_t B, int64_t T, const float
     float* planes = (float*)(ws + c.planes);
     const int nf = m->n_flow, L = m->n_layer;
 
-    if (run_upsample(m, B, T, mel, ws, c, st, len)) return fail(FWN_ERR_HIP, "%s: mel copy failed", what);
+    const ClipRows rows{len, (long)B, st};
+    {
+        UpsampleBufs u;
+        memset(&u, 0, sizeof(u));
+        u.mel_copy = (float*)(ws + c.mel);
+        for (int i = 0; i + 1 < m->n_up; ++i) u.inner[i] = (float*)(ws + ((i & 1) ? c.up1 : c.up0));
+        u.cplanes = ws + c.cplanes;
+        if (fwn_run_upsample(m, (long)B, (long)T, mel, u, rows)) return fail(FWN_ERR_HIP, "%s: mel copy failed", what);
+    }
     fwn_launch_split(in, B, T, planes, st);   // (reverse: the n_block pre-squeezes of model.py:374-392 are index math)
     // ragged batch: both planes hold clip b's samples at [b][0, len / 2) at every block (a row of block i is 2^i of them, and
     // len is a multiple of 2^n_block); the rest is zeroed here and behind every flow (ActNorm^-1 and the coupling leave -b
     // and t there, and the next front conv reads one row across the clip's end)
-    auto mask_planes = [&]() { if (len) fwn_launch_mask_rows(planes, 2 * (long)B, (long)(T / 2), 4, len, (int)B, 2, st); };
-    mask_planes();
+    rows.zero_planes(planes, (long)T);
     if (c.sync_bytes && hipMemsetAsync(ws + c.sync, 0, c.sync_bytes, st) != hipSuccess)
         return fail(FWN_ERR_HIP, "%s: hipMemsetAsync failed", what);
     int p = 0;
@@ -1230,12 +1264,20 @@ static int model_pass(const fwn_model_desc* m, int64_t B, int64_t T, const float
             unsigned* sync = (!init && b.one_launch) ? (unsigned*)(ws + c.sync + (size_t)(i * nf + j) * c.sync_stride) : nullptr;
             FlowChain ch = flow_chain(m, d, next, M, init != 0, pl.spare, have_h0, b.chained && !sync);
             const FlowRagged rg{(float*)(ws + c.zsave), (double*)(ws + c.acc) + (size_t)(i * nf + j) * B * fwn_ragged_logdet_nslot((long)B),
-                                ragged_init ? (double*)(ws + c.mompart) : nullptr};
-            rc = flow_run_impl(d, B, T, pl.at[p], pl.at[p ^ 1], ca, hA, hB, ws + c.o, P, reverse ? nullptr : partial + poff, reverse, init,
-                               mom, reduce, user, m->gate_fp8 ? ws + c.h8a : nullptr, m->gate_fp8 ? ws + c.h8b : nullptr, &ch, stream, sync, len,
-                               len && !reverse ? &rg : nullptr);
+                                pt.mompart ? (double*)(ws + c.mompart) : nullptr};
+            FlowRun fr;
+            memset(&fr, 0, sizeof(fr));
+            fr.d = d; fr.B = B; fr.T = T; fr.xa = pl.at[p]; fr.xb = pl.at[p ^ 1]; fr.ca = ca; fr.P = P;
+            fr.h0 = hA; fr.h1 = hB; fr.o = ws + c.o;
+            fr.partial = reverse ? nullptr : partial + poff;
+            fr.inverse = reverse; fr.ddi = init; fr.mom = mom; fr.reduce = reduce; fr.user = user;
+            if (m->gate_fp8) { fr.h8a = ws + c.h8a; fr.h8b = ws + c.h8b; }
+            fr.chain = &ch; fr.sync = sync; fr.len = len;
+            if (pt.logdet) fr.rg = &rg;
+            fr.stream = stream;
+            rc = flow_run_impl(fr);
             if (rc) return rc;
-            mask_planes();
+            rows.zero_planes(planes, (long)T);
             if (!reverse) poff += ch.n_partial;
             planes_after_flow(pl, p, ch.xb_out != nullptr);
             have_h0 = ch.h0_next != nullptr;
@@ -1247,7 +1289,7 @@ static int model_pass(const fwn_model_desc* m, int64_t B, int64_t T, const float
     if (planes_go_home(pl, plane_elems * 4, st)) return fail(FWN_ERR_HIP, "%s: plane copy failed", what);
     if (reverse) {
         fwn_launch_merge(planes, B, T, x_out, st);
-        if (len) fwn_launch_mask_rows(x_out, (long)B, (long)T, 4, len, (int)B, 1, st);
+        rows.zero(x_out, (long)T, 4, 1);
     } else {
         if (len) fwn_launch_ragged_finish(planes, (long)B, (long)T, (const double*)(ws + c.acc), m->n_block * nf, nf, len, out2, st);
         else fwn_launch_prior(planes, (long)(B * T), partial, poff, 1.0 / (double)(B * T), out2, st);
@@ -1262,30 +1304,32 @@ static int model_pass(const fwn_model_desc* m, int64_t B, int64_t T, const float
 int fwn_model_forward(const fwn_model_desc* m, int64_t B, int64_t T, const float* x, const float* mel,
                       void* workspace, size_t workspace_bytes, float* out2, float* z_planes, int init,
                       void* stream) {
-    return model_pass(m, B, T, x, mel, workspace, workspace_bytes, false, init ? 1 : 0, nullptr, nullptr, out2, z_planes, nullptr,
-                      stream);
+    return model_pass(init ? PASS_FORWARD_DDI : PASS_FORWARD, m, B, T, x, mel, nullptr, workspace, workspace_bytes, nullptr, nullptr, out2,
+                      z_planes, nullptr, stream);
 }
 int fwn_model_forward_init(const fwn_model_desc* m, int64_t B, int64_t T, const float* x, const float* mel,
                            void* workspace, size_t workspace_bytes, float* out2, float* z_planes,
                            fwn_reduce_fn reduce, void* user, void* stream) {
-    return model_pass(m, B, T, x, mel, workspace, workspace_bytes, false, 2, reduce, user, out2, z_planes, nullptr, stream);
+    return model_pass(PASS_FORWARD_INIT, m, B, T, x, mel, nullptr, workspace, workspace_bytes, reduce, user, out2, z_planes, nullptr, stream);
 }
 
 int fwn_model_reverse(const fwn_model_desc* m, int64_t B, int64_t T, const float* z, const float* mel,
                       void* workspace, size_t workspace_bytes, float* x_out, void* stream) {
-    return model_pass(m, B, T, z, mel, workspace, workspace_bytes, true, 0, nullptr, nullptr, nullptr, nullptr, x_out, stream);
+    return model_pass(PASS_REVERSE, m, B, T, z, mel, nullptr, workspace, workspace_bytes, nullptr, nullptr, nullptr, nullptr, x_out, stream);
 }
 int fwn_model_reverse_ragged(const fwn_model_desc* m, int64_t B, int64_t T, const float* z, const float* mel, const int32_t* len_dev,
                              void* workspace, size_t workspace_bytes, float* x_out, void* stream) {
     REQUIRE(len_dev, "fwn_model_reverse_ragged: null lengths");
     REQUIRE(B < 32768, "fwn_model_reverse_ragged: B=%lld clips (at most 32767 per call)", (long long)B);
-    return model_pass(m, B, T, z, mel, workspace, workspace_bytes, true, 0, nullptr, nullptr, nullptr, nullptr, x_out, stream, len_dev);
+    return model_pass(PASS_REVERSE_RAGGED, m, B, T, z, mel, len_dev, workspace, workspace_bytes, nullptr, nullptr, nullptr, nullptr, x_out,
+                      stream);
 }
 int fwn_model_forward_ragged(const fwn_model_desc* m, int64_t B, int64_t T, const float* x, const float* mel, const int32_t* len_dev,
                              void* workspace, size_t workspace_bytes, float* out2B, float* z_planes, void* stream) {
     REQUIRE(len_dev, "fwn_model_forward_ragged: null lengths");
     REQUIRE(B < 32768, "fwn_model_forward_ragged: B=%lld clips (at most 32767 per call)", (long long)B);
-    return model_pass(m, B, T, x, mel, workspace, workspace_bytes, false, 0, nullptr, nullptr, out2B, z_planes, nullptr, stream, len_dev);
+    return model_pass(PASS_FORWARD_RAGGED, m, B, T, x, mel, len_dev, workspace, workspace_bytes, nullptr, nullptr, out2B, z_planes, nullptr,
+                      stream);
 }
 
 int fwn_model_forward_init_ragged(const fwn_model_desc* m, int64_t B, int64_t T, const float* x, const float* mel, const int32_t* len_dev,
@@ -1293,7 +1337,7 @@ int fwn_model_forward_init_ragged(const fwn_model_desc* m, int64_t B, int64_t T,
                                   void* stream) {
     REQUIRE(len_dev, "fwn_model_forward_init_ragged: null lengths");
     REQUIRE(B < 32768, "fwn_model_forward_init_ragged: B=%lld clips (at most 32767 per call)", (long long)B);
-    return model_pass(m, B, T, x, mel, workspace, workspace_bytes, false, 2, reduce, user, out2B, z_planes, nullptr, stream, len_dev, true);
+    return model_pass(PASS_INIT_RAGGED, m, B, T, x, mel, len_dev, workspace, workspace_bytes, reduce, user, out2B, z_planes, nullptr, stream);
 }
 
 }  // extern "C"

@@ -15,6 +15,7 @@
 #include "../../include/fwn.h"
 #include "common.h"
 #include "fwn_internal.h"
+#include "fwn_sequence.h"
 
 int fwn_set_error(int code, const char* fmt, ...);      // api.hip: thread-local message of fwn_last_error()
 #define TREQUIRE(cond, ...) do { if (!(cond)) return fwn_set_error(FWN_ERR_ARG, __VA_ARGS__); } while (0)
@@ -26,9 +27,6 @@ constexpr float SQH = 0.70710678118654752440f;          // sqrt(1/2), modules.py
 // ---- small kernels that replace the host-framework tensor ops of the Python sequencing -----------------------------
 __global__ __launch_bounds__(256) void scale_copy_kernel(float* __restrict__ dst, const float* __restrict__ src, long n, float s) {
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) dst[i] = (src[i] + 0.0f) * s;
-}
-__global__ __launch_bounds__(256) void cast_bf16_kernel(bf16* __restrict__ dst, const float* __restrict__ src, long n) {
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) dst[i] = (bf16)src[i];
 }
 // mel planes [2][B][T][half] -> rows [B][T][2 half]: the gradient image (fp32) and the up-sampled conditioning (bf16 -> fp32)
 __global__ __launch_bounds__(256) void planes_to_rows_kernel(const float* __restrict__ dplanes, const bf16* __restrict__ cplanes,
@@ -98,9 +96,6 @@ struct Bump {
         return p;
     }
 };
-inline long roundup(long v, long m) { return (v + m - 1) / m * m; }
-inline int dilation_of(int layer) { int d = 1; for (int i = 0; i < layer; ++i) d *= 3; return d; }
-inline int hop_of(const fwn_model_desc* m) { int h = 1; for (int i = 0; i < m->n_up; ++i) h *= m->up_scale[i]; return h; }
 
 // Fork / join markers of the side stream: created on first use (the eager first call), reused by every later call - a
 // recorded call creates nothing.  One pool per host thread and device.
@@ -124,14 +119,6 @@ EventPool* event_pool() {
 }
 
 struct TnSpec { int kx, n, ntap; };
-inline int tn_group_splits(const TnSpec* sp, int n, int m) {          // training.tn_group_splits
-    const int e = fwn_tn_tile(m);
-    long tiles = 0;
-    for (int i = 0; i < n; ++i) tiles += (long)sp[i].ntap * ((sp[i].kx + e - 1) / e) * ((sp[i].n + e - 1) / e);
-    const long a = (m + 63) / 64, b = 256 / (tiles > 1 ? tiles : 1);
-    const long r = a < b ? a : b;
-    return (int)(r < 1 ? 1 : r);
-}
 
 // Round 4: the split count of a flow's weight-gradient GEMMs is planned for its BLOCK - with a side stream the groups of all
 // n_flow flows of a block run as one launch (fwn_tn_multi_launch), and the one-stream path uses the same count so that both
@@ -209,7 +196,8 @@ long tn_partial_floats(const fwn_model_desc* md, int i, long m) {
     return tot * md->n_flow;
 }
 
-void plan(const fwn_train_desc* t, long B, long T, void* ws, Plan& pl, bool ragged = false) {
+// kind: PASS_TRAIN or PASS_TRAIN_RAGGED (what the ragged step adds lies behind everything else)
+void plan(const fwn_train_desc* t, long B, long T, void* ws, Plan& pl, PassKind kind) {
     const fwn_model_desc* md = t->model;
     const int L = md->n_layer, half = md->num_mels / 2, nmel = 2 * half;
     Bump b(ws);
@@ -308,16 +296,15 @@ void plan(const fwn_train_desc* t, long B, long T, void* ws, Plan& pl, bool ragg
     // up-sampling backward
     pl.up_dy = (float*)b.take((size_t)B * T * nmel * 4);
     pl.up_y = (float*)b.take((size_t)B * T * nmel * 4);
-    long Hs = T;
     int smax = 2;
     for (int n = 0; n < md->n_up; ++n) smax = md->up_scale[n] > smax ? md->up_scale[n] : smax;
-    for (int k = 0; k < 2; ++k) { pl.up_dx[k] = (float*)b.take((size_t)B * (T / md->up_scale[md->n_up - 1]) * nmel * 4); (void)Hs; }
+    for (int k = 0; k < 2; ++k) { pl.up_dx[k] = (float*)b.take((size_t)B * (T / md->up_scale[md->n_up - 1]) * nmel * 4); }
     pl.up_dwb = (float*)b.take((size_t)(6 * smax + 1) * 4);
     pl.up_scr = (float*)b.take((size_t)64 * (6 * smax + 1) * 4);
     pl.up_g3 = (float*)b.take(16);
     pl.up_dv = (float*)b.take((size_t)2 * smax * 3 * 4);
     pl.up_dg3 = (float*)b.take(16);
-    if (ragged) {
+    if (pass_traits(kind).ragged) {
         pl.melc = (float*)b.take((size_t)B * (T / hop_of(md)) * nmel * 4);
         pl.acc = (double*)b.take((size_t)md->n_block * md->n_flow * B * fwn_ragged_logdet_nslot(B) * 8);
         pl.out2B = (float*)b.take((size_t)2 * B * 4);
@@ -353,142 +340,201 @@ struct TnList {
 };
 struct WnItem { int tn; const float* part_direct; int part_nsplit; long part_stride; int part_rows, part_ld;   // tn < 0: part_direct
                  const fwn_conv_grad* c; int k, n, col0; float scale; const int32_t* row_src; const int32_t* col_src; };
+// The weight gradients of one flow, collected by its data-gradient chain and enqueued behind it (or on the side stream)
+struct Deferred {
+    TnList tn; WnItem wn[4 + 7 * FWN_MAX_LAYERS]; int nwn; long m, ti; int ch, i; const BwdSet* w;
+    const fwn_flow_train_desc* td;
+    const float* an;                                   // the flow's ActNorm table (totals of the small gradients)
+    fwn_gemm_desc dca[FWN_MAX_LAYERS]; int ndca;      // conditioning-gradient GEMMs (accumulate into the mel image: order kept)
+    void add_wn(int tnj, const fwn_conv_grad* c, int k, int n, int col0, float scale, const int32_t* row_src, const int32_t* col_src) {
+        wn[nwn++] = WnItem{tnj, nullptr, 0, 0, 0, 0, c, k, n, col0, scale, row_src, col_src};
+    }
+};
 
-}  // namespace
+// NULL: a step can run this model at (B, T); else what is wrong with the shape (the workspace queries answer 0 there)
+const char* shape_error(const fwn_model_desc* md, long B, long T) {
+    if (!(md->n_block >= 1 && md->n_block <= 16 && md->n_flow >= 1 && md->n_block * md->n_flow <= 256 && md->n_layer >= 1 &&
+          md->n_layer <= FWN_MAX_LAYERS))
+        return "bad n_block / n_flow / n_layer";
+    if (!(B > 0 && T > 0 && T % hop_of(md) == 0 && T % (1L << md->n_block) == 0)) return "T must be a multiple of hop_size and 2^n_block";
+    return nullptr;
+}
 
-static size_t train_workspace(const fwn_train_desc* t, int64_t B, int64_t T, bool ragged) {
-    if (!t || !t->model || !t->flows || B <= 0 || T <= 0) return 0;
-    const fwn_model_desc* md = t->model;
-    if (md->n_block < 1 || md->n_block > 16 || md->n_flow < 1 || md->n_layer < 1 || md->n_layer > FWN_MAX_LAYERS) return 0;
-    if (T % hop_of(md) || T % (1L << md->n_block)) return 0;
-    if (md->n_block * md->n_flow > 256) return 0;
+size_t train_workspace(const fwn_train_desc* t, int64_t B, int64_t T, PassKind kind) {
+    if (!t || !t->model || !t->flows || shape_error(t->model, (long)B, (long)T)) return 0;
     FlowSaved saved[256];
     Plan pl{};
     pl.saved = saved;
-    plan(t, (long)B, (long)T, nullptr, pl, ragged);
+    plan(t, (long)B, (long)T, nullptr, pl, kind);
     return pl.total;
 }
 
-// The one sequencer of both entry points.  len (ragged step): the clips' lengths on the device - the forward half then runs
-// the fills of the ragged forward pass (api.hip flow_run_impl / model_pass with len) and the backward half their adjoint: where
-// the forward overwrote rows with a constant, the gradient arriving at those rows is dropped.  out2B: per-clip scalars (NULL: kept
-// in the workspace).
-static int train_impl(const fwn_train_desc* t, int64_t B_, int64_t T_, const float* x, const float* mel, const int32_t* len, void* workspace,
-                      size_t workspace_bytes, float* out3, float* out2B, fwn_block_done_fn on_block_done, void* user, void* stream) {
-    TREQUIRE(t && t->model && t->flows && t->model->flows, "fwn_train_loss_and_grads: null descriptor");
-    TREQUIRE(x && mel && workspace && out3, "fwn_train_loss_and_grads: null pointer");
-    TREQUIRE((((uintptr_t)workspace) & 255) == 0, "fwn_train_loss_and_grads: workspace must be 256-byte aligned");
-    const fwn_model_desc* md = t->model;
-    const long B = (long)B_, T = (long)T_;
-    const int L = md->n_layer, half = md->num_mels / 2, nmel = 2 * half, NF = md->n_flow;
-    TREQUIRE(md->n_block >= 1 && md->n_block <= 16 && NF >= 1 && md->n_block * NF <= 256 && L >= 1 && L <= FWN_MAX_LAYERS,
-             "fwn_train_loss_and_grads: bad n_block / n_flow / n_layer");
-    TREQUIRE(B > 0 && T > 0 && T % hop_of(md) == 0 && T % (1L << md->n_block) == 0, "fwn_train_loss_and_grads: T must be a multiple of hop_size and 2^n_block");
-    TREQUIRE((int64_t)L * (B * T / 2) * 512 < ((int64_t)1 << 31), "fwn_train_loss_and_grads: B*T too large (2 GiB per activation buffer)");
-    for (int i = 0; i < md->n_block; ++i)
-        TREQUIRE(t->cond_rows[i] && t->front_rows[i] && t->zinv32[i] && t->br[i] && t->zcol[i], "fwn_train_loss_and_grads: missing index table (block %d)", i);
-    FlowSaved saved[256];
+// One call of either entry point: what its phases share, and one member function per phase - run() is the sequence.
+// len (ragged step): the clips' lengths on the device - the forward half then runs the fills of the ragged forward pass
+// (fwn_sequence.h: the walks inference runs) and the backward half their adjoint: where the forward overwrote rows with a
+// constant, the gradient arriving at those rows is dropped.  out2B: per-clip scalars (NULL: kept in the workspace).
+struct TrainCall {
+    // ---- the arguments ----
+    PassKind kind;
+    const fwn_train_desc* t;
+    long B, T;
+    const float* x; const float* mel; const int32_t* len;
+    void* workspace; size_t workspace_bytes;
+    float* out3; float* out2B;
+    fwn_block_done_fn on_block_done; void* user;
+    hipStream_t st;
+    // ---- set by prepare() ----
+    const fwn_model_desc* md = nullptr;
+    int L = 0, half = 0, nmel = 0, NF = 0;
+    size_t plane_elems = 0, cplane_elems = 0;
+    ClipRows rows{nullptr, 0, nullptr};
     Plan pl{};
-    pl.saved = saved;
-    TREQUIRE(!len || !md->gate_fp8, "fwn_train_loss_and_grads_ragged: per-clip lengths go with a model without fp8 gates (its e4m3 copies of h are not masked)");
-    TREQUIRE(!len || B < 32768, "fwn_train_loss_and_grads_ragged: B=%ld clips (at most 32767 per call)", B);
-    plan(t, B, T, workspace, pl, len != nullptr);
-    if (workspace_bytes < pl.total) return fwn_set_error(FWN_ERR_WORKSPACE, "workspace %zu < required %zu bytes", workspace_bytes, pl.total);
-    hipStream_t st = (hipStream_t)stream;
+    FlowSaved saved[256];
+    // ---- the side stream (backward) ----
+    hipStream_t side = nullptr;
+    EventPool* evp = nullptr;
+    std::vector<Deferred> pending;        // the flows of the block whose weight gradients are still to be enqueued
+    int pending_block = -1;               // block whose weight gradients run on the side stream, not yet joined
+    bool hook_failed = false;             // a hook that returns non-zero stops the sequencing where it stands (the side stream is joined at that point)
+    hipEvent_t dca_done = nullptr;        // side stream, block 0: behind the last conditioning-gradient GEMM of the call
+    bool forked = false;                  // something has been handed to the side stream and run() has not ended in FWN_OK
+
+    // What one flow's backward works on
+    struct FlowCtx {
+        int i, j, ch, cin, ldz; long ti, m;
+        const fwn_flow_desc* d; const fwn_flow_train_desc* td; const FlowSaved* s; const BwdSet* w;
+        float* xa; float* xb;              // y_a, out_b
+        float* ga; float* gb;
+        const void* ca; float* dca;
+    };
+
+    // Error exits (ADVICE r4): once anything has been handed to the side stream, EVERY return path joins it into `st` first -
+    // otherwise weight-gradient kernels of the block handed over last would keep reading and writing the caller's workspace
+    // and gradient buffers after the call has returned an error.  Event-based, so it is also legal while the stream is being
+    // captured.
+    ~TrainCall() {
+        if (!forked || !side || !evp) return;
+        hipEvent_t e = evp->get();
+        if (!e || hipEventRecord(e, side) != hipSuccess || hipStreamWaitEvent(st, e, 0) != hipSuccess) (void)hipStreamSynchronize(side);
+    }
+
+    int run() {
+        int rc = prepare();
+        if (rc != FWN_OK) return rc;
+        rc = forward();
+        if (rc != FWN_OK) return rc;
+        finish_loss();
+        rc = backward();
+        if (rc != FWN_OK) return rc;
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return fwn_set_error(FWN_ERR_HIP, "fwn_train_loss_and_grads: %s", hipGetErrorString(e));
+        forked = false;                   // every block was joined on the way (join_pending)
+        return FWN_OK;
+    }
+
+    // ---------------- argument checks and planning ----------------
+    int prepare() {
+        TREQUIRE(t && t->model && t->flows && t->model->flows, "fwn_train_loss_and_grads: null descriptor");
+        TREQUIRE(x && mel && workspace && out3, "fwn_train_loss_and_grads: null pointer");
+        TREQUIRE((((uintptr_t)workspace) & 255) == 0, "fwn_train_loss_and_grads: workspace must be 256-byte aligned");
+        md = t->model;
+        L = md->n_layer; half = md->num_mels / 2; nmel = 2 * half; NF = md->n_flow;
+        const char* bad = shape_error(md, B, T);
+        TREQUIRE(!bad, "fwn_train_loss_and_grads: %s", bad);
+        TREQUIRE((int64_t)L * (B * T / 2) * 512 < ((int64_t)1 << 31), "fwn_train_loss_and_grads: B*T too large (2 GiB per activation buffer)");
+        for (int i = 0; i < md->n_block; ++i)
+            TREQUIRE(t->cond_rows[i] && t->front_rows[i] && t->zinv32[i] && t->br[i] && t->zcol[i], "fwn_train_loss_and_grads: missing index table (block %d)", i);
+        TREQUIRE(!len || !md->gate_fp8, "fwn_train_loss_and_grads_ragged: per-clip lengths go with a model without fp8 gates (its e4m3 copies of h are not masked)");
+        TREQUIRE(!len || B < 32768, "fwn_train_loss_and_grads_ragged: B=%ld clips (at most 32767 per call)", B);
+        pl.saved = saved;
+        plan(t, B, T, workspace, pl, kind);
+        if (workspace_bytes < pl.total) return fwn_set_error(FWN_ERR_WORKSPACE, "workspace %zu < required %zu bytes", workspace_bytes, pl.total);
+        plane_elems = (size_t)B * T / 2;
+        cplane_elems = (size_t)B * T * half;
+        rows = ClipRows{len, B, st};
+        return FWN_OK;
+    }
 
     // ---------------- forward, keeping what the backward needs ----------------
-    // ragged: rows [len / samples per row, rows) of every clip of a [B][rows][row_bytes] buffer are zeroed
-    auto mask = [&](void* base, long nclip, long rows, long row_bytes, int spr) {
-        if (len) fwn_launch_mask_rows(base, nclip, rows, row_bytes, len, (int)B, spr, st);
-    };
-    {
-        long H = T / hop_of(md);
-        int spr = hop_of(md);                // samples per row of the current stage's input
-        const float* in = mel;
-        if (len) {      // the stages run on a copy of the mel with the frames past each clip's end zeroed, and so is every inner
-                        // stage's output (api.hip run_upsample); the up-sampling backward reads these very buffers
-            if (hipMemcpyAsync(pl.melc, mel, (size_t)B * H * nmel * 4, hipMemcpyDeviceToDevice, st) != hipSuccess)
-                return fwn_set_error(FWN_ERR_HIP, "fwn_train_loss_and_grads_ragged: mel copy failed");
-            mask(pl.melc, B, H, (long)nmel * 4, spr);
-            in = pl.melc;
+    int forward() {
+        {   // ragged: the up-sampling backward reads the masked buffers of this walk
+            UpsampleBufs u;
+            memset(&u, 0, sizeof(u));
+            u.mel_copy = pl.melc;
+            for (int n = 0; n < md->n_up; ++n) {
+                TREQUIRE(t->up_bias_dev[n], "fwn_train_loss_and_grads: up_bias_dev[%d] is null", n);
+                u.inner[n] = pl.ups[n];
+            }
+            u.cplanes = pl.cplanes;
+            u.bias_dev = t->up_bias_dev;
+            if (fwn_run_upsample(md, B, T, mel, u, rows)) return fwn_set_error(FWN_ERR_HIP, "fwn_train_loss_and_grads_ragged: mel copy failed");
         }
-        for (int n = 0; n < md->n_up; ++n) {
-            const bool last = n == md->n_up - 1;
-            TREQUIRE(t->up_bias_dev[n], "fwn_train_loss_and_grads: up_bias_dev[%d] is null", n);
-            fwn_launch_upsample(in, (int)B, (int)H, nmel, md->up_w[n], 0.0f, t->up_bias_dev[n], md->up_scale[n], last ? nullptr : pl.ups[n],
-                                last ? pl.cplanes : nullptr, st);
-            H *= md->up_scale[n];
-            spr /= md->up_scale[n];
-            if (!last) mask(pl.ups[n], B, H, (long)nmel * 4, spr);
-            in = pl.ups[n];
-        }
-    }
-    fwn_launch_split(x, B, T, pl.planes, st);
-    // ragged: both planes hold clip b's samples at [b][0, len / 2) at every block; the rest is zeroed here and behind every flow
-    auto mask_planes = [&]() { mask(pl.planes, 2 * B, T / 2, 4, 2); };
-    mask_planes();
-    const int nslot = len ? fwn_ragged_logdet_nslot(B) : 0;
-    const size_t plane_elems = (size_t)B * T / 2, cplane_elems = (size_t)B * T * half;
-    int p = 0;
-    for (int i = 0; i < md->n_block; ++i) {
-        const int ch = 1 << i;
-        const long ti = T / (2 * ch), m = B * ti;
-        const int cin = half * (2 << i);
-        const fwn_flow_desc* d0 = &md->flows[i * NF];
-        const bool hoist = pl.cond[i].hoist;
-        if (hoist)
-            fwn_run_cond(pl.cond[i], (const bf16*)pl.cplanes + (size_t)p * cplane_elems, (const bf16*)pl.cplanes + (size_t)(p ^ 1) * cplane_elems,
-                         d0->Wc[0], pl.P, pl.Ppart, (int)m, NF, L, cin, d0->kcpad, st);
-        for (int j = 0; j < NF; ++j) {
-            const fwn_flow_desc* d = &md->flows[i * NF + j];
-            FlowSaved& s = saved[i * NF + j];
-            s.p = p;
-            float* xa = pl.planes + (size_t)p * plane_elems;
-            float* xb = pl.planes + (size_t)(p ^ 1) * plane_elems;
-            const void* ca = (const bf16*)pl.cplanes + (size_t)p * cplane_elems;
-            // the inference kernels, keeping what the backward needs: the front conv applies the flow's ActNorm on the fly, the
-            // tail (skip sum -> final conv -> ZeroConv -> coupling + ActNorm of both planes, csrc/tail_chain.h) leaves
-            // y_a / out_b in the planes - the state the backward starts from - and writes S, U and Z on its way
-            // ragged: -shift in x_a's rows past a clip's end, so that the front conv's on-the-fly ActNorm reads exact zeros there;
-            // h zeroed in those rows behind every kernel that writes it, BEFORE it is kept (the weight gradients read it)
-            if (len) fwn_launch_fill_neg_shift(xa, B, ti, ch, d->an, len, (int)B, 2 * ch, st);
-            fwn_launch_front(xa, d->an, d->Wfront, d->Wfront2, d->bfront, s.h[0], ch >= 32 ? pl.xhl : nullptr, (int)m, (int)ti, ch, d->kfpad, 1, nullptr, st);
-            mask(s.h[0], B, ti, 512, 2 * ch);
-            for (int l = 0; l < L; ++l) {
-                const float* Pl = hoist ? pl.P + ((size_t)j * L + l) * m * 512 : nullptr;
-                fwn_launch_gate(s.h[l], hoist ? nullptr : ca, Pl, d->Wd[l], d->Wc[l], nullptr, d->bgate[l], s.o[l], (int)m, (int)ti, dilation_of(l), d->cin,
-                                d->kcpad, s.aux[l], st);
-                if (l + 1 < L) {
-                    fwn_launch_res(s.o[l], s.h[l], d->Wres[l], d->bres[l], s.h[l + 1], (int)m, nullptr, st);
-                    mask(s.h[l + 1], B, ti, 512, 2 * ch);
+        fwn_launch_split(x, B, T, pl.planes, st);
+        // ragged: both planes hold clip b's samples at [b][0, len / 2) at every block; the rest is zeroed here and behind every flow
+        rows.zero_planes(pl.planes, T);
+        const int nslot = len ? fwn_ragged_logdet_nslot(B) : 0;
+        int p = 0;
+        for (int i = 0; i < md->n_block; ++i) {
+            const int ch = 1 << i;
+            const long ti = T / (2 * ch), m = B * ti;
+            const int cin = half * (2 << i);
+            const fwn_flow_desc* d0 = &md->flows[i * NF];
+            const bool hoist = pl.cond[i].hoist;
+            if (hoist)
+                fwn_run_cond(pl.cond[i], (const bf16*)pl.cplanes + (size_t)p * cplane_elems, (const bf16*)pl.cplanes + (size_t)(p ^ 1) * cplane_elems,
+                             d0->Wc[0], pl.P, pl.Ppart, (int)m, NF, L, cin, d0->kcpad, st);
+            for (int j = 0; j < NF; ++j) {
+                const fwn_flow_desc* d = &md->flows[i * NF + j];
+                FlowSaved& s = saved[i * NF + j];
+                s.p = p;
+                float* xa = pl.planes + (size_t)p * plane_elems;
+                float* xb = pl.planes + (size_t)(p ^ 1) * plane_elems;
+                const void* ca = (const bf16*)pl.cplanes + (size_t)p * cplane_elems;
+                // the inference kernels, keeping what the backward needs: the front conv applies the flow's ActNorm on the fly, the
+                // tail (skip sum -> final conv -> ZeroConv -> coupling + ActNorm of both planes, csrc/tail_chain.h) leaves
+                // y_a / out_b in the planes - the state the backward starts from - and writes S, U and Z on its way.
+                // The stages over the buffers kept per layer: no fp8, no gate stream, the bf16 (hi | lo) image as the front
+                // conv's scratch from Ch >= 32
+                FlowStages sg;
+                memset(&sg, 0, sizeof(sg));
+                for (int l = 0; l < L; ++l) { sg.h[l] = s.h[l]; sg.o[l] = s.o[l]; sg.aux[l] = s.aux[l]; }
+                sg.front_scratch = ch >= 32 ? pl.xhl : nullptr;
+                fwn_run_stages(d, sg, xa, hoist ? nullptr : ca, hoist ? pl.P + (size_t)j * L * m * 512 : nullptr, (int)m, (int)ti, 0, rows);
+                const int rc = tail(d, s, xa, xb, m, ch);
+                if (rc != FWN_OK) return rc;
+                if (len) {      // per-clip log-det sums from the Z the tail keeps for the backward (its own whole-batch partials are ignored)
+                    fwn_launch_ragged_logdet(s.z, B, ti, ch, d->ezero, d->an, len, (int)B, 2 * ch, pl.acc + (size_t)(i * NF + j) * B * nslot, st);
+                    rows.zero_planes(pl.planes, T);
                 }
+                p ^= 1;
             }
-            {
-                const long o_stride = L > 1 ? (long)(((const char*)s.o[1] - (const char*)s.o[0]) / 2) : 0;
-                for (int l = 1; l < L; ++l)
-                    TREQUIRE((const char*)s.o[l] == (const char*)s.o[0] + (size_t)l * o_stride * 2, "fwn_train_loss_and_grads: o buffers not evenly spaced");
-                // the tail addresses o through ONE 32-bit buffer descriptor (byte span of all L layers, as fwn_tail_train checks)
-                TREQUIRE(((long)(L - 1) * o_stride + m * 256) * 2 < (1L << 31), "fwn_train_loss_and_grads: o rows of a flow span %ld bytes: beyond the tail's 32-bit buffer offsets", ((long)(L - 1) * o_stride + m * 256) * 2);
-                fwn_tail_chain tc;
-                memset(&tc, 0, sizeof(tc));
-                tc.save_s = s.s_act; tc.save_u = s.u_act; tc.save_z = s.z;
-                fwn_launch_tail(s.o[0], o_stride, L, d->Wskip, d->bskip, d->Wfinal, d->bfinal, d->Wzero, d->bzero, d->ezero, d->an, xa, xb, s.part,
-                                (int)m, ch, d->npt, 0, nullptr, nullptr, &tc, d->Wts, st);
-            }
-            if (len) {      // per-clip log-det sums from the Z the tail keeps for the backward (its own whole-batch partials are ignored)
-                fwn_launch_ragged_logdet(s.z, B, ti, ch, d->ezero, d->an, len, (int)B, 2 * ch, pl.acc + (size_t)(i * NF + j) * B * nslot, st);
-                mask_planes();
-            }
-            p ^= 1;
         }
+        return FWN_OK;
     }
-    if (len) {
-        float* o2 = out2B ? out2B : pl.out2B;
-        fwn_launch_ragged_finish(pl.planes, B, T, pl.acc, md->n_block * NF, NF, len, o2, st);
-        hipLaunchKernelGGL(finish_loss_ragged_kernel, dim3(1), dim3(64), 0, st, (const float*)o2, B, out3);
-    } else {
-        fwn_launch_prior(pl.planes, B * T, pl.partial_all, pl.npart, 1.0 / (double)(B * T), pl.out2, st);
-        hipLaunchKernelGGL(finish_loss_kernel, dim3(1), dim3(64), 0, st, pl.out2, out3);
+    int tail(const fwn_flow_desc* d, const FlowSaved& s, float* xa, float* xb, long m, int ch) {
+        const long o_stride = L > 1 ? (long)(((const char*)s.o[1] - (const char*)s.o[0]) / 2) : 0;
+        for (int l = 1; l < L; ++l)
+            TREQUIRE((const char*)s.o[l] == (const char*)s.o[0] + (size_t)l * o_stride * 2, "fwn_train_loss_and_grads: o buffers not evenly spaced");
+        // the tail addresses o through ONE 32-bit buffer descriptor (byte span of all L layers, as fwn_tail_train checks)
+        TREQUIRE(((long)(L - 1) * o_stride + m * 256) * 2 < (1L << 31), "fwn_train_loss_and_grads: o rows of a flow span %ld bytes: beyond the tail's 32-bit buffer offsets", ((long)(L - 1) * o_stride + m * 256) * 2);
+        fwn_tail_chain tc;
+        memset(&tc, 0, sizeof(tc));
+        tc.save_s = s.s_act; tc.save_u = s.u_act; tc.save_z = s.z;
+        fwn_launch_tail(s.o[0], o_stride, L, d->Wskip, d->bskip, d->Wfinal, d->bfinal, d->Wzero, d->bzero, d->ezero, d->an, xa, xb, s.part,
+                        (int)m, ch, d->npt, 0, nullptr, nullptr, &tc, d->Wts, st);
+        return FWN_OK;
+    }
+
+    // ---------------- the loss ----------------
+    void finish_loss() {
+        if (len) {
+            float* o2 = out2B ? out2B : pl.out2B;
+            fwn_launch_ragged_finish(pl.planes, B, T, pl.acc, md->n_block * NF, NF, len, o2, st);
+            hipLaunchKernelGGL(finish_loss_ragged_kernel, dim3(1), dim3(64), 0, st, (const float*)o2, B, out3);
+        } else {
+            fwn_launch_prior(pl.planes, B * T, pl.partial_all, pl.npart, 1.0 / (double)(B * T), pl.out2, st);
+            hipLaunchKernelGGL(finish_loss_kernel, dim3(1), dim3(64), 0, st, pl.out2, out3);
+        }
     }
 
     // ---------------- backward ----------------
@@ -500,48 +546,231 @@ static int train_impl(const fwn_train_desc* t, int64_t B_, int64_t T_, const flo
     // joining before the end.  The two queues overlap only partly (tools/diag/train_timeline.py: a chain launch of a few
     // workgroups waits behind the dispatch of a side kernel that fills the chip - tools/probe/queue_overlap.hip).
     // Without a side stream they follow their flow on the one stream.
-    hipStream_t side = (hipStream_t)t->side_stream;
-    EventPool* evp = nullptr;
-    if (side) {
-        evp = event_pool();
-        TREQUIRE(evp, "fwn_train_loss_and_grads: hipEventCreate failed");
-        evp->next = 0;
-    }
-    struct Deferred {
-        TnList tn; WnItem wn[4 + 7 * FWN_MAX_LAYERS]; int nwn; long m, ti; int ch, i; const BwdSet* w;
-        const fwn_flow_train_desc* td;
-        const float* an;                                   // the flow's ActNorm table (totals of the small gradients)
-        fwn_gemm_desc dca[FWN_MAX_LAYERS]; int ndca;      // conditioning-gradient GEMMs (accumulate into the mel image: order kept)
-    };
-    std::vector<Deferred> pending;        // the flows of the block whose weight gradients are still to be enqueued
-    // Error exits (ADVICE r4): once anything has been handed to the side stream, EVERY return path joins it into `st` first -
-    // otherwise weight-gradient kernels of the block handed over last would keep reading and writing the caller's workspace
-    // and gradient buffers after the call has returned an error.  Event-based, so it is also legal while the stream is being
-    // captured.
-    struct SideJoinGuard {
-        hipStream_t st, side; EventPool* evp; bool armed;
-        ~SideJoinGuard() {
-            if (!armed || !side || !evp) return;
-            hipEvent_t e = evp->get();
-            if (!e || hipEventRecord(e, side) != hipSuccess || hipStreamWaitEvent(st, e, 0) != hipSuccess) (void)hipStreamSynchronize(side);
+    int backward() {
+        side = (hipStream_t)t->side_stream;
+        if (side) {
+            evp = event_pool();
+            TREQUIRE(evp, "fwn_train_loss_and_grads: hipEventCreate failed");
+            evp->next = 0;
         }
-    } side_guard{st, side, evp, false};
-    int pending_block = -1;               // block whose weight gradients run on the side stream, not yet joined
-    // a hook that returns non-zero stops the sequencing where it stands (the side stream is joined at that point)
-    bool hook_failed = false;
-    auto hook_stop = [&]() -> int { return fwn_set_error(FWN_ERR_CALLBACK, "fwn_train_loss_and_grads: the on_block_done callback asked to stop"); };
-    // The weight gradients of a flow in three stages: (1) totals of the small gradients + the conditioning-gradient GEMMs,
+        // d loss / d z = z / (B T)   (log_p = mean 0.5 (-log 2 pi - z^2))
+        if (len) hipLaunchKernelGGL(dz_init_ragged_kernel, dim3(grid_of(B * T)), dim3(256), 0, st, pl.gplanes, (const float*)pl.planes, B, T / 2, len);
+        else hipLaunchKernelGGL(scale_copy_kernel, dim3(grid_of(B * T)), dim3(256), 0, st, pl.gplanes, pl.planes, B * T, (float)(1.0 / (double)(B * T)));
+        if (hipMemsetAsync(pl.dcplanes, 0, (size_t)2 * B * T * half * 4, st) != hipSuccess) return fwn_set_error(FWN_ERR_HIP, "hipMemsetAsync failed");
+        for (int i = md->n_block - 1; i >= 0; --i)
+            for (int j = NF - 1; j >= 0; --j) {
+                const int rc = flow_backward(i, j);
+                if (rc != FWN_OK) return rc;
+            }
+        // The conditioning gradient is complete behind stage (1) of block 0's weight gradients (side stream): the up-sampling
+        // backward waits for THAT event and runs under the rest of block 0's side work (its grouped TN GEMM and weight-norm
+        // backward: ~1 ms in which the chain's queue had nothing to do); block 0 is joined and reported behind it.
+        if (side && dca_done) {
+            if (hipStreamWaitEvent(st, dca_done, 0) != hipSuccess) return fwn_set_error(FWN_ERR_HIP, "fwn_train_loss_and_grads: hipStreamWaitEvent failed");
+        } else if (side) {
+            if (!join_pending()) return fwn_set_error(FWN_ERR_HIP, "fwn_train_loss_and_grads: joining the side stream failed");
+            if (hook_failed) return hook_stop();
+        }
+        const int rc = upsample_backward();
+        if (rc != FWN_OK) return rc;
+        if (side && !join_pending()) return fwn_set_error(FWN_ERR_HIP, "fwn_train_loss_and_grads: joining the side stream failed");
+        if (hook_failed) return hook_stop();
+        if (on_block_done && on_block_done(user, -1) != 0) return hook_stop();
+        return FWN_OK;
+    }
+    int hook_stop() { return fwn_set_error(FWN_ERR_CALLBACK, "fwn_train_loss_and_grads: the on_block_done callback asked to stop"); }
+
+    // One flow: its data-gradient chain, and where its weight gradients go - behind the chain's front-conv job on the one
+    // stream, or with its block's to the side stream once the block's first flow is through
+    int flow_backward(int i, int j) {
+        const FlowCtx F = flow_ctx(i, j);
+        pending.emplace_back();
+        Deferred& D = pending.back();
+        D.nwn = 0; D.m = F.m; D.ti = F.ti; D.ch = F.ch; D.i = i; D.w = F.w; D.td = F.td; D.ndca = 0; D.an = F.d->an;
+        chain_to_skip(F, D);
+        int rc = chain_layers(F, D);
+        if (rc != FWN_OK) return rc;
+        rc = chain_front(F, D);
+        if (rc != FWN_OK) return rc;
+        if (!side) {
+            rc = weight_grads(D, st);
+            if (rc != FWN_OK) return rc;
+            pending.clear();
+        }
+        rc = chain_end(F);
+        if (rc != FWN_OK) return rc;
+        if (!side) fwn_small_grads_final(F.d->an, F.m, F.ch, (const long long*)t->br[i], (const long long*)t->zcol[i], F.w->sg, F.td->d_an_b,
+                                         F.td->d_an_logs, F.td->d_zscale, st);
+        if (!side && j == 0 && on_block_done && on_block_done(user, i) != 0) hook_failed = true;
+        if (hook_failed) return hook_stop();
+        if (side && j == 0) {      // this block's weight gradients: under the next block's chain
+            if (!join_pending()) return fwn_set_error(FWN_ERR_HIP, "fwn_train_loss_and_grads: joining the side stream failed");
+            if (hook_failed) return hook_stop();
+            rc = hand_over(i == 0);
+            if (rc != FWN_OK) return rc;
+            pending_block = i;
+        }
+        return FWN_OK;
+    }
+    FlowCtx flow_ctx(int i, int j) const {
+        FlowCtx F;
+        F.i = i; F.j = j; F.ch = 1 << i;
+        F.ti = T / (2 * F.ch); F.m = B * F.ti;
+        F.cin = half * (2 << i);
+        F.ldz = 2 * F.ch > 8 ? 2 * F.ch : 8;
+        F.d = &md->flows[i * NF + j];
+        F.td = &t->flows[i * NF + j];
+        F.s = &saved[i * NF + j];
+        F.w = side ? &pl.sets[(size_t)i * NF + j] : &pl.sets[0];
+        const int pp = F.s->p;
+        F.xa = pl.planes + (size_t)pp * plane_elems;
+        F.xb = pl.planes + (size_t)(pp ^ 1) * plane_elems;
+        F.ga = pl.gplanes + (size_t)pp * plane_elems;
+        F.gb = pl.gplanes + (size_t)(pp ^ 1) * plane_elems;
+        F.ca = (const bf16*)pl.cplanes + (size_t)pp * cplane_elems;
+        F.dca = pl.dcplanes + (size_t)pp * cplane_elems;
+        return F;
+    }
+    // nothing in the flow chain reads the conditioning gradient: with a side stream it leaves the chain
+    void cond_grad(Deferred& D, const fwn_gemm_desc& g) {
+        if (side) D.dca[D.ndca++] = g;
+        else fwn_gemm_launch(&g, st);
+    }
+
+    // ---- the data-gradient chain of one flow (all on `st`), collecting the flow's weight-gradient jobs in D ----
+    // coupling -> ZeroConv -> final conv -> the skip convs of every layer
+    void chain_to_skip(const FlowCtx& F, Deferred& D) {
+        const FlowSaved& s = *F.s;
+        const BwdSet& w = *F.w;
+        const fwn_flow_train_desc* td = F.td;
+        const long m = F.m;
+        const int ch = F.ch, ldz = F.ldz;
+        TnList& tn = D.tn;
+        // coupling
+        // (also: the bf16 copy of y_a for the front conv's weight gradient, and the zero padding of dZ's rows)
+        if (len) fwn_ew_coupling_bwd_ragged(F.gb, F.xb, s.z, td->ez, B, F.ti, ch, len, 2 * ch, w.dz, ldz, pl.dzz, F.xa, w.ya_bf, ch < 8 ? 8 : ch, st);
+        else fwn_ew_coupling_bwd_ex(F.gb, F.xb, s.z, td->ez, m * ch, ch, (float)(1.0 / (2.0 * (double)m * ch)), w.dz, ldz, pl.dzz, F.xa, w.ya_bf, ch < 8 ? 8 : ch, st);
+        {
+            Seg a{w.dz, m, ldz, ldz, 0, 0};
+            fwn_gemm_desc g = gemm_desc(&a, 1, td->WzT, ldz, 256, m, 0, w.du, 256, false);
+            g.mask = s.u_act; g.ldmask = 256;
+            fwn_gemm_launch(&g, st);
+        }
+        D.add_wn(tn.add(s.u_act, 256, w.dz, ldz, 256, ldz, 1, 0, 0), &td->zero, 256, 2 * ch, 0, 1.0f, nullptr, t->zinv32[F.i]);
+        D.add_wn(tn.add(s.s_act, 256, w.du, 256, 256, 256, 1, 0, 0), &td->final_, 256, 256, 0, 1.0f, nullptr, nullptr);
+        {
+            Seg a{w.du, m, 256, 256, 0, 0};
+            fwn_gemm_desc g = gemm_desc(&a, 1, td->WfinT, 256, 256, m, 0, w.ds, 256, false);
+            g.mask = s.s_act; g.ldmask = 256;
+            fwn_gemm_launch(&g, st);
+            Seg a2{w.ds, m, 256, 256, 0, 0};
+            g = gemm_desc(&a2, 1, td->WskipT_all, 256, L * 256, m, 0, pl.d_all, L * 256, false);      // do_l = dS Wskip_l for every layer at once
+            // the last layer's do is complete here: its gate derivative rides this epilogue (no store + fwn_gate_bwd)
+            g.gate_aux = s.aux[L - 1]; g.gate_out = w.dpre[L - 1]; g.gate_col0 = (L - 1) * 256;
+            fwn_gemm_launch(&g, st);
+        }
+        for (int l = 0; l < L; ++l) D.add_wn(tn.add(s.o[l], 256, w.ds, 256, 256, 256, 1, 0, 0), &td->skip[l], 256, 256, 0, 1.0f, nullptr, nullptr);
+    }
+    // the layers, last first: res conv -> gate -> dilated conv (and the layer's conditioning gradient); leaves dh_0 in w.dh[0]
+    int chain_layers(const FlowCtx& F, Deferred& D) {
+        const FlowSaved& s = *F.s;
+        const BwdSet& w = *F.w;
+        const fwn_flow_train_desc* td = F.td;
+        const long m = F.m;
+        const int cin = F.cin;
+        TnList& tn = D.tn;
+        const void* dh_next = nullptr;
+        for (int l = L - 1; l >= 0; --l) {
+            const int dil = dilation_of(l);
+            const void* d_ol = (const bf16*)pl.d_all + (size_t)l * 256;
+            int ld_do = L * 256;
+            if (dh_next) {      // h_{l+1} = (h_l + res(o_l)) sqrt(1/2)
+                D.add_wn(tn.add(s.o[l], 256, dh_next, 256, 256, 256, 1, 0, 0), &td->res[l], 256, 256, 0, SQH, nullptr, nullptr);
+                Seg a{dh_next, m, 256, 256, 0, 0};
+                fwn_gemm_desc g = gemm_desc(&a, 1, td->WresT[l], 256, 256, m, 0, pl.d_o[l], 256, false);
+                g.R = d_ol; g.ldr = ld_do; g.rscale = (float)(1.0 / 0.7071067811865476); g.oscale = SQH;
+                g.gate_aux = s.aux[l]; g.gate_out = w.dpre[l]; g.gate_col0 = 0;      // do_l goes straight through the gate derivative
+                fwn_gemm_launch(&g, st);
+            } else if (t->zero_dead_res) {      // dead res_conv of the last layer (modules.py:126-128): zero gradients
+                const fwn_conv_grad& c = td->res[l];
+                if (c.dV && hipMemsetAsync(c.dV, 0, (size_t)256 * 256 * 4, st) != hipSuccess) return fwn_set_error(FWN_ERR_HIP, "hipMemsetAsync failed");
+                if (c.dg && hipMemsetAsync(c.dg, 0, 256 * 4, st) != hipSuccess) return fwn_set_error(FWN_ERR_HIP, "hipMemsetAsync failed");
+                if (c.db && hipMemsetAsync(c.db, 0, 256 * 4, st) != hipSuccess) return fwn_set_error(FWN_ERR_HIP, "hipMemsetAsync failed");
+            }
+            const int jd = tn.add(s.h[l], 256, w.dpre[l], 512, 256, 512, 3, -dil, dil);
+            D.add_wn(jd, &td->filt[l], 768, 256, 0, 1.0f, nullptr, nullptr);
+            D.add_wn(jd, &td->gate[l], 768, 256, 256, 1.0f, nullptr, nullptr);
+            const int jc = tn.add(F.ca, cin, w.dpre[l], 512, cin, 512, 1, 0, 0);
+            D.add_wn(jc, &td->filt_c[l], cin, 256, 0, 1.0f, t->cond_rows[F.i], nullptr);
+            D.add_wn(jc, &td->gate_c[l], cin, 256, 256, 1.0f, t->cond_rows[F.i], nullptr);
+            if (td->wct_ld != L * 512) {        // (else the layers' WcT lie side by side: one GEMM behind the loop, chain_front)
+                Seg a{w.dpre[l], m, 512, 512, 0, 0};
+                fwn_gemm_desc g = gemm_desc(&a, 1, td->WcT[l], td->wct_ld ? td->wct_ld : 512, cin, m, 0, F.dca, cin, true);
+                g.accumulate = 1;
+                cond_grad(D, g);
+            }
+            Seg sg[3];
+            for (int tap = 0; tap < 3; ++tap) sg[tap] = {w.dpre[l], m, 512, 512, -(tap - 1) * dil, tap * 512};
+            fwn_gemm_desc g = gemm_desc(sg, 3, td->WdT[l], 1536, 256, m, (int)F.ti, w.dh[l], 256, false);
+            if (dh_next) { g.R = dh_next; g.ldr = 256; g.rscale = SQH; }
+            if (l == 0) { g.mask = s.h[0]; g.ldmask = 256; }
+            // ragged: the forward zeroed h_l past each clip's end, so dh_l is stored as 0 there (in this launch's epilogue)
+            if (len) { g.row_len = len; g.len_spr = 2 * F.ch; }
+            fwn_gemm_launch(&g, st);
+            dh_next = w.dh[l];
+        }
+        return FWN_OK;
+    }
+    // the flow's conditioning gradient where it is one GEMM, and the front conv's weight-gradient job
+    int chain_front(const FlowCtx& F, Deferred& D) {
+        const BwdSet& w = *F.w;
+        const fwn_flow_train_desc* td = F.td;
+        const int ch = F.ch;
+        if (td->wct_ld == L * 512) {      // conditioning gradient of the flow: dca += [dpre_0 | dpre_1 | ..] [Wc_0 ; Wc_1 ; ..]
+            Seg sg[FWN_MAX_LAYERS];
+            for (int l = 0; l < L; ++l) {
+                TREQUIRE((const char*)td->WcT[l] == (const char*)td->WcT[0] + (size_t)l * 512 * 2, "fwn_train_loss_and_grads: wct_ld = L*512 needs WcT[l] = WcT[0] + l*512");
+                sg[l] = {w.dpre[l], F.m, 512, 512, 0, l * 512};
+            }
+            fwn_gemm_desc g = gemm_desc(sg, L, td->WcT[0], L * 512, F.cin, F.m, 0, F.dca, F.cin, true);
+            g.accumulate = 1;
+            cond_grad(D, g);
+        }
+        // front conv: y_a rows are padded to 8 channels (16 bytes: the unit the TN GEMM moves), so every block's front weight
+        // gradient is one more job of the group; front_rows maps logical row tap Ch + c to GEMM row tap max(Ch, 8) + c'
+        const int kxp = ch < 8 ? 8 : ch;
+        D.add_wn(D.tn.add(w.ya_bf, kxp, w.dh[0], 256, kxp, 256, 3, -1, 1), &td->front, 3 * ch, 256, 0, 1.0f, t->front_rows[F.i], nullptr);
+        return FWN_OK;
+    }
+    // front conv's data gradient, then ActNorm of both planes back to the flow's inputs, with the row-range partials of its
+    // b / logs gradients and of the ZeroConv scale gradient
+    int chain_end(const FlowCtx& F) {
+        const fwn_flow_train_desc* td = F.td;
+        {
+            Seg sg[3];
+            for (int tap = 0; tap < 3; ++tap) sg[tap] = {F.w->dh[0], F.m, 256, 256, -(tap - 1), tap * 256};
+            fwn_gemm_desc g = gemm_desc(sg, 3, td->WfT, 768, F.ch, F.m, (int)F.ti, F.ga, F.ch, true);
+            g.accumulate = 1;
+            fwn_gemm_launch(&g, st);
+        }
+        TREQUIRE(td->d_an_b && td->d_an_logs && td->d_zscale, "fwn_train_loss_and_grads: flow (%d,%d): missing small gradient pointers", F.i, F.j);
+        if (len) fwn_small_grads_main_ragged(F.ga, F.xa, F.gb, F.xb, pl.dzz, F.d->an, B, F.ti, F.ch, len, 2 * F.ch, F.w->sg, st);
+        else fwn_small_grads_main(F.ga, F.xa, F.gb, F.xb, pl.dzz, F.d->an, F.m, F.ch, F.w->sg, st);
+        return FWN_OK;
+    }
+
+    // ---- the weight gradients of a flow in three stages: (1) totals of the small gradients + the conditioning-gradient GEMMs,
     // (2) the grouped TN GEMM(s) into fp32 partials, (3) the grouped weight-norm backward(s) that total them.  One stream:
     // (1)-(3) behind the flow's chain.  Side stream: (1) of every flow of the block, then (2) of ALL its flows as ONE launch
     // (fwn_tn_multi_launch: the block fills the chip with a sixth of the splits a flow on its own would need - a sixth of the
     // partials to write and to read back), then (3) flow by flow.  `part`: where the flow's partials go (advanced).
-    auto wg_small = [&](Deferred& D, hipStream_t s_) {
+    void wg_small(Deferred& D, hipStream_t s_) {
         if (side)       // (one stream: totalled right behind their first pass, on the chain)
             fwn_small_grads_final(D.an, D.m, D.ch, (const long long*)t->br[D.i], (const long long*)t->zcol[D.i], D.w->sg, D.td->d_an_b, D.td->d_an_logs,
                                   D.td->d_zscale, s_);
         for (int k = 0; k < D.ndca; ++k) fwn_gemm_launch(&D.dca[k], s_);
-    };
-    auto wg_place = [&](Deferred& D, float*& part) {          // split count of the block, partial regions of this flow's jobs
+    }
+    void wg_place(Deferred& D, float*& part) {          // split count of the block, partial regions of this flow's jobs
         TnList& tn = D.tn;
         TnSpec sp[4 + 5 * FWN_MAX_LAYERS];
         for (int k = 0; k < tn.n; ++k) sp[k] = {tn.job[k].Kx, tn.job[k].N, tn.job[k].ntap};
@@ -552,8 +781,8 @@ static int train_impl(const fwn_train_desc* t, int64_t B_, int64_t T_, const flo
             q.part = part; q.split_stride = size; q.nsplit = ns;
             part += (size_t)ns * size;
         }
-    };
-    auto wg_wn = [&](Deferred& D, hipStream_t s_) -> int {
+    }
+    int wg_wn(Deferred& D, hipStream_t s_) {
         TnList& tn = D.tn;
         for (int w0 = 0; w0 < D.nwn; w0 += FWN_MAX_GROUP) {
             const int cnt = D.nwn - w0 < FWN_MAX_GROUP ? D.nwn - w0 : FWN_MAX_GROUP;
@@ -577,17 +806,18 @@ static int train_impl(const fwn_train_desc* t, int64_t B_, int64_t T_, const flo
             fwn_wn_group_launch(jobs, cnt, pl.wn_scratch, s_);
         }
         return FWN_OK;
-    };
-    auto weight_grads = [&](Deferred& D, hipStream_t s_) -> int {        // one flow, start to end (the one-stream path)
+    }
+    int weight_grads(Deferred& D, hipStream_t s_) {        // one flow, start to end (the one-stream path)
         wg_small(D, s_);
         float* part = pl.tn_part;
         wg_place(D, part);
         for (int g0 = 0; g0 < D.tn.n; g0 += FWN_MAX_GROUP)
             fwn_tn_group_launch(D.tn.job + g0, D.tn.n - g0 < FWN_MAX_GROUP ? D.tn.n - g0 : FWN_MAX_GROUP, (int)D.m, (int)D.ti, s_);
         return wg_wn(D, s_);
-    };
-    // after_small: recorded on s_ behind stage (1) of the block's last flow (block 0: the conditioning gradient is complete there)
-    auto weight_grads_block = [&](std::vector<Deferred>& flows, hipStream_t s_, hipEvent_t after_small) -> int {      // all flows of a block (side stream)
+    }
+    // all flows of a block (side stream).  after_small: recorded on s_ behind stage (1) of the block's last flow (block 0: the
+    // conditioning gradient is complete there)
+    int weight_grads_block(std::vector<Deferred>& flows, hipStream_t s_, hipEvent_t after_small) {
         if (flows.empty()) return FWN_OK;
         const fwn_tn_job* gj[FWN_MAX_GROUP * 2];
         int gn[FWN_MAX_GROUP * 2], ng = 0;
@@ -623,26 +853,27 @@ static int train_impl(const fwn_train_desc* t, int64_t B_, int64_t T_, const flo
             if (rc != FWN_OK) return rc;
         }
         return FWN_OK;
-    };
-    // side stream: everything enqueued on `st` so far happens before what `side` gets next
-    auto fork_side = [&]() -> bool {
+    }
+
+    // ---- the side-stream protocol ----
+    // everything enqueued on `st` so far happens before what `side` gets next
+    bool fork_side() {
         hipEvent_t e = evp->get();
-        side_guard.armed = true;
+        forked = true;
         return e && hipEventRecord(e, st) == hipSuccess && hipStreamWaitEvent(side, e, 0) == hipSuccess;
-    };
-    auto join_side = [&]() -> bool {
+    }
+    bool join_side() {
         hipEvent_t e = evp->get();
         return e && hipEventRecord(e, side) == hipSuccess && hipStreamWaitEvent(st, e, 0) == hipSuccess;
-    };
-    auto join_pending = [&]() -> bool {      // the block handed over last: join it into `st`, then report it
+    }
+    bool join_pending() {      // the block handed over last: join it into `st`, then report it
         if (pending_block < 0) return true;
         if (!join_side()) return false;
         if (on_block_done && on_block_done(user, pending_block) != 0) hook_failed = true;
         pending_block = -1;
         return true;
-    };
-    hipEvent_t dca_done = nullptr;          // side stream, block 0: behind the last conditioning-gradient GEMM of the call
-    auto hand_over = [&](bool last_block) -> int {          // fork, then everything in `pending` to the side stream
+    }
+    int hand_over(bool last_block) {          // fork, then everything in `pending` to the side stream
         if (!fork_side()) return fwn_set_error(FWN_ERR_HIP, "fwn_train_loss_and_grads: forking the side stream failed");
         if (last_block) {
             dca_done = evp->get();
@@ -652,162 +883,12 @@ static int train_impl(const fwn_train_desc* t, int64_t B_, int64_t T_, const flo
         if (rc != FWN_OK) return rc;
         pending.clear();
         return FWN_OK;
-    };
-    // d loss / d z = z / (B T)   (log_p = mean 0.5 (-log 2 pi - z^2))
-    if (len) hipLaunchKernelGGL(dz_init_ragged_kernel, dim3(grid_of(B * T)), dim3(256), 0, st, pl.gplanes, (const float*)pl.planes, B, T / 2, len);
-    else hipLaunchKernelGGL(scale_copy_kernel, dim3(grid_of(B * T)), dim3(256), 0, st, pl.gplanes, pl.planes, B * T, (float)(1.0 / (double)(B * T)));
-    if (hipMemsetAsync(pl.dcplanes, 0, (size_t)2 * B * T * half * 4, st) != hipSuccess) return fwn_set_error(FWN_ERR_HIP, "hipMemsetAsync failed");
-    for (int i = md->n_block - 1; i >= 0; --i) {
-        const int ch = 1 << i;
-        const long ti = T / (2 * ch), m = B * ti;
-        const int cin = half * (2 << i);
-        const int ldz = 2 * ch > 8 ? 2 * ch : 8;
-        for (int j = NF - 1; j >= 0; --j) {
-            const fwn_flow_desc* d = &md->flows[i * NF + j];
-            const fwn_flow_train_desc* td = &t->flows[i * NF + j];
-            const FlowSaved& s = saved[i * NF + j];
-            const BwdSet& w = side ? pl.sets[(size_t)i * NF + j] : pl.sets[0];
-            const int pp = s.p;
-            float* xa = pl.planes + (size_t)pp * plane_elems;          // y_a
-            float* xb = pl.planes + (size_t)(pp ^ 1) * plane_elems;    // out_b
-            float* ga = pl.gplanes + (size_t)pp * plane_elems;
-            float* gb = pl.gplanes + (size_t)(pp ^ 1) * plane_elems;
-            const void* ca = (const bf16*)pl.cplanes + (size_t)pp * cplane_elems;
-            float* dca = pl.dcplanes + (size_t)pp * cplane_elems;
-            // coupling
-            // (also: the bf16 copy of y_a for the front conv's weight gradient, and the zero padding of dZ's rows)
-            if (len) fwn_ew_coupling_bwd_ragged(gb, xb, s.z, td->ez, B, ti, ch, len, 2 * ch, w.dz, ldz, pl.dzz, xa, w.ya_bf, ch < 8 ? 8 : ch, st);
-            else fwn_ew_coupling_bwd_ex(gb, xb, s.z, td->ez, m * ch, ch, (float)(1.0 / (2.0 * (double)m * ch)), w.dz, ldz, pl.dzz, xa, w.ya_bf, ch < 8 ? 8 : ch, st);
-            {
-                Seg a{w.dz, m, ldz, ldz, 0, 0};
-                fwn_gemm_desc g = gemm_desc(&a, 1, td->WzT, ldz, 256, m, 0, w.du, 256, false);
-                g.mask = s.u_act; g.ldmask = 256;
-                fwn_gemm_launch(&g, st);
-            }
-            pending.emplace_back();
-            Deferred& D = pending.back();
-            D.nwn = 0; D.m = m; D.ti = ti; D.ch = ch; D.i = i; D.w = &w; D.td = td; D.ndca = 0; D.an = d->an;
-            TnList& tn = D.tn;
-            auto add_wn = [&](int tnj, const fwn_conv_grad* c, int k, int n, int col0, float scale, const int32_t* row_src, const int32_t* col_src) {
-                D.wn[D.nwn++] = WnItem{tnj, nullptr, 0, 0, 0, 0, c, k, n, col0, scale, row_src, col_src};
-            };
-            add_wn(tn.add(s.u_act, 256, w.dz, ldz, 256, ldz, 1, 0, 0), &td->zero, 256, 2 * ch, 0, 1.0f, nullptr, t->zinv32[i]);
-            add_wn(tn.add(s.s_act, 256, w.du, 256, 256, 256, 1, 0, 0), &td->final_, 256, 256, 0, 1.0f, nullptr, nullptr);
-            {
-                Seg a{w.du, m, 256, 256, 0, 0};
-                fwn_gemm_desc g = gemm_desc(&a, 1, td->WfinT, 256, 256, m, 0, w.ds, 256, false);
-                g.mask = s.s_act; g.ldmask = 256;
-                fwn_gemm_launch(&g, st);
-                Seg a2{w.ds, m, 256, 256, 0, 0};
-                g = gemm_desc(&a2, 1, td->WskipT_all, 256, L * 256, m, 0, pl.d_all, L * 256, false);      // do_l = dS Wskip_l for every layer at once
-                // the last layer's do is complete here: its gate derivative rides this epilogue (no store + fwn_gate_bwd)
-                g.gate_aux = s.aux[L - 1]; g.gate_out = w.dpre[L - 1]; g.gate_col0 = (L - 1) * 256;
-                fwn_gemm_launch(&g, st);
-            }
-            for (int l = 0; l < L; ++l) add_wn(tn.add(s.o[l], 256, w.ds, 256, 256, 256, 1, 0, 0), &td->skip[l], 256, 256, 0, 1.0f, nullptr, nullptr);
-            const void* dh_next = nullptr;
-            for (int l = L - 1; l >= 0; --l) {
-                const int dil = dilation_of(l);
-                const void* d_ol = (const bf16*)pl.d_all + (size_t)l * 256;
-                int ld_do = L * 256;
-                if (dh_next) {      // h_{l+1} = (h_l + res(o_l)) sqrt(1/2)
-                    add_wn(tn.add(s.o[l], 256, dh_next, 256, 256, 256, 1, 0, 0), &td->res[l], 256, 256, 0, SQH, nullptr, nullptr);
-                    Seg a{dh_next, m, 256, 256, 0, 0};
-                    fwn_gemm_desc g = gemm_desc(&a, 1, td->WresT[l], 256, 256, m, 0, pl.d_o[l], 256, false);
-                    g.R = d_ol; g.ldr = ld_do; g.rscale = (float)(1.0 / 0.7071067811865476); g.oscale = SQH;
-                    g.gate_aux = s.aux[l]; g.gate_out = w.dpre[l]; g.gate_col0 = 0;      // do_l goes straight through the gate derivative
-                    fwn_gemm_launch(&g, st);
-                } else if (t->zero_dead_res) {      // dead res_conv of the last layer (modules.py:126-128): zero gradients
-                    const fwn_conv_grad& c = td->res[l];
-                    if (c.dV && hipMemsetAsync(c.dV, 0, (size_t)256 * 256 * 4, st) != hipSuccess) return fwn_set_error(FWN_ERR_HIP, "hipMemsetAsync failed");
-                    if (c.dg && hipMemsetAsync(c.dg, 0, 256 * 4, st) != hipSuccess) return fwn_set_error(FWN_ERR_HIP, "hipMemsetAsync failed");
-                    if (c.db && hipMemsetAsync(c.db, 0, 256 * 4, st) != hipSuccess) return fwn_set_error(FWN_ERR_HIP, "hipMemsetAsync failed");
-                }
-                const int jd = tn.add(s.h[l], 256, w.dpre[l], 512, 256, 512, 3, -dil, dil);
-                add_wn(jd, &td->filt[l], 768, 256, 0, 1.0f, nullptr, nullptr);
-                add_wn(jd, &td->gate[l], 768, 256, 256, 1.0f, nullptr, nullptr);
-                const int jc = tn.add(ca, cin, w.dpre[l], 512, cin, 512, 1, 0, 0);
-                add_wn(jc, &td->filt_c[l], cin, 256, 0, 1.0f, t->cond_rows[i], nullptr);
-                add_wn(jc, &td->gate_c[l], cin, 256, 256, 1.0f, t->cond_rows[i], nullptr);
-                {
-                    const bool merged = td->wct_ld == L * 512;          // the layers' WcT side by side: one GEMM below, after the loop
-                    if (!merged) {
-                        Seg a{w.dpre[l], m, 512, 512, 0, 0};
-                        fwn_gemm_desc g = gemm_desc(&a, 1, td->WcT[l], td->wct_ld ? td->wct_ld : 512, cin, m, 0, dca, cin, true);
-                        g.accumulate = 1;
-                        // nothing in the flow chain reads the conditioning gradient: with a side stream it leaves the chain
-                        if (side) D.dca[D.ndca++] = g;
-                        else fwn_gemm_launch(&g, st);
-                    }
-                    Seg sg[3];
-                    for (int tap = 0; tap < 3; ++tap) sg[tap] = {w.dpre[l], m, 512, 512, -(tap - 1) * dil, tap * 512};
-                    fwn_gemm_desc g = gemm_desc(sg, 3, td->WdT[l], 1536, 256, m, (int)ti, w.dh[l], 256, false);
-                    if (dh_next) { g.R = dh_next; g.ldr = 256; g.rscale = SQH; }
-                    if (l == 0) { g.mask = s.h[0]; g.ldmask = 256; }
-                    // ragged: the forward zeroed h_l past each clip's end, so dh_l is stored as 0 there (in this launch's epilogue)
-                    if (len) { g.row_len = len; g.len_spr = 2 * ch; }
-                    fwn_gemm_launch(&g, st);
-                }
-                dh_next = w.dh[l];
-            }
-            // front conv
-            if (td->wct_ld == L * 512) {      // conditioning gradient of the flow: dca += [dpre_0 | dpre_1 | ..] [Wc_0 ; Wc_1 ; ..]
-                Seg sg[FWN_MAX_LAYERS];
-                for (int l = 0; l < L; ++l) {
-                    TREQUIRE((const char*)td->WcT[l] == (const char*)td->WcT[0] + (size_t)l * 512 * 2, "fwn_train_loss_and_grads: wct_ld = L*512 needs WcT[l] = WcT[0] + l*512");
-                    sg[l] = {w.dpre[l], m, 512, 512, 0, l * 512};
-                }
-                fwn_gemm_desc g = gemm_desc(sg, L, td->WcT[0], L * 512, cin, m, 0, dca, cin, true);
-                g.accumulate = 1;
-                if (side) D.dca[D.ndca++] = g;
-                else fwn_gemm_launch(&g, st);
-            }
-            // front conv: y_a rows are padded to 8 channels (16 bytes: the unit the TN GEMM moves), so every block's front weight
-            // gradient is one more job of the group; front_rows maps logical row tap Ch + c to GEMM row tap max(Ch, 8) + c'
-            const int kxp = ch < 8 ? 8 : ch;
-            add_wn(tn.add(w.ya_bf, kxp, dh_next, 256, kxp, 256, 3, -1, 1), &td->front, 3 * ch, 256, 0, 1.0f, t->front_rows[i], nullptr);
-            if (!side) {
-                const int rc = weight_grads(D, st);
-                if (rc != FWN_OK) return rc;
-                pending.clear();
-            }
-            {
-                Seg sg[3];
-                for (int tap = 0; tap < 3; ++tap) sg[tap] = {dh_next, m, 256, 256, -(tap - 1), tap * 256};
-                fwn_gemm_desc g = gemm_desc(sg, 3, td->WfT, 768, ch, m, (int)ti, ga, ch, true);
-                g.accumulate = 1;
-                fwn_gemm_launch(&g, st);
-            }
-            // ActNorm of both planes back to the flow's inputs, with its b / logs gradients and the ZeroConv scale gradient
-            TREQUIRE(td->d_an_b && td->d_an_logs && td->d_zscale, "fwn_train_loss_and_grads: flow (%d,%d): missing small gradient pointers", i, j);
-            if (len) fwn_small_grads_main_ragged(ga, xa, gb, xb, pl.dzz, d->an, B, ti, ch, len, 2 * ch, w.sg, st);
-            else fwn_small_grads_main(ga, xa, gb, xb, pl.dzz, d->an, m, ch, w.sg, st);
-            if (!side) fwn_small_grads_final(d->an, m, ch, (const long long*)t->br[i], (const long long*)t->zcol[i], w.sg, td->d_an_b, td->d_an_logs,
-                                             td->d_zscale, st);
-            if (!side && j == 0 && on_block_done && on_block_done(user, i) != 0) hook_failed = true;
-            if (hook_failed) return hook_stop();
-            if (side && j == 0) {      // this block's weight gradients: under the next block's chain
-                if (!join_pending()) return fwn_set_error(FWN_ERR_HIP, "fwn_train_loss_and_grads: joining the side stream failed");
-                if (hook_failed) return hook_stop();
-                const int rc = hand_over(i == 0);
-                if (rc != FWN_OK) return rc;
-                pending_block = i;
-            }
-        }
     }
-    // The conditioning gradient is complete behind stage (1) of block 0's weight gradients (side stream): the up-sampling
-    // backward waits for THAT event and runs under the rest of block 0's side work (its grouped TN GEMM and weight-norm
-    // backward: ~1 ms in which the chain's queue had nothing to do); block 0 is joined and reported behind it.
-    if (side && dca_done) {
-        if (hipStreamWaitEvent(st, dca_done, 0) != hipSuccess) return fwn_set_error(FWN_ERR_HIP, "fwn_train_loss_and_grads: hipStreamWaitEvent failed");
-    } else if (side) {
-        if (!join_pending()) return fwn_set_error(FWN_ERR_HIP, "fwn_train_loss_and_grads: joining the side stream failed");
-        if (hook_failed) return hook_stop();
-    }
-    // up-sampling transposed convolutions (model.py:301-311), last stage first
-    hipLaunchKernelGGL(planes_to_rows_kernel, dim3(grid_of(B * T * nmel)), dim3(256), 0, st, pl.dcplanes, (const bf16*)pl.cplanes, B * T, half, pl.up_dy,
-                       pl.up_y);
-    {
+
+    // ---------------- up-sampling transposed convolutions (model.py:301-311), last stage first ----------------
+    int upsample_backward() {
+        hipLaunchKernelGGL(planes_to_rows_kernel, dim3(grid_of(B * T * nmel)), dim3(256), 0, st, pl.dcplanes, (const bf16*)pl.cplanes, B * T, half, pl.up_dy,
+                           pl.up_y);
         float* dy = pl.up_dy;
         const float* y = pl.up_y;
         for (int n = md->n_up - 1; n >= 0; --n) {
@@ -821,7 +902,7 @@ static int train_impl(const fwn_train_desc* t, int64_t B_, int64_t T_, const flo
             fwn_up_bwd_launch(dy, y, xin, (int)B, (int)hh, nmel, s_, md->up_w[n], dx, pl.up_dwb, pl.up_scr, st);
             // ragged: the forward zeroed this stage's input past each clip's end - its gradient is dropped there before the
             // stage below reads it
-            if (dx) mask(dx, B, hh, (long)nmel * 4, (int)(T / hh));
+            if (dx) rows.zero(dx, hh, (long)nmel * 4, (int)(T / hh));
             hipLaunchKernelGGL(up_prepare_kernel, dim3(1), dim3(64), 0, st, c.g, pl.up_g3);
             fwn_wn_job q;
             memset(&q, 0, sizeof(q));
@@ -832,32 +913,37 @@ static int train_impl(const fwn_train_desc* t, int64_t B_, int64_t T_, const flo
             dy = dx;
             y = xin;
         }
+        return FWN_OK;
     }
-    if (side && !join_pending()) return fwn_set_error(FWN_ERR_HIP, "fwn_train_loss_and_grads: joining the side stream failed");
-    if (hook_failed) return hook_stop();
-    if (on_block_done && on_block_done(user, -1) != 0) return hook_stop();
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fwn_set_error(FWN_ERR_HIP, "fwn_train_loss_and_grads: %s", hipGetErrorString(e));
-    side_guard.armed = false;             // every block was joined on the way (join_pending)
-    return FWN_OK;
+};
+
+int train_call(PassKind kind, const fwn_train_desc* t, int64_t B, int64_t T, const float* x, const float* mel, const int32_t* len, void* workspace,
+               size_t workspace_bytes, float* out3, float* out2B, fwn_block_done_fn on_block_done, void* user, void* stream) {
+    TrainCall c;
+    c.kind = kind; c.t = t; c.B = (long)B; c.T = (long)T; c.x = x; c.mel = mel; c.len = len;
+    c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.out3 = out3; c.out2B = out2B;
+    c.on_block_done = on_block_done; c.user = user; c.st = (hipStream_t)stream;
+    return c.run();
 }
+
+}  // namespace
 
 extern "C" {
 
-size_t fwn_train_workspace_bytes(const fwn_train_desc* t, int64_t B, int64_t T) { return train_workspace(t, B, T, false); }
+size_t fwn_train_workspace_bytes(const fwn_train_desc* t, int64_t B, int64_t T) { return train_workspace(t, B, T, PASS_TRAIN); }
 size_t fwn_train_ragged_workspace_bytes(const fwn_train_desc* t, int64_t B, int64_t T) {
     if (B >= 32768 || (t && t->model && t->model->gate_fp8)) return 0;
-    return train_workspace(t, B, T, true);
+    return train_workspace(t, B, T, PASS_TRAIN_RAGGED);
 }
 int fwn_train_loss_and_grads(const fwn_train_desc* t, int64_t B, int64_t T, const float* x, const float* mel, void* workspace,
                              size_t workspace_bytes, float* out3, fwn_block_done_fn on_block_done, void* user, void* stream) {
-    return train_impl(t, B, T, x, mel, nullptr, workspace, workspace_bytes, out3, nullptr, on_block_done, user, stream);
+    return train_call(PASS_TRAIN, t, B, T, x, mel, nullptr, workspace, workspace_bytes, out3, nullptr, on_block_done, user, stream);
 }
 int fwn_train_loss_and_grads_ragged(const fwn_train_desc* t, int64_t B, int64_t T, const float* x, const float* mel, const int32_t* len_dev,
                                     void* workspace, size_t workspace_bytes, float* out3, float* out2B, fwn_block_done_fn on_block_done,
                                     void* user, void* stream) {
     TREQUIRE(len_dev, "fwn_train_loss_and_grads_ragged: null lengths");
-    return train_impl(t, B, T, x, mel, len_dev, workspace, workspace_bytes, out3, out2B, on_block_done, user, stream);
+    return train_call(PASS_TRAIN_RAGGED, t, B, T, x, mel, len_dev, workspace, workspace_bytes, out3, out2B, on_block_done, user, stream);
 }
 
 }  // extern "C"

@@ -2,8 +2,10 @@
 
     python tools/dispatch_tables.py LIB OUT
 
-Writes fwn_workspace_bytes / fwn_train_workspace_bytes over BASELINE-like and small configs (B 1 - 16, several T, every
-cond_mode / persist_mode / chain_mode, with and without tail / conditioning streams and the fp8 gate), the per-block
+Writes fwn_workspace_bytes / fwn_train_workspace_bytes and the four ragged workspace queries (fwn_ragged_workspace_bytes,
+fwn_ragged_forward_workspace_bytes, fwn_ragged_init_workspace_bytes, fwn_train_ragged_workspace_bytes) over BASELINE-like and
+small configs (B 1 - 16, several T, every cond_mode / persist_mode / chain_mode, with and without tail / conditioning streams
+and the fp8 gate), the per-block
 fwn_flow_persist_supported / fwn_cond_stream_splits, and the four tail queries plus the split counts over M = 1 .. 2^17.
 Descriptors carry dummy aligned weight pointers: the host never dereferences them.  A change to host dispatch that must
 not change what runs keeps the table identical:  python tools/dispatch_tables.py <old lib> a.txt; ... <new lib> b.txt;
@@ -22,6 +24,12 @@ lib.fwn_workspace_bytes.restype = C.c_size_t
 lib.fwn_workspace_bytes.argtypes = [C.POINTER(MD), C.c_int64, C.c_int64]
 lib.fwn_train_workspace_bytes.restype = C.c_size_t
 lib.fwn_train_workspace_bytes.argtypes = [C.POINTER(TD), C.c_int64, C.c_int64]
+RAGGED = ("fwn_ragged_workspace_bytes", "fwn_ragged_forward_workspace_bytes", "fwn_ragged_init_workspace_bytes")
+for q in RAGGED:
+    getattr(lib, q).restype = C.c_size_t
+    getattr(lib, q).argtypes = [C.POINTER(MD), C.c_int64, C.c_int64]
+lib.fwn_train_ragged_workspace_bytes.restype = C.c_size_t
+lib.fwn_train_ragged_workspace_bytes.argtypes = [C.POINTER(TD), C.c_int64, C.c_int64]
 lib.fwn_flow_persist_supported.argtypes = [C.POINTER(FD), C.c_int64, C.c_int64]
 FAKE = [0x7f0000000000]
 def fp():
@@ -74,6 +82,10 @@ for (name, nb, nf, L, mels, ups, Bs, Ts) in cfgs:
                 ws = lib.fwn_workspace_bytes(C.byref(m), B, T)
                 tw = lib.fwn_train_workspace_bytes(C.byref(t), B, T) if (cm, pm, chm, cs, fp8) == (0, 0, 0, 0, 0) else -1
                 out.write("ws %s cm%d pm%d ch%d wts%d cs%d fp8%d B%d T%d %d %d\n" % (name, cm, pm, chm, wts, cs, fp8, B, T, ws, tw))
+                # the ragged queries on the same rows (the training one where the training query is asked)
+                rw = [getattr(lib, q)(C.byref(m), B, T) for q in RAGGED]
+                rt = lib.fwn_train_ragged_workspace_bytes(C.byref(t), B, T) if tw != -1 else -1
+                out.write("rws %s cm%d pm%d ch%d wts%d cs%d fp8%d B%d T%d %d %d %d %d\n" % (name, cm, pm, chm, wts, cs, fp8, B, T, *rw, rt))
                 if (cm, pm, chm, cs, fp8) == (0, 0, 0, 0, 0):
                     for i in range(nb):
                         d = m.flows[i * nf]
