@@ -686,6 +686,39 @@ int fwn_train_loss_and_grads_ragged(const fwn_train_desc* t, int64_t B, int64_t 
                                     const int32_t* len_dev, void* workspace, size_t workspace_bytes, float* out3, float* out2B,
                                     fwn_block_done_fn on_block_done, void* user, void* stream);
 
+/* ---- device-side synthesis (additive; FWN_VERSION unchanged): the latent z drawn on the device, 16-bit PCM written there, and
+ * both around the inverse pass in one call - only the mel has to go up and only int16 has to come down.
+ *
+ * fwn_latent_normal: z [B][T] fp32 = temp * N(0,1) from Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, Weyl constants
+ * 0x9E3779B9 / 0xBB67AE85, ten rounds).  Key = (seed & 0xffffffff, seed >> 32); counter = (q, 0, clip_id[b], 0) with q = i / 4
+ * for sample i of clip b; clip_id_dev is a DEVICE uint32 [B], NULL: clip_id[b] = b.  The four output words r0..r3 give samples
+ * 4q .. 4q+3: for the pairs (r0, r1) and (r2, r3), u1 = ((r >> 8) + 1) 2^-24 in (0, 1], u2 = (r' >> 8) 2^-24, rad =
+ * sqrt(-2 ln u1), and the two samples are rad cos(2 pi u2) and rad sin(2 pi u2), times temp.  Sample i of a clip depends on
+ * (seed, clip_id, i, temp) only - not on B, the clip's row, T or the pointer's alignment: a clip draws the same z whichever
+ * batch it lands in.  The stream is this library's own (neither TensorFlow's nor torch's).  Any T in [1, 2^34] and any 4-byte
+ * aligned z; B < 65536.  len_dev (may be NULL): DEVICE int32 [B], read and clamped to [0, T] on the device as in fwn_mask_rows; samples
+ * at i >= len[b] are +0.0f, the ones before it have the bits they have without len.  fp32 evaluation with accurate log / sqrt /
+ * sincos: within 1e-5 temp of the fp64 value of the formula (tests/philox_ref.py).
+ *
+ * fwn_pcm16: pcm [B][T] int16 = rint((double)clamp(x, -1, 1) * 32767.0), halves to even, NaN -> 0 - the arithmetic of the
+ * synthesize CLI's float64 wav writer bit for bit.  x 4-byte, pcm 2-byte aligned, any T >= 1, B < 65536; len_dev as above:
+ * samples at i >= len[b] are 0.
+ *
+ * fwn_model_synthesize: fwn_latent_normal -> fwn_model_reverse (len_dev NULL) or fwn_model_reverse_ragged -> fwn_pcm16, enqueued
+ * on one stream.  mel [B][T/hop][num_mels] fp32; pcm_out [B][T] int16; wav_out / z_out (each may be NULL) [B][T] fp32 receive
+ * the waveform and the latent; all three 16-byte aligned.  Without them z and the waveform live in the workspace, behind the
+ * inverse pass's own: fwn_synthesize_workspace_bytes(m, B, T, ragged != 0 for a call with len_dev), 0 for a descriptor or shape
+ * the call would refuse.  Refusals (FWN_ERR_ARG, before anything is launched): those of the two inverse entries - a gate_fp8
+ * descriptor with len_dev, odd n_block * n_flow, B >= 32768 - and null or misaligned pointers.  Lengths are validated by the
+ * caller as for fwn_model_reverse_ragged.  CLI-level speed: tools/bench_synth.py. */
+int fwn_latent_normal(float* z, int64_t B, int64_t T, uint64_t seed, const uint32_t* clip_id_dev, float temp,
+                      const int32_t* len_dev, void* stream);
+int fwn_pcm16(const float* x, int16_t* pcm, int64_t B, int64_t T, const int32_t* len_dev, void* stream);
+size_t fwn_synthesize_workspace_bytes(const fwn_model_desc* m, int64_t B, int64_t T, int ragged);
+int fwn_model_synthesize(const fwn_model_desc* m, int64_t B, int64_t T, const float* mel, uint64_t seed,
+                         const uint32_t* clip_id_dev, float temp, const int32_t* len_dev, void* workspace, size_t workspace_bytes,
+                         int16_t* pcm_out, float* wav_out, float* z_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

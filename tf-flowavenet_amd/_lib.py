@@ -249,6 +249,10 @@ SIGNATURES = {
     "fwn_actnorm_moments_ragged": (C.c_int, [vp, vp, i64, i64, C.c_int, vp, i32, vp, vp, i64, vp]),
     "fwn_ragged_init_workspace_bytes": (C.c_size_t, [C.POINTER(ModelDesc), i64, i64]),
     "fwn_model_forward_init_ragged": (C.c_int, [C.POINTER(ModelDesc), i64, i64, vp, vp, vp, vp, C.c_size_t, vp, vp, vp, vp, vp]),
+    "fwn_latent_normal": (C.c_int, [vp, i64, i64, C.c_uint64, vp, C.c_float, vp, vp]),
+    "fwn_pcm16": (C.c_int, [vp, vp, i64, i64, vp, vp]),
+    "fwn_synthesize_workspace_bytes": (C.c_size_t, [C.POINTER(ModelDesc), i64, i64, C.c_int]),
+    "fwn_model_synthesize": (C.c_int, [C.POINTER(ModelDesc), i64, i64, vp, C.c_uint64, vp, C.c_float, vp, vp, C.c_size_t, vp, vp, vp, vp]),
 }
 
 _lib = None

@@ -1340,4 +1340,54 @@ int fwn_model_forward_init_ragged(const fwn_model_desc* m, int64_t B, int64_t T,
     return model_pass(PASS_INIT_RAGGED, m, B, T, x, mel, len_dev, workspace, workspace_bytes, reduce, user, out2B, z_planes, nullptr, stream);
 }
 
+// ---- device-side synthesis: z drawn on the device -> the inverse pass -> 16-bit PCM (include/fwn.h) ----
+int fwn_latent_normal(float* z, int64_t B, int64_t T, uint64_t seed, const uint32_t* clip_id_dev, float temp, const int32_t* len_dev,
+                      void* stream) {
+    REQUIRE(z && B > 0 && B < 65536 && T > 0, "fwn_latent_normal: bad argument");
+    REQUIRE((((uintptr_t)z) & 3) == 0, "fwn_latent_normal: z must be 4-byte aligned");
+    REQUIRE(T <= ((int64_t)1 << 34), "fwn_latent_normal: T=%lld exceeds the 2^32 quads one clip's counter word numbers", (long long)T);
+    fwn_launch_latent_normal(z, (long)B, (long)T, (unsigned long long)seed, clip_id_dev, temp, len_dev, (hipStream_t)stream);
+    return check_launch("fwn_latent_normal");
+}
+int fwn_pcm16(const float* x, int16_t* pcm, int64_t B, int64_t T, const int32_t* len_dev, void* stream) {
+    REQUIRE(x && pcm && B > 0 && B < 65536 && T > 0, "fwn_pcm16: bad argument");
+    REQUIRE((((uintptr_t)x) & 3) == 0 && (((uintptr_t)pcm) & 1) == 0, "fwn_pcm16: x must be 4-byte and pcm 2-byte aligned");
+    fwn_launch_pcm16(x, (short*)pcm, (long)B, (long)T, len_dev, (hipStream_t)stream);
+    return check_launch("fwn_pcm16");
+}
+// the inverse pass's own workspace first (so model_pass carves it as ever), then z and the waveform, B T floats each
+static size_t synth_extra(int64_t B, int64_t T) { return align_up((size_t)B * T * 4); }
+size_t fwn_synthesize_workspace_bytes(const fwn_model_desc* m, int64_t B, int64_t T, int ragged) {
+    if (check_model(m, B, T) != FWN_OK || B >= 32768 || (ragged && m->gate_fp8)) return 0;
+    return carve(m, B, T, ragged ? PASS_REVERSE_RAGGED : PASS_REVERSE).total + 2 * synth_extra(B, T);
+}
+int fwn_model_synthesize(const fwn_model_desc* m, int64_t B, int64_t T, const float* mel, uint64_t seed, const uint32_t* clip_id_dev,
+                         float temp, const int32_t* len_dev, void* workspace, size_t workspace_bytes, int16_t* pcm_out, float* wav_out,
+                         float* z_out, void* stream) {
+    // everything the inverse pass would refuse is refused here, before the latent fill is enqueued
+    int rc = check_model(m, B, T);
+    if (rc) return rc;
+    REQUIRE(mel && workspace && pcm_out, "fwn_model_synthesize: null pointer");
+    REQUIRE((((uintptr_t)workspace) & 255) == 0, "fwn_model_synthesize: workspace must be 256-byte aligned");
+    REQUIRE(ALIGNED16(pcm_out) && ALIGNED16(wav_out) && ALIGNED16(z_out), "fwn_model_synthesize: pcm_out, wav_out and z_out must be 16-byte aligned");
+    REQUIRE(B < 32768, "fwn_model_synthesize: B=%lld clips (at most 32767 per call)", (long long)B);
+    REQUIRE(((m->n_block * m->n_flow) & 1) == 0,
+            "fwn_model_synthesize: reverse with odd n_block*n_flow ends in swapped channel order (model.py:199,254); unsupported");
+    REQUIRE(!len_dev || !m->gate_fp8,
+            "fwn_model_synthesize: per-clip lengths go with a model without fp8 gates (its e4m3 copies of h are not masked)");
+    const PassKind kind = len_dev ? PASS_REVERSE_RAGGED : PASS_REVERSE;
+    const size_t base = carve(m, B, T, kind).total, extra = synth_extra(B, T);
+    if (workspace_bytes < base + 2 * extra)
+        return fail(FWN_ERR_WORKSPACE, "fwn_model_synthesize: workspace %zu < required %zu bytes", workspace_bytes, base + 2 * extra);
+    float* z = z_out ? z_out : (float*)((char*)workspace + base);
+    float* wav = wav_out ? wav_out : (float*)((char*)workspace + base + extra);
+    fwn_launch_latent_normal(z, (long)B, (long)T, (unsigned long long)seed, clip_id_dev, temp, len_dev, (hipStream_t)stream);
+    rc = check_launch("fwn_model_synthesize (latent)");
+    if (rc) return rc;
+    rc = model_pass(kind, m, B, T, z, mel, len_dev, workspace, base, nullptr, nullptr, nullptr, nullptr, wav, stream);
+    if (rc) return rc;
+    fwn_launch_pcm16(wav, (short*)pcm_out, (long)B, (long)T, len_dev, (hipStream_t)stream);
+    return check_launch("fwn_model_synthesize");
+}
+
 }  // extern "C"

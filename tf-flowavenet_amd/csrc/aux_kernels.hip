@@ -491,6 +491,111 @@ __global__ __launch_bounds__(256) void mask_rows_kernel(char* __restrict__ buf, 
     }
 }
 
+// ---- synthesis: the latent z drawn on the device ------------------------------------------------------------
+// z [B][T] fp32 = temp * N(0,1) from Philox4x32-10 (include/fwn.h fwn_latent_normal has the stream's definition; the fp64
+// restatement the tests compare against is tests/philox_ref.py).  Sample i of a clip comes from counter (i / 4, 0, clip_id, 0)
+// alone, so it does not depend on B, on the clip's row, on T or on where the buffer starts.  blockIdx.y = clip and the
+// workgroups of a clip stride over its quads (mask_rows_kernel's grid); one lane runs one Philox call and stores its four
+// samples as one 16-byte piece where that piece is whole and 16-byte aligned, as single dwords otherwise (the last quad of
+// a T that is no multiple of 4; every quad of a row that does not start on 16 bytes).  Samples at i >= len[b] (clamped to
+// [0, T] here, so no value of it stores outside) are +0.  logf / sqrtf / sincospif are the library's accurate forms (the build
+// has no fast-math): |z - fp64| stays within a few ulp of |z| <= 5.77 temp; 2 u2 is exact, so the sine and cosine see no
+// argument rounding.
+__device__ __forceinline__ uint4 philox4x32_10(uint4 c, unsigned k0, unsigned k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const unsigned hi0 = __umulhi(0xD2511F53u, c.x), lo0 = 0xD2511F53u * c.x;
+        const unsigned hi1 = __umulhi(0xCD9E8D57u, c.z), lo1 = 0xCD9E8D57u * c.z;
+        c = make_uint4(hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0);
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    return c;
+}
+__device__ __forceinline__ void box_muller(unsigned r, unsigned r2, float temp, float& a, float& b) {
+    const float u1 = (float)((r >> 8) + 1u) * 0x1p-24f;          // (0, 1], exact
+    const float u2x2 = (float)(r2 >> 8) * 0x1p-23f;              // 2 u2 in [0, 2), exact
+    const float rad = sqrtf(-2.0f * logf(u1));
+    float s, c;
+    sincospif(u2x2, &s, &c);
+    a = rad * c * temp;
+    b = rad * s * temp;
+}
+__global__ __launch_bounds__(256) void latent_normal_kernel(float* __restrict__ z, long T, unsigned k0, unsigned k1,
+                                                            const unsigned* __restrict__ clip_id, float temp,
+                                                            const int* __restrict__ len) {
+    const long b = blockIdx.y;
+    long keep = len ? (long)len[b] : T;
+    keep = keep < 0 ? 0 : (keep > T ? T : keep);
+    const unsigned clip = clip_id ? clip_id[b] : (unsigned)b;
+    float* row = z + (size_t)b * T;
+    const long nq = (T + 3) >> 2;
+    for (long q = (long)blockIdx.x * 256 + threadIdx.x; q < nq; q += (long)gridDim.x * 256) {
+        const long i0 = q * 4;
+        float v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        if (i0 < keep) {                                          // a quad wholly past the clip's end draws nothing
+            const uint4 r = philox4x32_10(make_uint4((unsigned)q, 0u, clip, 0u), k0, k1);
+            box_muller(r.x, r.y, temp, v[0], v[1]);
+            box_muller(r.z, r.w, temp, v[2], v[3]);
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (i0 + e >= keep) v[e] = 0.0f;
+        }
+        float* p = row + i0;
+        if (i0 + 4 <= T && (((uintptr_t)p) & 15) == 0) {
+            *(float4*)p = make_float4(v[0], v[1], v[2], v[3]);
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (i0 + e < T) p[e] = v[e];
+        }
+    }
+}
+
+// ---- synthesis: fp32 waveform -> 16-bit PCM ------------------------------------------------------------------
+// x [B][T] fp32 -> pcm [B][T] int16 = rint((double)clamp(x, -1, 1) * 32767.0), NaN -> 0: synthesize.write_wav's float64 NumPy
+// arithmetic bit for bit (the fp64 product of an fp32 value and 32767 is exact, so the one rounding is rint's half-to-even;
+// the fp32 product would round twice at near-ties).  Samples at i >= len[b] (clamped as above) are 0.  blockIdx.y = clip.
+// Between the first and the last 16-byte boundary of the clip's pcm row, one lane turns eight samples (two 16-byte loads)
+// into one 16-byte store - where x is 16-byte aligned at that first boundary too; the up to seven samples on either side go
+// one by one, and so does the whole row where x and pcm disagree about their 16-byte phase.
+__device__ __forceinline__ short pcm16_of(float v) {
+    v = (v != v) ? 0.0f : fminf(fmaxf(v, -1.0f), 1.0f);
+    return (short)(int)rint((double)v * 32767.0);
+}
+__global__ __launch_bounds__(256) void pcm16_kernel(const float* __restrict__ x, short* __restrict__ pcm, long T,
+                                                    const int* __restrict__ len) {
+    const long b = blockIdx.y;
+    long keep = len ? (long)len[b] : T;
+    keep = keep < 0 ? 0 : (keep > T ? T : keep);
+    const float* xr = x + (size_t)b * T;
+    short* pr = pcm + (size_t)b * T;
+    // [a0, a1): the samples of the row whose pcm bytes form whole aligned 16-byte pieces
+    long a0 = (long)(((16 - (((uintptr_t)pr) & 15)) & 15) >> 1);
+    if (a0 > T) a0 = T;
+    long a1 = a0 + ((T - a0) & ~7L);
+    if ((((uintptr_t)(xr + a0)) & 15) != 0) a1 = a0 = 0;         // phases disagree: everything goes through the tail loop
+    const long first = (long)blockIdx.x * 256 + threadIdx.x, stride = (long)gridDim.x * 256;
+    for (long g = first; g < ((a1 - a0) >> 3); g += stride) {
+        const long i0 = a0 + g * 8;
+        union { short s[8]; uint4 u; } o;
+        if (i0 >= keep) {
+            o.u = make_uint4(0u, 0u, 0u, 0u);                     // past the clip's end: nothing is loaded
+        } else {
+            const float4 lo = *(const float4*)(xr + i0), hi = *(const float4*)(xr + i0 + 4);
+            const float v[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+#pragma unroll
+            for (int e = 0; e < 8; ++e) o.s[e] = (i0 + e < keep) ? pcm16_of(v[e]) : (short)0;
+        }
+        *(uint4*)(pr + i0) = o.u;
+    }
+    const long nside = a0 + (T - a1);                             // head [0, a0) and tail [a1, T)
+    for (long j = first; j < nside; j += stride) {
+        const long i = j < a0 ? j : a1 + (j - a0);
+        pr[i] = i < keep ? pcm16_of(xr[i]) : (short)0;
+    }
+}
+
 // ---- ragged forward: the rows past each clip's end of a flow's x_a plane hold -shift --------------------
 // The front conv applies ActNorm on the fly, (v + shift[tau]) * scale[tau]: a zero in a padded row would reach its +-1 taps
 // as shift * scale, where a clip on its own is zero-padded AFTER ActNorm.  (-s + s) is exactly +0, so with -shift[tau] in
@@ -946,6 +1051,19 @@ void fwn_launch_mask_rows(void* base, long nclip, long rows, long row_bytes, con
     const long gx = want < 1 ? 1 : (want > cap ? cap : want);
     hipLaunchKernelGGL(mask_rows_kernel, dim3((unsigned)gx, (unsigned)nclip), dim3(256), 0, st, (char*)base, rows, row_bytes, len,
                        nlen, samples_per_row);
+}
+void fwn_launch_latent_normal(float* z, long B, long T, unsigned long long seed, const unsigned* clip_id, float temp, const int* len,
+                              hipStream_t st) {
+    // write-bound: four 16-byte stores per thread, at most ~2048 workgroups over all clips (fwn_launch_mask_rows)
+    const long want = (T * 4 + 16383) / 16384, cap = B < 2048 ? 2048 / B : 1;
+    const long gx = want < 1 ? 1 : (want > cap ? cap : want);
+    hipLaunchKernelGGL(latent_normal_kernel, dim3((unsigned)gx, (unsigned)B), dim3(256), 0, st, z, T, (unsigned)(seed & 0xffffffffull),
+                       (unsigned)(seed >> 32), clip_id, temp, len);
+}
+void fwn_launch_pcm16(const float* x, short* pcm, long B, long T, const int* len, hipStream_t st) {
+    const long want = (T * 2 + 16383) / 16384, cap = B < 2048 ? 2048 / B : 1;              // four 16-byte stores per thread
+    const long gx = want < 1 ? 1 : (want > cap ? cap : want);
+    hipLaunchKernelGGL(pcm16_kernel, dim3((unsigned)gx, (unsigned)B), dim3(256), 0, st, x, pcm, T, len);
 }
 void fwn_launch_fill_neg_shift(float* plane, long nclip, long rows, int Ch, const float* shift, const int* len, int nlen,
                                int samples_per_row, hipStream_t st) {

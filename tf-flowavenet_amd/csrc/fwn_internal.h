@@ -137,6 +137,11 @@ void fwn_launch_merge(const float* planes, long B, long T, float* x, hipStream_t
 // rows past a clip's own length); len is read on the device and clamped to the buffer.  base and row_bytes: multiples of 4.
 void fwn_launch_mask_rows(void* base, long nclip, long rows, long row_bytes, const int* len, int nlen, int samples_per_row,
                           hipStream_t st);
+// synthesis (aux_kernels.hip): z [B][T] = temp * N(0,1), Philox4x32-10 keyed by (seed, clip_id[b]) (NULL: clip b is b), and
+// fp32 [B][T] -> int16 PCM; len (may be NULL) is read on the device and clamped to [0, T]: +0 / 0 from there on.
+void fwn_launch_latent_normal(float* z, long B, long T, unsigned long long seed, const unsigned* clip_id, float temp, const int* len,
+                              hipStream_t st);
+void fwn_launch_pcm16(const float* x, short* pcm, long B, long T, const int* len, hipStream_t st);
 // ragged forward (aux_kernels.hip).  -shift[tau] into rows [len / samples_per_row, rows) of every clip of a [nclip][rows][Ch]
 // fp32 plane: the front conv's on-the-fly ActNorm then gives exact zeros there.  Clamped like fwn_launch_mask_rows.
 void fwn_launch_fill_neg_shift(float* plane, long nclip, long rows, int Ch, const float* shift, const int* len, int nlen,

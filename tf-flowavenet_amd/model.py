@@ -313,6 +313,89 @@ class FloWaveNet:
             _lib.check(rc, "fwn_model_reverse_ragged")
         return x if dtype is None or dtype == torch.float32 else x.to(dtype)
 
+    # ------------------------------------------------------------------ device-side synthesis
+    def _clip_ids(self, clip_ids, b):
+        """``clip_ids`` -> device tensor holding B uint32 (as int32 bits), or None: clip b is b."""
+        import torch
+        if clip_ids is None:
+            return None
+        vals = clip_ids.detach().cpu().tolist() if hasattr(clip_ids, "detach") else np.asarray(clip_ids).tolist()
+        if not isinstance(vals, list) or len(vals) != b:
+            raise ValueError("clip_ids must hold one id per clip (B=%d), got %r" % (b, vals))
+        for v in vals:
+            if int(v) != v or not 0 <= v < (1 << 32):
+                raise ValueError("clip ids are integers in [0, 2^32), got %r" % (v,))
+        return torch.from_numpy(np.asarray([int(v) for v in vals], dtype=np.uint32).view(np.int32)).to(self._device)
+
+    def sample_z(self, b, t, seed, clip_ids=None, lengths=None, temp=None):
+        """The latent of ``b`` clips of ``t`` samples, drawn on the device: fp32 [b, t, 1] = temp * N(0,1) (``temp``: default
+        ``hparams.temp``) from a Philox4x32-10 stream keyed by (``seed`` mod 2^64, clip id) - include/fwn.h
+        ``fwn_latent_normal``.  ``clip_ids`` (B integers in [0, 2^32); None: 0 .. b-1) name the clips: sample i of a clip
+        depends on (seed, clip id, i, temp) only, so a clip draws the same z whichever batch, row or T it is given.
+        ``lengths`` (the rules of ``reverse``): z is +0 from each clip's length on, and unchanged before it."""
+        import torch
+        b, t = int(b), int(t)
+        if b < 1 or t < 1:
+            raise ValueError("b and t must be positive, got %d, %d" % (b, t))
+        ids = self._clip_ids(clip_ids, b)
+        lens = None if lengths is None else torch.tensor(self._check_lengths(lengths, b, t), dtype=torch.int32).to(self._device)
+        z = torch.empty(b, t, 1, dtype=torch.float32, device=self._device)
+        rc = self._lib.fwn_latent_normal(z.data_ptr(), b, t, int(seed) % (1 << 64), None if ids is None else ids.data_ptr(),
+                                         float(self._hparams.temp if temp is None else temp),
+                                         None if lens is None else lens.data_ptr(), self._stream())
+        _lib.check(rc, "fwn_latent_normal")
+        return z
+
+    def synthesize(self, c, seed, clip_ids=None, lengths=None, temp=None, return_wav=False, return_z=False):
+        """c [B,F,num_mels] -> 16-bit PCM, ``torch.int16`` [B, F*hop] on the device, in one call: the latent of ``sample_z(B,
+        F*hop, seed, clip_ids, lengths, temp)``, ``reverse`` (with ``lengths``: the ragged pass, same rules and refusals), and
+        ``rint(clip(x, -1, 1) * 32767)`` in float64 with halves to even (NaN -> 0) - the arithmetic of
+        ``synthesize.write_wav``.  Nothing touches the host.  Past a clip's length the PCM, the waveform and z are 0.
+        return_wav / return_z add the fp32 waveform [B,T,1] / the latent [B,T,1] to the result, in that order."""
+        import torch
+        if self._packed is None:
+            raise RuntimeError("no parameters loaded: call load_params() / init_synthetic() first")
+        hp = self._hparams
+        if c.dim() != 3 or c.shape[2] != hp.num_mels:
+            raise ValueError("c must have shape [B, T/hop, %d], got %r" % (hp.num_mels, tuple(c.shape)))
+        b, t = int(c.shape[0]), int(c.shape[1]) * self.hop
+        if b < 1 or t < 1 or t % (1 << hp.n_block):
+            raise ValueError("T=%d must be a positive multiple of 2^n_block=%d (model.py:226)" % (t, 1 << hp.n_block))
+        c32 = c.to(device=torch.device(self._device), dtype=torch.float32).contiguous()
+        ids = self._clip_ids(clip_ids, b)
+        lens = None
+        if lengths is not None:
+            if self._gate_fp8:
+                raise ValueError("a gate_fp8 model takes no lengths: the e4m3 copies of h are not masked")
+            lens = torch.tensor(self._check_lengths(lengths, b, t), dtype=torch.int32).to(self._device)
+        wsp, wsn = self._synth_workspace(b, t, lens is not None)
+        pcm = torch.empty(b, t, dtype=torch.int16, device=self._device)
+        wav = torch.empty(b, t, 1, dtype=torch.float32, device=self._device) if return_wav else None
+        z = torch.empty(b, t, 1, dtype=torch.float32, device=self._device) if return_z else None
+        rc = self._lib.fwn_model_synthesize(C.byref(self._packed.model_desc), b, t, c32.data_ptr(), int(seed) % (1 << 64),
+                                            None if ids is None else ids.data_ptr(), float(hp.temp if temp is None else temp),
+                                            None if lens is None else lens.data_ptr(), wsp, wsn, pcm.data_ptr(),
+                                            wav.data_ptr() if return_wav else None, z.data_ptr() if return_z else None,
+                                            self._stream())
+        _lib.check(rc, "fwn_model_synthesize")
+        return pcm if not (return_wav or return_z) else (pcm,) + ((wav,) if return_wav else ()) + ((z,) if return_z else ())
+
+    def _synth_workspace(self, b, t, ragged):
+        """``_workspace`` for ``synthesize``: the inverse pass's scratch with z and the fp32 waveform behind it."""
+        import torch
+        key = (b, t, self._stream(), "synth", bool(ragged))
+        ws = self._ws.get(key)
+        if ws is None:
+            n = self._lib.fwn_synthesize_workspace_bytes(C.byref(self._packed.model_desc), b, t, 1 if ragged else 0)
+            if n == 0:
+                _lib.check(-1, "fwn_synthesize_workspace_bytes")
+            for k in [k for k in self._ws if k[:2] != (b, t)]:
+                del self._ws[k]   # keep only the current shape's workspaces
+            ws = torch.empty(n + 256, dtype=torch.uint8, device=self._device)
+            self._ws[key] = ws
+        off = (-ws.data_ptr()) % 256
+        return ws.data_ptr() + off, ws.numel() - off
+
     def upsample(self, c):
         """c [B,F,num_mels] -> [B,F*hop,num_mels] fp32 (model.py:398-404)."""
         import torch

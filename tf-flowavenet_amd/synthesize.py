@@ -10,7 +10,9 @@ tensor-bundle format itself is out of scope), the wav writer is the stdlib ``wav
 seedable (``--seed``; TF's Philox stream cannot be reproduced), and mels of equal length are
 batched into one launch.  ``--ragged`` batches mels of *similar* length too (``plan_batches``; ``FloWaveNet.reverse(...,
 lengths=)`` gives every clip what it gives alone), and draws each clip's ``z`` from a generator of its own, so a clip's
-audio does not depend on the batch it lands in.
+audio does not depend on the batch it lands in.  ``--device_rng`` (opt-in) keeps the arithmetic on the device
+(``FloWaveNet.synthesize``): z comes from a Philox4x32-10 stream keyed by (``--seed``, the clip's index in sorted file-name order) -
+a stream of this package's own - with or without ``--ragged``, only the mel goes up and only 16-bit PCM comes down.
 """
 from __future__ import annotations
 
@@ -106,6 +108,15 @@ def write_wav(path, audio, sample_rate):
         w.writeframes(pcm.tobytes())
 
 
+def write_wav_pcm(path, pcm, sample_rate):
+    """``write_wav`` for audio that already is 16-bit PCM (``FloWaveNet.synthesize``): the int16 samples go to the file as they are."""
+    with wave.open(path, "wb") as w:
+        w.setnchannels(1)
+        w.setsampwidth(2)
+        w.setframerate(int(sample_rate))
+        w.writeframes(np.ascontiguousarray(pcm, dtype="<i2").tobytes())
+
+
 def synthesize(args, hparams, model=None):
     import torch
     from .model import FloWaveNet
@@ -114,6 +125,8 @@ def synthesize(args, hparams, model=None):
     os.makedirs(args.output_dir, exist_ok=True)
     names = sorted(f for f in os.listdir(args.mels_dir) if f.endswith(".npy"))
     mels = {n: np.load(os.path.join(args.mels_dir, n)).astype(np.float32) for n in names}
+    if getattr(args, "device_rng", False):
+        return _synthesize_device(args, hparams, model, names, mels)
     if getattr(args, "ragged", False):
         return _synthesize_ragged(args, hparams, model, names, mels)
     by_len = {}
@@ -161,6 +174,82 @@ def _synthesize_ragged(args, hparams, model, names, mels):
     return names
 
 
+def device_batches(frame_counts, args, hparams):
+    """The calls of ``--device_rng``: a list of groups of indices into ``frame_counts``.  With ``--ragged`` ``plan_batches``;
+    without it clips of equal length only, in ascending length, ``--batch`` (or what one call can address) at a time - the
+    grouping of the host path.  Pure host code."""
+    if getattr(args, "ragged", False):
+        return plan_batches(frame_counts, int(args.batch), float(getattr(args, "max_pad_frac", 0.25)), hparams)
+    by_len = {}
+    for k, f in enumerate(frame_counts):
+        by_len.setdefault(f, []).append(k)
+    groups = []
+    for f, ks in sorted(by_len.items()):
+        t = _aligned_frames(f, hparams) * hparams.hop_size
+        per_call = min(int(args.batch), max_clips_per_call(hparams, t))
+        if per_call < 1:
+            raise ValueError("an utterance of %d samples exceeds what one call can address (%d samples): split the mel"
+                             % (t, max_clips_per_call(hparams, 1)))
+        groups += [ks[i:i + per_call] for i in range(0, len(ks), per_call)]
+    return groups
+
+
+def synthesize_device(model, hparams, mel_list, groups, seed, ragged, emit):
+    """The device path over ``groups`` (lists of indices into ``mel_list``, arrays [F, num_mels]): per group one upload of the
+    padded mels, one ``FloWaveNet.synthesize`` - clip k draws the z of (seed, clip id k) - and one non-blocking copy of the int16
+    result into one of two pinned host buffers.  ``emit(k, pcm)`` gets clip k's samples (a view of the pinned buffer, valid
+    during the call) once the group's copy has landed - and that is after the NEXT group has been enqueued, so the device
+    works while the host writes files.  One event orders it: recorded behind each copy and waited for before that copy's buffer
+    is read; the buffers alternate, so the copy enqueued next never lands in the one being read."""
+    import torch
+    hop = hparams.hop_size
+    frames = [int(m.shape[0]) for m in mel_list]
+    pinned = [None, None]
+    done = torch.cuda.Event()
+    pending = None                                   # (group, T, buffer) of the call whose copy `done` marks
+
+    def flush():
+        done.synchronize()
+        group, t, buf = pending
+        host = buf[:len(group) * t].numpy().reshape(len(group), t)
+        for row, k in enumerate(group):
+            emit(k, host[row, :frames[k] * hop])
+
+    for n, group in enumerate(groups):
+        own = [_aligned_frames(frames[k], hparams) for k in group]        # frames of each clip after its own edge padding
+        top = max(own)
+        c = np.zeros((len(group), top, hparams.num_mels), dtype=np.float32)
+        for row, (k, f) in enumerate(zip(group, own)):
+            c[row, :f] = np.pad(mel_list[k], ((0, f - frames[k]), (0, 0)), mode="edge")
+        if not ragged and min(own) != top:
+            raise ValueError("clips of different lengths share a call only with ragged=True")
+        pcm = model.synthesize(torch.from_numpy(c).cuda(), seed, clip_ids=list(group),
+                               lengths=[f * hop for f in own] if ragged else None)
+        if pending is not None:
+            flush()                                  # the previous group: its buffer is the OTHER one
+        need = len(group) * top * hop
+        if pinned[n & 1] is None or pinned[n & 1].numel() < need:
+            pinned[n & 1] = torch.empty(need, dtype=torch.int16).pin_memory()
+        pinned[n & 1][:need].copy_(pcm.reshape(-1), non_blocking=True)
+        done.record()
+        pending = (group, top * hop, pinned[n & 1])
+    if pending is not None:
+        flush()
+
+
+def _synthesize_device(args, hparams, model, names, mels):
+    """``--device_rng``: clip k (in sorted file-name order) has clip id k under ``--seed``, with and without ``--ragged`` - the
+    same seed gives a clip the same z in either mode; the padding rules are those of the host paths."""
+    mel_list = [mels[n] for n in names]
+    groups = device_batches([m.shape[0] for m in mel_list], args, hparams)
+
+    def emit(k, pcm):
+        write_wav_pcm(os.path.join(args.output_dir, names[k][:-4] + ".wav"), pcm, hparams.sample_rate)
+
+    synthesize_device(model, hparams, mel_list, groups, int(args.seed), bool(getattr(args, "ragged", False)), emit)
+    return names
+
+
 def main(argv=None):
     from .hparams import hparams
     parser = argparse.ArgumentParser()
@@ -174,6 +263,9 @@ def main(argv=None):
     parser.add_argument("--max_pad_frac", type=float, default=0.25,
                         help="with --ragged: the largest share of a launch's samples that may be padding (policy: launches "
                              "saved against samples wasted)")
+    parser.add_argument("--device_rng", action="store_true",
+                        help="draw z on the device (Philox4x32-10 keyed by --seed and the clip's index: not the default z) and "
+                             "bring 16-bit PCM back instead of fp32")
     args = parser.parse_args(argv)
     synthesize(args, hparams)
 
