@@ -333,6 +333,14 @@ int fwn_clip_adam(float* w, const float* g, float* m, float* v, int64_t n, const
 double fwn_adam_rate(float lr, int64_t step, float beta1, float beta2);
 int fwn_clip_adam_dev(float* w, const float* g, float* m, float* v, int64_t n, const float* gnorm, float gscale,
                       float clip, const float* lr_t, float beta1, float beta2, float eps, void* stream);
+/* Gradient accumulation (additive; FWN_VERSION unchanged): one optimiser update over K micro-batches sums their gradients in a
+ * second flat buffer and passes K where the loss scale goes (gscale = 1 / (world * K)).
+ * dst[i] = a ? a[i] + b[i] : b[i], one IEEE fp32 add per element, i in [0, n).  dst may be a or b (in place); any other
+ * overlap of dst with a source is refused.  Pointers need 4-byte alignment only: with one shared misalignment mod 16 (a range
+ * of the flat layout in all three buffers) the kernel runs a scalar head of up to 3 elements, a 16-byte body and a scalar
+ * tail, otherwise it moves dwords.  FWN_ERR_ARG before any launch: NULL dst or b, n <= 0, a pointer not 4-byte aligned,
+ * partial overlap. */
+int fwn_grad_accumulate(float* dst, const float* a, const float* b, int64_t n, void* stream);
 
 /* ---- training-side primitives (work in progress: the backward pass) ----
  * Generic multi-segment GEMM on the LDS-DMA ring core:

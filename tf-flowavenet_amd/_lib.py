@@ -227,6 +227,7 @@ SIGNATURES = {
                                 C.c_float, C.c_float, vp]),
     "fwn_adam_rate": (C.c_double, [C.c_float, i64, C.c_float, C.c_float]),
     "fwn_clip_adam_dev": (C.c_int, [vp, vp, vp, vp, i64, vp, C.c_float, C.c_float, vp, C.c_float, C.c_float, C.c_float, vp]),
+    "fwn_grad_accumulate": (C.c_int, [vp, vp, vp, i64, vp]),
     "fwn_workspace_bytes": (C.c_size_t, [C.POINTER(ModelDesc), i64, i64]),
     "fwn_model_forward": (C.c_int, [C.POINTER(ModelDesc), i64, i64, vp, vp, vp, C.c_size_t, vp, vp,
                                     C.c_int, vp]),

@@ -942,6 +942,20 @@ int fwn_clip_adam_dev(float* w, const float* g, float* m, float* v, int64_t n, c
     fwn_launch_adam(w, g, m, v, (long)n, gnorm, gscale, clip, 0.0f, lr_t, beta1, beta2, eps, (hipStream_t)stream);
     return check_launch("fwn_clip_adam_dev");
 }
+int fwn_grad_accumulate(float* dst, const float* a, const float* b, int64_t n, void* stream) {
+    REQUIRE(dst && b, "fwn_grad_accumulate: dst and b must not be NULL");
+    REQUIRE(n > 0, "fwn_grad_accumulate: n must be positive");
+    REQUIRE(!(((uintptr_t)dst | (uintptr_t)a | (uintptr_t)b) & 3), "fwn_grad_accumulate: pointers must be 4-byte aligned");
+    // in place (dst == a or dst == b) every element is read and written by one lane; any other overlap with dst would let one
+    // lane read what another has already written
+    const uintptr_t d0 = (uintptr_t)dst, bytes = (uintptr_t)n * 4;
+    for (const float* src : {a, b}) {
+        const uintptr_t s0 = (uintptr_t)src;
+        REQUIRE(!src || s0 == d0 || s0 + bytes <= d0 || d0 + bytes <= s0, "fwn_grad_accumulate: dst overlaps a source without being it");
+    }
+    fwn_launch_grad_accumulate(dst, a, b, (long)n, (hipStream_t)stream);
+    return check_launch("fwn_grad_accumulate");
+}
 
 // ---------------------------------------------------------------------------------------------
 // Whole-model sequencing

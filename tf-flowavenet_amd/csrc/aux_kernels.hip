@@ -1011,6 +1011,27 @@ __global__ __launch_bounds__(256) void adam_clip_kernel(float* __restrict__ w, c
         }
     }
 }
+// Gradient accumulation: dst[i] = a ? a[i] + b[i] : b[i], one IEEE fp32 add per element.  dst may be a or b: every element is
+// read and written by the same lane, so no pointer is __restrict__.  A block range of the flat layout starts at any element
+// offset: `head` (0..3) scalar elements bring the three pointers to a 16-byte boundary when they share one misalignment, then
+// nv float4s, then the scalar tail; pointers that do not share it come with head = 0, nv = 0 - the scalar loop over everything.
+__global__ __launch_bounds__(256) void grad_accumulate_kernel(float* dst, const float* a, const float* b, long n, int head, long nv) {
+    const long t0 = (long)blockIdx.x * 256 + threadIdx.x, stride = (long)gridDim.x * 256;
+    for (long q = t0; q < nv; q += stride) {
+        const long i = head + 4 * q;
+        float4 s = *(const float4*)(b + i);
+        if (a) {
+            const float4 av = *(const float4*)(a + i);
+            s.x = av.x + s.x; s.y = av.y + s.y; s.z = av.z + s.z; s.w = av.w + s.w;
+        }
+        *(float4*)(dst + i) = s;
+    }
+    const long ns = n - 4 * nv;                          // the head in front of the float4 body and the tail behind it
+    for (long s = t0; s < ns; s += stride) {
+        const long i = s < head ? s : s + 4 * nv;
+        dst[i] = a ? a[i] + b[i] : b[i];
+    }
+}
 
 // ---- launchers -------------------------------------------------------------------------------
 static inline int grid_for(long total) {
@@ -1179,4 +1200,12 @@ void fwn_launch_adam(float* w, const float* g, float* m, float* v, long n, const
                      float clip, float lr_t, const float* lr_dev, float b1, float b2, float eps, hipStream_t st) {
     hipLaunchKernelGGL(adam_clip_kernel, dim3(fwn_sqnorm_blocks(n)), dim3(256), 0, st, w, g, m, v, n, gnorm, gscale,
                        clip, lr_t, lr_dev, b1, b2, eps);
+}
+void fwn_launch_grad_accumulate(float* dst, const float* a, const float* b, long n, hipStream_t st) {
+    const unsigned mis = (unsigned)((uintptr_t)dst & 15);
+    const bool same = ((uintptr_t)b & 15) == mis && (!a || ((uintptr_t)a & 15) == mis);
+    long head = same ? (long)((16 - mis) & 15) / 4 : 0;
+    if (head > n) head = n;
+    const long nv = same ? (n - head) / 4 : 0;
+    hipLaunchKernelGGL(grad_accumulate_kernel, dim3(fwn_sqnorm_blocks(n)), dim3(256), 0, st, dst, a, b, n, (int)head, nv);
 }

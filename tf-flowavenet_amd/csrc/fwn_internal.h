@@ -172,6 +172,8 @@ void fwn_launch_mel(const float* wav, long B, long T, const float* window, const
 void fwn_launch_grad_norm(const float* g, long n, float gscale, double* partial, float* out, hipStream_t st);
 void fwn_launch_adam(float* w, const float* g, float* m, float* v, long n, const float* gnorm, float gscale,
                      float clip, float lr_t, const float* lr_dev, float b1, float b2, float eps, hipStream_t st);
+// dst[i] = a ? a[i] + b[i] : b[i]; dst may be a or b.  float4 body when the pointers share one misalignment mod 16, else dwords
+void fwn_launch_grad_accumulate(float* dst, const float* a, const float* b, long n, hipStream_t st);
 
 // train_kernels.hip
 struct fwn_gemm_desc;

@@ -138,7 +138,9 @@ def gather_from_owners(w, group=None):
 class DataParallelAdam:
     """fp32 master weights + Adam slots in flat device buffers; ``step()`` = all-reduce -> global
     norm -> clip -> Adam, returning the (device) global gradient norm.  exchange = "zero1": reduce onto the shard owners ->
-    norm of the shards (all-reduced) -> clip + Adam on the own shard -> gather the masters (see above)."""
+    norm of the shards (all-reduced) -> clip + Adam on the own shard -> gather the masters (see above).
+    ``acc`` (None until ``accumulate_pending`` is first called) holds the gradient sum of micro-batches that did not end their
+    update; ``fold_pending`` adds it into ``g`` and ``step(loss_scale=K)`` averages the K of them."""
 
     def __init__(self, hp, params, device="cuda", clip=1.0, beta1=0.9, beta2=0.999, eps=1e-8, group=None,
                  bucket_elems=64 << 20, grad_reduce_dtype="fp32", exchange="allreduce"):
@@ -163,6 +165,7 @@ class DataParallelAdam:
         self.clip, self.b1, self.b2, self.eps = clip, beta1, beta2, eps
         self.w = torch.from_numpy(self.layout.flatten(params)).to(device)
         self.g = torch.zeros_like(self.w)
+        self.acc = None       # the pending sum of a gradient accumulation: allocated on first use (accumulate_pending)
         self.m = torch.zeros_like(self.w)
         self.v = torch.zeros_like(self.w)
         self.global_step = 0
@@ -237,6 +240,32 @@ class DataParallelAdam:
         if self.grad_reduce_dtype == "bf16" and self._g16 is None:
             self._g16 = torch.empty(self.g.numel(), dtype=torch.bfloat16, device=self.g.device)
         return self._g16
+
+    # -- gradient accumulation: one update over K micro-batches.  ``acc`` is a second flat fp32 buffer, allocated by the first
+    # ``accumulate_pending`` and never before; the sum is averaged by passing K as ``loss_scale`` (gscale = 1 / (world * K)).
+    def _accumulate(self, dst, a, b, lo, hi):
+        import torch
+        st = torch.cuda.current_stream(torch.device(self.device)).cuda_stream
+        _lib.check(self._lib.fwn_grad_accumulate(dst.data_ptr() + 4 * lo, a.data_ptr() + 4 * lo if a is not None else None,
+                                                 b.data_ptr() + 4 * lo, hi - lo, st), "fwn_grad_accumulate")
+
+    def ensure_accumulator(self):
+        import torch
+        if self.acc is None:
+            self.acc = torch.empty_like(self.g)
+        return self.acc
+
+    def accumulate_pending(self, first):
+        """``g`` holds the gradient of a micro-batch that does not end the update: acc = g (the first one) or acc += g."""
+        acc = self.ensure_accumulator()
+        self._accumulate(acc, None if first else acc, self.g, 0, self.g.numel())
+
+    def fold_pending(self, lo=0, hi=None):
+        """g[lo:hi] = acc[lo:hi] + g[lo:hi]: the pending sum folded into the last micro-batch's gradient, so that everything
+        downstream (exchange, norm, clip / Adam) still reads ``g``."""
+        if self.acc is None:
+            raise RuntimeError("fold_pending: nothing was accumulated")
+        self._accumulate(self.g, self.acc, self.g, lo, self.g.numel() if hi is None else hi)
 
     def step(self, loss_scale=1.0, works=None):
         """``self.g`` holds this rank's gradient of (loss_scale * loss).  works: handles of all-reduces

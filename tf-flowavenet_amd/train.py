@@ -341,14 +341,23 @@ def train(log_dir, args, hparams, input_path, device="cuda", params=None):
         with open(os.path.join(path, "summary.jsonl"), "a") as f:
             f.write(json.dumps(rec) + "\n")
 
+    # --accum_steps K: an update is K draws, K - 1 through accumulate and the last through step, in draw order; every rank runs
+    # this very loop, so all of them accumulate the same number of times per update.  Steps, the rate schedule and every
+    # interval below count updates, and a checkpoint is only ever written between two updates: no pending state to save.
+    accum_steps = int(getattr(args, "accum_steps", 1))
     while step < args.train_steps:
         start_time = time.time()
-        if ragged:
-            mels, audios, lens = dataset.next_train()
-            loss, log_p, logdet, gnorm = trainer.step(audios, mels, lengths=lens)
-        else:
-            mels, audios = dataset.next_train()
-            loss, log_p, logdet, gnorm = trainer.step(audios, mels)
+        clip_lengths = []
+        for micro in range(accum_steps):
+            run = trainer.step if micro == accum_steps - 1 else trainer.accumulate
+            if ragged:
+                mels, audios, lens = dataset.next_train()
+                out = run(audios, mels, lengths=lens)
+                clip_lengths.extend(lens)
+            else:
+                mels, audios = dataset.next_train()
+                out = run(audios, mels)
+        loss, log_p, logdet, gnorm = out
         step = trainer.opt.global_step
         total_loss = float(loss)                                             # synchronises: the step time is real
         step_duration = time.time() - start_time
@@ -359,9 +368,9 @@ def train(log_dir, args, hparams, input_path, device="cuda", params=None):
             print("\nWriting summary at step {}".format(step))
             rec = {"step": step, "losses/total_loss": total_loss, "losses/log_p": float(log_p),
                    "losses/logdet": float(logdet), "learning_rate": learning_rate(step - 1),
-                   "gradient_global_norm": float(gnorm)}
+                   "gradient_global_norm": float(gnorm), "accum_steps": accum_steps}
             if ragged:
-                rec["mean_clip_length"] = float(np.mean(lens))
+                rec["mean_clip_length"] = float(np.mean(clip_lengths))
             log(train_logdir, rec)
             model = FloWaveNet(hparams, device=device, cond_mode=1).load_params(trainer.opt.master_views())
             if ragged:      # per-clip scalars, each over the clip's own samples: the numbers `score` reports per utterance
@@ -410,6 +419,15 @@ def main(argv=None):
     parser.add_argument("--ragged_init", action="store_true",
                         help="with --ragged: take the ActNorm init batch as a training batch is drawn (short utterances whole, with "
                              "their lengths) on any corpus")
+    def positive(s):
+        k = int(s)
+        if k < 1:
+            raise argparse.ArgumentTypeError("must be >= 1")
+        return k
+
+    parser.add_argument("--accum_steps", type=positive, default=1,
+                        help="micro-batches per optimiser update: the gradients of K batches are summed and averaged into one "
+                             "clip / Adam update (effective batch K x batch_size x ranks); steps and every interval count updates")
     args = parser.parse_args(argv)
     import torch
     import torch.distributed as dist

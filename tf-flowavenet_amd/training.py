@@ -409,18 +409,21 @@ class GradEngine:
     def _call(self, name, *args):
         _lib.check(getattr(self.lib, name)(*args), name)
 
-    def loss_and_grads(self, params, x, c, grad_out=None, on_block_done=None, lengths=None):
+    def loss_and_grads(self, params, x, c, grad_out=None, on_block_done=None, lengths=None, repack=True):
         """grad_out: optional dict name -> fp32 tensor (e.g. views of a flat gradient buffer): gradients are
         written there (the large ones in place) and returned as those very tensors.  on_block_done(i) is
         called when every gradient of block i is in grad_out (blocks finish last to first; -1 = the
         up-sampling convs, at the end) - the hook a data-parallel step uses to start that block's
         all-reduce under the rest of the backward pass.
         lengths: a list, NumPy array or tensor of B sample counts (a ragged batch, see the class) - validated on the host
-        by ``model.check_lengths`` before anything is launched; or ``DeviceLengths`` (already validated, read at run time)."""
+        by ``model.check_lengths`` before anything is launched; or ``DeviceLengths`` (already validated, read at run time).
+        repack: False skips the re-pack of the bf16 copies from the fp32 masters - for a caller that knows the masters have not
+        moved since this engine's last call on them (the later micro-batches of a gradient accumulation); the first call on a
+        set of masters packs whatever it says."""
         self._gout = grad_out
         self._on_block = on_block_done
         try:
-            return self._loss_and_grads(params, x, c, lengths)
+            return self._loss_and_grads(params, x, c, lengths, repack)
         finally:
             _STREAMS.clear()
             self._gout = None
@@ -433,7 +436,7 @@ class GradEngine:
             raise ValueError("gate_fp8 hparams take no lengths: the e4m3 copies of h are not masked")
         return model.check_lengths(lengths, b, t, int(np.prod(self.hp.upsample_scales)), self.hp.n_block)
 
-    def _loss_and_grads(self, params, x, c, lengths=None):
+    def _loss_and_grads(self, params, x, c, lengths=None, repack=True):
         import torch
         hp, lib = self.hp, self.lib
         dev = torch.device(self.device)
@@ -452,7 +455,8 @@ class GradEngine:
         key = next(iter(params.values())).data_ptr()
         tp = getattr(self, "_tp", None)
         if tp is not None and getattr(self, "_tp_key", None) == key:
-            tp.refresh()
+            if repack:
+                tp.refresh()
         else:
             tp = self._tp = _TrainPack(params, hp, self.device)
             self._tp_key = key
@@ -599,6 +603,9 @@ class Trainer:
         self.engine = GradEngine(hparams, device)
         self.graph = bool(graph)
         self._recorded = {}
+        self._recorded_acc = {}     # the recordings only a gradient accumulation makes: (shape key, kind) -> as _recorded
+        self.pending = 0            # micro-batches accumulated since the last update (accumulate)
+        self._sums = self._pending_b = None
         self.per_clip = None
         # False: skip the gradient exchange (bench.py's compute-only step time, to price the overlap)
         self.exchange = True
@@ -633,23 +640,79 @@ class Trainer:
         lengths: a ragged batch (``GradEngine.loss_and_grads``): loss, log_p and logdet are then the means over the clips of
         the per-clip values, which ``per_clip`` holds afterwards as ``(log_p [B], logdet [B])`` (None after a plain step).
         The recorded step keeps the lengths in a static device buffer beside x and c - one recording per shape serves every
-        batch, whatever its lengths."""
-        if lengths is not None:
-            import torch
-            xs = torch.as_tensor(x)
-            lengths = self.engine.check_lengths(lengths, int(xs.shape[0]), int(xs.numel() // max(1, int(xs.shape[0]))))
+        batch, whatever its lengths.
+        With ``pending`` = n micro-batches accumulated (``accumulate``): this batch is the last of the update.  Its gradient
+        takes the pending sum in, block range by block range as the ranges become final - ``opt.g`` = ((g_0 + g_1) + ...) + g_n
+        in call order -, then exchange, norm and clip / Adam run as ever with the loss scale n + 1.  loss, log_p and logdet
+        are the means over the n + 1 micro-batches (device arithmetic, no host synchronisation), ``per_clip`` is the last
+        micro-batch's.  With nothing pending this is the step it always was, to the bit."""
+        import torch
+        lengths = self._admit(x, lengths)
+        n = self.pending
         if self.graph and self.opt.exchange == "allreduce":     # (the sharded exchange is eager only: optim.record_update)
-            return self._step_recorded(x, c, lengths)
-        return self._step_eager(x, c, lengths)
+            out = self._step_recorded(x, c, lengths, n=n)
+        else:
+            out = self._step_eager(x, c, lengths, n=n)
+        if not n:
+            return out
+        mean = (self._sums + torch.stack(out[:3])) / float(n + 1)
+        self.drop_pending()
+        return mean[0], mean[1], mean[2], out[3]
+
+    def accumulate(self, x, c, lengths=None):
+        """-> (loss, log_p, logdet) of this micro-batch; its gradient on the current masters joins the pending sum.  No
+        collective, no update, ``global_step`` unchanged: the next ``step`` ends the update (one optimiser update over
+        ``pending`` + 1 micro-batches, averaged).  Every micro-batch of an update holds the same number of clips (the mean of
+        the means is the mean over the clips only then; ValueError otherwise, before anything is launched and with the pending
+        state as it was); T may differ.  The first micro-batch of an update re-packs the bf16 copies from the masters (a restore
+        or ``ddi`` may have touched them), the following ones do not: nothing may write the masters between the first
+        ``accumulate`` of an update and its ``step``.  Data parallel: every rank must call ``accumulate`` the same number of
+        times per update - nothing checks it (a collective would cost what the accumulation saves); ``train.py`` does by
+        construction."""
+        import torch
+        lengths = self._admit(x, lengths)
+        first = self.pending == 0
+        self.opt.ensure_accumulator()          # outside any recording: the buffer must not come from a graph's pool
+        if self.graph and self.opt.exchange == "allreduce":
+            out = self._step_recorded(x, c, lengths, micro=first)
+        else:
+            out = self._micro_eager(x, c, lengths, first)
+        cur = torch.stack(out[:3])
+        self._sums = cur if first else self._sums + cur
+        self._pending_b = int(torch.as_tensor(x).shape[0])
+        self.pending += 1
+        return cur[0], cur[1], cur[2]
+
+    def drop_pending(self):
+        """Forget the pending sum (e.g. after an exception in the middle of an update): the next ``step`` is a plain one."""
+        self.pending, self._sums, self._pending_b = 0, None, None
+
+    def _admit(self, x, lengths):
+        """What is checked on the host before anything is launched: the lengths of a ragged batch (-> list of ints) and, with
+        micro-batches pending, that this one holds as many clips as they did."""
+        import torch
+        xs = torch.as_tensor(x)
+        b = int(xs.shape[0]) if xs.dim() else 0
+        if lengths is not None:
+            lengths = self.engine.check_lengths(lengths, b, int(xs.numel() // max(1, b)))
+        if self.pending and b != self._pending_b:
+            raise ValueError("gradient accumulation: this micro-batch holds %d clips, the %d pending ones hold %d each (the mean "
+                             "of the micro-batch means is the mean over the clips only for equal sizes)" % (b, self.pending, self._pending_b))
+        return lengths
 
     def _ranges(self):
         return {("upsample" if key == "upsample" else int(key.split("_")[1])): (lo, hi) for key, lo, hi in self.opt.block_ranges()}
 
-    def _step_recorded(self, x, c, lengths=None):
+    def _step_recorded(self, x, c, lengths=None, n=0, micro=None):
         """First call at a shape: eager (creates the packing plan, fills every cache).  Second: record.  The
         recording is a chain of hipGraphs cut where a block's gradients are final, so that with more than one
         rank each block's all-reduce still starts between two replays, under the rest of the backward pass;
-        the Adam rate is refreshed before the replay (the packing, tables included, is inside the recording)."""
+        the Adam rate is refreshed before the replay (the packing, tables included, is inside the recording).
+        n: micro-batches pending - the folds of their sum are captured inside the segments, each in front of the cut that
+        starts its range's exchange, and the recorded update carries gscale = 1 / (world (n + 1)): a recording per n.
+        micro: True / False - not an update but a micro-batch that does not end one, the first of its update (it re-packs and
+        starts the sum) or a later one: ONE uncut hipGraph at any world size - gradients and the whole-buffer accumulation, no
+        hooks - that returns (loss, log_p, logdet, None)."""
         import torch
         import torch.distributed as dist
         dev = torch.device(self.device)
@@ -657,10 +720,18 @@ class Trainer:
         c = torch.as_tensor(c)
         # the shapes, not the lengths: one recording serves every ragged batch (the plain step keeps its own key)
         key = (tuple(x.shape), tuple(c.shape)) + (("ragged",) if lengths is not None else ())
-        rec = self._recorded.get(key)
+        table = self._recorded
+        if n or micro is not None:
+            table, key = self._recorded_acc, (key, ("micro", bool(micro)) if micro is not None else ("step", n))
+        if micro is not None:
+            eager = lambda: self._micro_eager(x, c, lengths, micro) + (None,)
+        else:
+            eager = lambda: self._step_eager(x, c, lengths, n=n)
+        rec = table.get(key)
         if rec is None:
-            self._recorded[key] = "warm"
-            return self._step_eager(x, c, lengths)
+            table[key] = "warm"
+            return eager()
+        ranges = self._ranges()
         world = dist.get_world_size(self.opt.group) if dist.is_available() and dist.is_initialized() else 1
         if rec == "warm":
             # cut(-1) below holds for the side-stream sequence only: one stream enqueues the up-sampling backward between
@@ -683,9 +754,11 @@ class Trainer:
                     cur[0].capture_begin(pool=pool, capture_error_mode="thread_local")
 
                     def cut(i):
+                        if n:       # the pending sum of this range, still inside the segment that ends here
+                            self.opt.fold_pending(*ranges["upsample" if i < 0 else i])
                         if world == 1 and i >= 0 and not self.opt.force_collectives:
                             return
-                        if i == -1 and segs and segs[-1][1] == 0:
+                        if i == -1 and not n and segs and segs[-1][1] == 0:     # (with n the up-sampling range's fold lies between)
                             # fwn_train_loss_and_grads reports block 0 and then the up-sampling convs (-1) back to back - with the
                             # side stream block 0 is joined behind the up-sampling backward, nothing is enqueued between the two hooks
                             # (csrc/train_api.hip: join_pending, then the -1 hook) - so there is nothing to cut: no empty
@@ -697,10 +770,15 @@ class Trainer:
                         cur[0] = torch.cuda.CUDAGraph()
                         cur[0].capture_begin(pool=pool, capture_error_mode="thread_local")
 
-                    loss, log_p, logdet, _ = self.engine.loss_and_grads(params, xs, cs, grad_out=gv, on_block_done=cut,
-                                                                        lengths=DeviceLengths(ls) if ls is not None else None)
+                    loss, log_p, logdet, _ = self.engine.loss_and_grads(params, xs, cs, grad_out=gv, on_block_done=cut if micro is None else None,
+                                                                        lengths=DeviceLengths(ls) if ls is not None else None,
+                                                                        repack=(n == 0) if micro is None else micro)
                     per_clip = self.engine.per_clip
-                    gnorm = self.opt.record_update()
+                    if micro is None:
+                        gnorm = self.opt.record_update(loss_scale=n + 1)
+                    else:
+                        self.opt.accumulate_pending(micro)
+                        gnorm = None
                     cur[0].capture_end()
                     segs.append((cur[0], None))
             except Exception as e:      # recording is an optimisation: a runtime that refuses it must not stop training
@@ -713,16 +791,17 @@ class Trainer:
                 torch.cuda.synchronize(dev)
                 warnings.warn("recording the training step failed (%s: %s); continuing with eager steps" % (type(e).__name__, e))
                 self.graph = False
-                return self._step_eager(x, c, lengths)
+                return eager()
             torch.cuda.current_stream(dev).wait_stream(side)
-            rec = self._recorded[key] = dict(xs=xs, cs=cs, ls=ls, segs=segs, out=(loss, log_p, logdet, gnorm), per_clip=per_clip)
+            rec = table[key] = dict(xs=xs, cs=cs, ls=ls, segs=segs, out=(loss, log_p, logdet, gnorm), per_clip=per_clip)
         rec["xs"].copy_(x.reshape(rec["xs"].shape), non_blocking=True)
         rec["cs"].copy_(c, non_blocking=True)
         if rec["ls"] is not None:
             rec["ls"].copy_(torch.tensor(lengths, dtype=torch.int32), non_blocking=False)
         self.per_clip = rec["per_clip"]
-        self.opt.advance()
-        ranges, works = self._ranges(), []
+        if micro is None:
+            self.opt.advance()
+        works = []
         for g, i in rec["segs"]:
             if i is None:                       # the optimiser: every exchange must have landed
                 for w in works:
@@ -735,18 +814,35 @@ class Trainer:
                 works.append(self.opt.allreduce_range(lo, hi))
         return rec["out"]
 
-    def _step_eager(self, x, c, lengths=None):
+    def _step_eager(self, x, c, lengths=None, n=0):
         params = self.opt.master_views()
         gv = self.opt.grad_views()
         ranges = {("upsample" if key == "upsample" else int(key.split("_")[1])): (lo, hi) for key, lo, hi in self.opt.block_ranges()}
         works = []
+        # n micro-batches pending: their sum joins a block's range in front of that range's all-reduce (the ranges cover the
+        # layout); the sharded exchange starts no all-reduce here and takes the whole buffer at once below
+        fold_ranges = n > 0 and self.opt.exchange != "zero1"
 
         def block_done(i):      # block i's gradients are final: its all-reduce runs under the remaining backward
+            lo, hi = ranges["upsample" if i < 0 else i]
+            if fold_ranges:
+                self.opt.fold_pending(lo, hi)
             if self.exchange:
-                lo, hi = ranges["upsample" if i < 0 else i]
                 works.append(self.opt.allreduce_range(lo, hi))
 
-        loss, log_p, logdet, grads = self.engine.loss_and_grads(params, x, c, grad_out=gv, on_block_done=block_done, lengths=lengths)
+        loss, log_p, logdet, grads = self.engine.loss_and_grads(params, x, c, grad_out=gv, on_block_done=block_done, lengths=lengths,
+                                                                repack=n == 0)
         self.per_clip = self.engine.per_clip
-        gnorm = self.opt.step(works=works)
+        if n and not fold_ranges:
+            self.opt.fold_pending()
+        gnorm = self.opt.step(loss_scale=n + 1, works=works)
         return loss, log_p, logdet, gnorm
+
+    def _micro_eager(self, x, c, lengths, first):
+        """A micro-batch that does not end the update: its gradient into ``opt.g`` (no hooks: nothing is exchanged), then into
+        the pending sum."""
+        loss, log_p, logdet, _ = self.engine.loss_and_grads(self.opt.master_views(), x, c, grad_out=self.opt.grad_views(), lengths=lengths,
+                                                            repack=first)
+        self.per_clip = self.engine.per_clip
+        self.opt.accumulate_pending(first)
+        return loss, log_p, logdet

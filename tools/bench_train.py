@@ -12,7 +12,13 @@ of the flat fp32 gradient, global-norm clip, Adam.  Prints one JSON line (whole-
 
 times three steps on one GPU, alternating them round by round in one process: the plain step, the ragged step
 (``Trainer.step(x, c, lengths=)``) with every length = T, and the ragged step with lengths spread over 1024 .. T; one JSON
-line with the per-round figures and their medians (also written to ``--out``)."""
+line with the per-round figures and their medians (also written to ``--out``).
+
+    python tools/bench_train.py --accum 2,4,8 --out profiles/accum_training.json
+
+times, the same way, the plain step against one optimiser update over K micro-batches (``Trainer.accumulate`` K - 1 times, then
+``Trainer.step``) for every K given: ms per update, ms per micro-batch, samples/s; and the fold kernel alone over the whole flat
+gradient buffer beside ``adam_clip_kernel``, in bytes/s from device events."""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -62,6 +68,89 @@ def ragged_leg(a):
             f.write(line + "\n")
 
 
+def accum_leg(a):
+    """Plain step | one update over K micro-batches for every K of a.accum, B = a.batch clips of a.samples samples, one trainer
+    each on the same initial weights; rounds of a.steps updates alternate between the legs (a round ends in a synchronise).
+    Then the fold alone - ``fwn_grad_accumulate(g, acc, g)`` over the whole flat buffer, 12 bytes per element - beside
+    ``adam_clip_kernel`` (``fwn_clip_adam``, 28 bytes per element) on buffers of the same length, both timed by device events."""
+    from tf_flowavenet_amd import _lib
+    from tf_flowavenet_amd.hparams import default_hparams
+    from tf_flowavenet_amd import weights as W
+    from tf_flowavenet_amd.training import Trainer
+    torch.cuda.set_device(0)
+    hp = default_hparams()
+    inp = W.synthetic_inputs(hp, a.batch, a.samples)
+    x, c = torch.from_numpy(inp["x"]).reshape(a.batch, a.samples).cuda(), torch.from_numpy(inp["c"]).cuda()
+    ks = [int(k) for k in a.accum.split(",")]
+    if any(k < 2 for k in ks):
+        raise SystemExit("--accum takes K >= 2 (the plain step is always a leg)")
+    legs = {"plain": 1}
+    legs.update({"accum_%d" % k: k for k in ks})
+
+    def update(tr, k):
+        for _ in range(k - 1):
+            tr.accumulate(x, c)
+        return tr.step(x, c)
+
+    trainers = {}
+    for name, k in legs.items():
+        tr = trainers[name] = Trainer(hp, W.synthetic_params(hp, 1234))
+        tr.ddi(x, c)
+        for _ in range(max(a.warmup, 3)):       # eager, record, replay - of every kind of micro-batch this K has
+            update(tr, k)
+    torch.cuda.synchronize()
+    ms = {name: [] for name in legs}
+    for _ in range(a.rounds):
+        for name, k in legs.items():
+            t0 = time.perf_counter()
+            for _ in range(a.steps):
+                update(trainers[name], k)
+            torch.cuda.synchronize()
+            ms[name].append((time.perf_counter() - t0) / a.steps * 1e3)
+    med = {name: float(np.median(v)) for name, v in ms.items()}
+    # the fold and the optimiser kernel alone, on the K = max trainer's buffers (its accumulator exists); Adam on scratch
+    # copies so that no trainer's state is touched
+    lib, opt = _lib.load(), trainers["accum_%d" % max(ks)].opt
+    n, st = opt.g.numel(), torch.cuda.current_stream().cuda_stream
+    w2, m2, v2, one = opt.w.clone(), torch.zeros_like(opt.w), torch.zeros_like(opt.w), torch.ones(1, device="cuda")
+    g, acc = opt.g, opt.acc
+    kernels = {
+        "fold": (12, lambda: lib.fwn_grad_accumulate(g.data_ptr(), acc.data_ptr(), g.data_ptr(), n, st)),
+        "first_store": (8, lambda: lib.fwn_grad_accumulate(acc.data_ptr(), None, g.data_ptr(), n, st)),
+        "adam_clip": (28, lambda: lib.fwn_clip_adam(w2.data_ptr(), g.data_ptr(), m2.data_ptr(), v2.data_ptr(), n, one.data_ptr(), 1.0, 1.0,
+                                                    1e-3, 1, 0.9, 0.999, 1e-8, st)),
+    }
+    alone = {}
+    for name, (nbytes, launch) in kernels.items():
+        for _ in range(3):
+            _lib.check(launch(), name)
+        times = []
+        for _ in range(a.rounds):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(10):
+                _lib.check(launch(), name)
+            e1.record()
+            e1.synchronize()
+            times.append(e0.elapsed_time(e1) / 10)
+        t = float(np.median(times))
+        alone[name] = {"ms": t, "bytes_per_element": nbytes, "bytes_per_s": nbytes * n / (t * 1e-3)}
+    rec = {"metric": "training update over K micro-batches, ms (one GPU), n_block=8 bf16", "unit": "ms per update",
+           "config": {"clips": a.batch, "samples_per_clip": a.samples, "updates_per_round": a.steps, "rounds": a.rounds, "flat_elements": n},
+           "ms_per_update": med,
+           "ms_per_micro_batch": {name: med[name] / k for name, k in legs.items()},
+           "samples_per_s": {name: a.batch * a.samples * k / (med[name] * 1e-3) for name, k in legs.items()},
+           "rounds_ms": ms, "kernels_alone": alone,
+           "fold_over_adam_bytes_per_s": alone["fold"]["bytes_per_s"] / alone["adam_clip"]["bytes_per_s"],
+           "recorded": {name: bool(trainers[name].graph) for name in legs}}
+    line = json.dumps(rec)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -70,11 +159,14 @@ def main():
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--samples", type=int, default=6400)
     ap.add_argument("--ragged", action="store_true", help="one GPU: plain step | ragged step, full lengths | lengths 1024 .. samples")
-    ap.add_argument("--rounds", type=int, default=5, help="--ragged: rounds of --steps steps per leg, alternating")
-    ap.add_argument("--out", default="", help="--ragged: also write the JSON line to this file")
+    ap.add_argument("--rounds", type=int, default=5, help="--ragged / --accum: rounds of --steps steps (updates) per leg, alternating")
+    ap.add_argument("--accum", default="", help="one GPU: plain step | one update over K micro-batches, for every K of this comma-separated list")
+    ap.add_argument("--out", default="", help="--ragged / --accum: also write the JSON line to this file")
     a = ap.parse_args()
     if a.ragged:
         return ragged_leg(a)
+    if a.accum:
+        return accum_leg(a)
     import torch.distributed as dist
     from tf_flowavenet_amd.hparams import default_hparams
     from tf_flowavenet_amd import weights as W
