@@ -31,7 +31,8 @@
 extern "C" {
 #endif
 
-#define FWN_VERSION 322            /* 0.3.22: - fwn_train_desc.an_logdet and .defer_block_done (a host built against 0.3.21 must be rebuilt).
+#define FWN_VERSION 322            /* (round 7, number kept: + fwn_flow_desc.Wds appended and fwn_gate_tile; fwn_flow_desc grew, so a host that builds
+                                    * the flows array must be rebuilt against this header.)  0.3.22: - fwn_train_desc.an_logdet and .defer_block_done (a host built against 0.3.21 must be rebuilt).
                                     * 0.3.21 (round 6): + fwn_model_desc.cond_stream (appended) and fwn_cond_stream* / fwn_pack_cond_stream (the register-streamed
                                     * conditioning projection, csrc/cond_rs.h; additive); fwn_pack_tail_stream_jobs.  0.3.20 (round 6): + fwn_flow_desc.Wts and fwn_tail_stream_bytes / fwn_pack_tail_stream / fwn_tail_stream_rows (the
                                     * register-streamed tail, csrc/tail_rs.h; additive: a 0.3.10 host that zero-fills its descriptors keeps working);
@@ -148,6 +149,12 @@ typedef struct fwn_flow_desc {
     /* Register-streamed tail (csrc/tail_rs.h; NULL = not packed): Wskip | Wfinal once more in MFMA-fragment order
      * (fwn_pack_tail_stream), read by the tail kernel of the larger row counts (fwn_tail_stream_rows) instead of them. */
     const void* Wts;
+    /* Register-streamed hoisted gate (round 7, csrc/cond_rs.h gate_hs_kernel; NULL = not packed): Wd[l] alone in the fragment
+     * order of the conditioning stream - fwn_pack_cond_stream(Wd[l], 512 * 768, 768, 1, out), fwn_cond_stream_bytes(768) bytes -
+     * read instead of Wd[l] by the gates with a hoisted P whose rows the ring path would give its un-split 64 x 128 tile
+     * (3 009 - 6 016 rows, dilation <= 3).  Bit-identical to that path.  Appended: the descriptor grew by 8 * FWN_MAX_LAYERS
+     * bytes, a host must be rebuilt against this header (the flows of a model are an array of these). */
+    const void* Wds[FWN_MAX_LAYERS];
 } fwn_flow_desc;
 
 /* ---- fragment-order tail weights (round 6, csrc/tail_rs.h; replaces nothing in the reference: a second packing of the
@@ -191,6 +198,12 @@ int fwn_front(const fwn_flow_desc* d, const float* xa, void* h_out, void* scratc
 /* K5 gated dilated layer `layer` (modules.py:113-124).  ca==NULL uses P (precomputed c_a@Wc). */
 int fwn_gate(const fwn_flow_desc* d, int layer, const void* h, const void* ca, const float* P, void* o,
              int M, int Ti, void* stream);
+/* K5 with a hoisted P on ONE named tile (tests and tile sweeps; every tile gives fwn_gate's bits): cols = 512 | 256 with
+ * rows = 64 | 96 | 128: the register-streamed form from d->Wds[layer] (rows = cols = 0: the tile fwn_gate takes), only at the
+ * shapes where fwn_gate would take it; cols = 128 with rows = 64 | 128 | 256: the ring tile of that height from d->Wd[layer].
+ * Returns the number of workgroups launched or a negative error code. */
+int fwn_gate_tile(const fwn_flow_desc* d, int layer, const void* h, const float* P, void* o, int M, int Ti, int rows, int cols,
+                  void* stream);
 /* K5 with the dilated taps in fp8 (v_mfma_scale_f32_32x32x64_f8f6f4): h8 = e4m3 copy of h [M][256] bytes
  * (fwn_cast_e4m3, or written by the front / res kernels inside fwn_flow_run_fp8), weights d->Wd8[layer]; the 1x1
  * conditioning conv stays bf16 in the same accumulators.  Exists for the MFMA-bound shapes only:

@@ -32,7 +32,7 @@ class FlowDesc(C.Structure):
         ("an", vp),
         ("Wd8", vp * FWN_MAX_LAYERS), ("wd8_exp", i32 * FWN_MAX_LAYERS),
         ("Wfront3", vp), ("kf3", i32), ("reserved", i32), ("Wgs", vp * FWN_MAX_LAYERS),
-        ("Wts", vp),
+        ("Wts", vp), ("Wds", vp * FWN_MAX_LAYERS),
     ]
 
 
@@ -152,6 +152,7 @@ SIGNATURES = {
     "fwn_actnorm_from_moments": (C.c_int, [vp, C.c_int, vp, vp]),
     "fwn_front": (C.c_int, [C.POINTER(FlowDesc), vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
     "fwn_gate": (C.c_int, [C.POINTER(FlowDesc), C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, vp]),
+    "fwn_gate_tile": (C.c_int, [C.POINTER(FlowDesc), C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "fwn_tail_can_chain": (C.c_int, [C.POINTER(FlowDesc), C.c_int, C.c_int]),
     "fwn_tail_partials_chained": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "fwn_tail_chained": (C.c_int, [C.POINTER(FlowDesc), C.POINTER(FlowDesc), vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]),

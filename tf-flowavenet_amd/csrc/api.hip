@@ -111,7 +111,7 @@ void fwn_run_stages(const fwn_flow_desc* d, const FlowStages& s, float* xa, cons
                                 d->kcpad, st);
         else
             fwn_launch_gate(s.h[l], ca, P ? P + (size_t)l * M * 512 : nullptr, d->Wd[l], d->Wc[l], s.gate_stream ? d->Wgs[l] : nullptr,
-                            d->bgate[l], s.o[l], M, Ti, dilation_of(l), d->cin, d->kcpad, s.aux[l], st);
+                            s.gate_stream ? d->Wds[l] : nullptr, d->bgate[l], s.o[l], M, Ti, dilation_of(l), d->cin, d->kcpad, s.aux[l], st);
         if (l + 1 < d->L) {
             fwn_launch_res(s.o[l], s.h[l], d->Wres[l], d->bres[l], s.h[l + 1], M, s.h8[l + 1], st);
             rows.zero(s.h[l + 1], Ti, 512, 2 * d->Ch);
@@ -279,6 +279,7 @@ static int check_desc(const fwn_flow_desc* d) {
                 "flow desc: Wgs[%d] given but no register-streamed gate kernel exists for cin = %d (or misaligned)", l, d->cin);
     REQUIRE(!d->Wts || (ALIGNED16(d->Wts) && fwn_tail_stream_size(d->L) != 0),
             "flow desc: Wts given but no register-streamed tail kernel exists for L = %d (or misaligned)", d->L);
+    for (int l = 0; l < d->L; ++l) REQUIRE(!d->Wds[l] || ALIGNED16(d->Wds[l]), "flow desc: Wds[%d] misaligned", l);
     if (d->Wfront3)
         REQUIRE(d->Ch <= 8 && d->kf3 == (6 * d->Ch + 15) / 16 * 16 && ALIGNED16(d->Wfront3),
                 "flow desc: Wfront3 needs Ch <= 8 and kf3 = 6 Ch rounded up to 16 (Ch %d, kf3 %d)", d->Ch, d->kf3);
@@ -305,9 +306,28 @@ int fwn_gate(const fwn_flow_desc* d, int layer, const void* h, const void* ca, c
     REQUIRE(h && o && M > 0 && Ti > 0 && M % Ti == 0, "fwn_gate: bad argument");
     REQUIRE((ca != nullptr) != (P != nullptr), "fwn_gate: exactly one of ca / P");
     REQUIRE(ALIGNED16(h) && ALIGNED16(o) && ALIGNED16(ca), "fwn_gate: buffers must be 16-byte aligned");
-    fwn_launch_gate(h, ca, P, d->Wd[layer], d->Wc[layer], d->Wgs[layer], d->bgate[layer], o, M, Ti, dilation_of(layer),
-                    d->cin, d->kcpad, nullptr, (hipStream_t)stream);
+    fwn_launch_gate(h, ca, P, d->Wd[layer], d->Wc[layer], d->Wgs[layer], d->Wds[layer], d->bgate[layer], o, M, Ti,
+                    dilation_of(layer), d->cin, d->kcpad, nullptr, (hipStream_t)stream);
     return check_launch("fwn_gate");
+}
+
+int fwn_gate_tile(const fwn_flow_desc* d, int layer, const void* h, const float* P, void* o, int M, int Ti, int rows, int cols,
+                  void* stream) {
+    int rc = check_desc(d);
+    if (rc) return rc;
+    REQUIRE(layer >= 0 && layer < d->L && h && P && o && M > 0 && Ti > 0 && M % Ti == 0, "fwn_gate_tile: bad argument");
+    REQUIRE(ALIGNED16(h) && ALIGNED16(o), "fwn_gate_tile: buffers must be 16-byte aligned");
+    int n = 0;
+    if (cols == 128) {
+        n = fwn_launch_gate_ring_tile(h, P, d->Wd[layer], d->bgate[layer], o, M, Ti, dilation_of(layer), rows, (hipStream_t)stream);
+    } else {
+        REQUIRE(d->Wds[layer], "fwn_gate_tile: the flow has no Wd stream (fwn_flow_desc.Wds)");
+        REQUIRE(fwn_gate_hs_ok(M, Ti, dilation_of(layer)), "fwn_gate_tile: M = %d, Ti = %d, layer %d is outside the streamed hoisted gate's range", M, Ti, layer);
+        n = fwn_launch_gate_hs(h, d->Wds[layer], d->bgate[layer], P, o, M, Ti, dilation_of(layer), rows, cols, (hipStream_t)stream);
+    }
+    REQUIRE(n > 0, "fwn_gate_tile: no %d x %d tile", rows, cols);
+    rc = check_launch("fwn_gate_tile");
+    return rc ? rc : n;
 }
 
 int fwn_gate_train(const fwn_flow_desc* d, int layer, const void* h, const void* ca, const float* P, void* o, void* aux,
@@ -318,7 +338,7 @@ int fwn_gate_train(const fwn_flow_desc* d, int layer, const void* h, const void*
     REQUIRE(h && o && aux && M > 0 && Ti > 0 && M % Ti == 0, "fwn_gate_train: bad argument");
     REQUIRE((ca != nullptr) != (P != nullptr), "fwn_gate_train: exactly one of ca / P");
     REQUIRE(ALIGNED16(h) && (!ca || ALIGNED16(ca)), "fwn_gate_train: buffers must be 16-byte aligned");
-    fwn_launch_gate(h, ca, P, d->Wd[layer], d->Wc[layer], nullptr, d->bgate[layer], o, M, Ti, dilation_of(layer),
+    fwn_launch_gate(h, ca, P, d->Wd[layer], d->Wc[layer], nullptr, nullptr, d->bgate[layer], o, M, Ti, dilation_of(layer),
                     d->cin, d->kcpad, aux, (hipStream_t)stream);
     return check_launch("fwn_gate_train");
 }

@@ -47,21 +47,24 @@ struct CondRsArgs {
 //   pieces of items 0 .. 2, ring loads W(0 .. R-2) (two per k-step); then per item i, per k-step g = 4 i + l:
 //   [l = 0: wait for the own pieces of item i, barrier] [wait for W(g)] [l = 0: the 2 pieces of item i + 3] the 2 loads of W(g + R - 1)
 // walked at compile time; the kernel's constants are checked against it.
-template <int R>
+// PPW: pieces per wave and item (2: the conditioning kernel and the 8-wave hoisted gate; MT: the 4-wave hoisted gate, whose
+// pieces ride the first PPW MFMA slots of an item's first k-step and whose weight loads follow them)
+template <int R, int PPW = 2>
 struct CrsCount {
     static constexpr int AHEAD = 3;
+    static constexpr int prologue = AHEAD * PPW + 2 * (R - 1);      // operations of the prologue: what is younger than anything issued in front of it
     // ops issued after the second load of W(g) when k-step g waits for it (kind 0) / after the second piece of item i at its barrier (kind 1)
     static constexpr int after(int kind, int key) {
         int count = -1;
 #define CRS_OP(k_, a_) do { if (count >= 0) ++count; if (kind == (k_) && key == (a_)) count = 0; } while (0)
-        for (int i = 0; i < AHEAD; ++i) { CRS_OP(2, -1); CRS_OP(1, i); }
+        for (int i = 0; i < AHEAD; ++i) { for (int j = 0; j < PPW - 1; ++j) CRS_OP(2, -1); CRS_OP(1, i); }
         for (int g = 0; g < R - 1; ++g) { CRS_OP(2, -1); CRS_OP(0, g); }
         for (int i = 0; i < 64; ++i)
             for (int l = 0; l < 4; ++l) {
                 const int g = 4 * i + l;
                 if (l == 0 && kind == 1 && key == i) return count;
                 if (kind == 0 && key == g) return count;
-                if (l == 0) { CRS_OP(2, -1); CRS_OP(1, i + AHEAD); }
+                if (l == 0) { for (int j = 0; j < PPW - 1; ++j) CRS_OP(2, -1); CRS_OP(1, i + AHEAD); }
                 CRS_OP(2, -1); CRS_OP(0, g + R - 1);
             }
 #undef CRS_OP
@@ -216,6 +219,177 @@ __global__ __launch_bounds__(512) void cond_rs_kernel(CondRsArgs p) {
 #pragma unroll
             for (int r = 0; r < 16; ++r)
                 buf_store_f32(so, voff, (uint32_t)((mi * 32 + acc_row_c(r)) * 512 * 4), acc[mi][cg][r]);
+    }
+}
+
+// ---- Hoisted gate, register-streamed form (round 7): o = tanh(f) sigmoid(g) with f | g = bias + taps(h) @ Wd^T + P, for the row
+// counts at which the ring path runs its un-split 64 x 128 tile (one workgroup per CU for a 12-chunk serial chain: DESIGN.md
+// section 3.4).  The kernel above with three changes:
+//   * the staged operand is h [M][256]: K = 768 is 12 items of 64 columns, item q = tap q / 4, channel slice q % 4 (GateProb::chunk_ctx's
+//     order, which is also the natural K order of Wd: the stream is fwn_pack_cond_stream of Wd with kcpad = 768); a piece row is
+//     row m0 + jrow + (tap - 1) dil of h, or zeros where the tap leaves the clip (GateProb::a_voff's rule);
+//   * the accumulators start at bias[column] (columns are on lanes here: two buffer loads per lane issued in front of the
+//     prologue - the oldest operations of the wave, waited for with the prologue's own count);
+//   * the epilogue adds P and applies the ring epilogue's gated unit (gated_unit2 on the same pairs): acc[mi][0] and acc[mi][1]
+//     of a wave are filter and gate of channel 32 wave + lr, so it is lane-local.
+// Every output element sees the ring tile's MFMAs in the ring tile's order: the results are bit-identical.
+// NW = 8: a workgroup owns all 512 columns; NW = 4: 256 columns (waves 4 half .. 4 half + 3 of the stream), MT pieces per wave.
+struct GateHsArgs {
+    const bf16* h;          // [M][256]
+    const bf16* Ws;         // fragment stream of Wd: [8 waves][48 k-steps][2][64][8]
+    const float* bias;      // [512] packed-N order
+    const float* P;         // [M][512] packed-N order
+    bf16* o;                // [M][256]
+    int M, Ti, dil;
+};
+__device__ __forceinline__ void crs_fload(float& dst, u32x4 srd, uint32_t voff) {
+    asm volatile("s_nop 4\n\tbuffer_load_dword %0, %1, %2, 0 offen" : "=v"(dst) : "v"(voff), "s"(srd) : "memory");
+}
+template <int N>
+__device__ __forceinline__ void crs_fwait2(float& a, float& b) {
+    static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit counter");
+    asm volatile("s_waitcnt vmcnt(%2)" : "+v"(a), "+v"(b) : "n"(N) : "memory");
+}
+
+template <int MT, int NW, int R = 8>
+__global__ __launch_bounds__(64 * NW, 8 / NW) void gate_hs_kernel(GateHsArgs p) {      // two waves per SIMD either way: two 4-wave workgroups share a CU
+    constexpr int PPW = NW == 8 ? 2 : MT;                // pieces per wave and item: 8 NW PPW slot rows >= 32 MT
+    constexpr int WS = PPW > 2 ? PPW : 2;                // MFMA slot of a k-step's first weight load (behind the pieces)
+    using C = CrsCount<R, PPW>;
+    static_assert(R == 8, "a pair of items = 8 k-steps = one turn of the ring");
+    static_assert(NW == 8 || NW == 4, "512 or 256 columns per workgroup");
+    static_assert(MT >= 2 && MT <= 4 && WS + 2 <= 2 * MT, "the pieces and the two loads of a k-step ride its MFMAs");
+    static_assert(C::steady(), "the vmcnt schedule must repeat from the second pair of items on");
+    static_assert(C::wait_item0 >= 0 && C::wait_item >= C::wait_item0 && C::wait_item < 64, "piece waits");
+    constexpr int BM = 32 * MT, SLOT = 128 * 128, AHEAD = C::AHEAD, NITEM = 12;
+    __shared__ __attribute__((aligned(1024))) unsigned char lds[4 * SLOT];
+    const uint32_t lds0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uintptr_t)(lds_ptr_t)lds);
+    const int wg = xcd_remap(blockIdx.x, gridDim.x);
+    constexpr int NH = 8 / NW;                            // column halves
+    const int half = wg % NH, rt = wg / NH;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wv = half * NW + wave;                      // this wave's 64 columns: its stream, its bias, its 32 channels
+    const int lr = lane & 31, lh = lane >> 5;
+    const int M = p.M, Ti = p.Ti, dil = p.dil, m0 = rt * BM;
+
+    // ---- bias: the first two vector-memory operations of the wave
+    const u32x4 sb = crs_srd(p.bias, 512u * 4u);
+    float b0, b1;
+    crs_fload(b0, sb, (uint32_t)(wv * 64 + lr) * 4u);
+    crs_fload(b1, sb, (uint32_t)(wv * 64 + 32 + lr) * 4u);
+
+    // ---- DMA pieces: piece j of this wave = slot rows 8 (wave + NW j) .. + 7 of item i in slot i % 4
+    const u32x4 srd_a = crs_srd(p.h, (uint32_t)((size_t)M * FWN_HID * 2));
+    int tq[PPW];                                          // time index within its clip of this lane's row of piece j
+#pragma unroll
+    for (int j = 0; j < PPW; ++j) tq[j] = (m0 + 8 * (wave + NW * j) + (lane >> 3)) % Ti;
+    auto issue_piece = [&](int i, int j) {
+        const int pi = wave + NW * j;
+        const int jrow = 8 * pi + (lane >> 3);
+        const int c = (lane & 7) ^ ((jrow >> 1) & 7);
+        const int shift = ((i >> 2) - 1) * dil;
+        const bool ok = (i < NITEM) & (jrow < BM) & (m0 + jrow < M) & ((unsigned)(tq[j] + shift) < (unsigned)Ti);
+        crs_dma16(srd_a, ok ? (uint32_t)((m0 + jrow + shift) * FWN_HID + (i & 3) * 64 + c * 8) * 2u : FWN_OOB,
+                  lds0 + (uint32_t)((i & 3) * SLOT + pi * 1024));
+    };
+    // ---- this wave's weight stream: k-step g -> ring stage g % 8, two fragments; past k-step 47 out of range (zeros)
+    constexpr int NKS = NITEM * 4;
+    const unsigned long long wbase = (unsigned long long)(uintptr_t)p.Ws + (unsigned long long)wv * NKS * 2048ull;
+    const u32x4 wsrd = {(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)wbase),
+                        (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(wbase >> 32)) & 0xffffu,
+                        (uint32_t)(NKS * 2048), 0x00020000u};
+    const uint32_t wl = (uint32_t)lane * 16u;
+    bf16x8 wq[R][2];
+    auto issue_w = [&](auto G, auto F, int pairbase) {
+        constexpr int g = decltype(G)::value, f = decltype(F)::value;
+        constexpr int off = g * 2048 + f * 1024;
+        rs_wload<off % 4096>(wq[g % R][f], wsrd, (uint32_t)(pairbase + (off / 4096) * 4096), wl);
+    };
+
+    // ---- prologue (order = CrsCount::after)
+#pragma unroll
+    for (int i = 0; i < AHEAD; ++i)
+#pragma unroll
+        for (int j = 0; j < PPW; ++j) issue_piece(i, j);
+    rs_static_for<R - 1>([&](auto G) {
+        issue_w(G, std::integral_constant<int, 0>{}, 0);
+        issue_w(G, std::integral_constant<int, 1>{}, 0);
+    });
+    crs_fwait2<C::prologue>(b0, b1);                      // everything younger than the bias loads is the prologue
+
+    f32x16 acc[MT][2];
+#pragma unroll
+    for (int mi = 0; mi < MT; ++mi)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            acc[mi][0][r] = b0;
+            acc[mi][1][r] = b1;
+        }
+    const int xv = (lh ^ ((lr >> 1) & 7)) << 4;
+    const int rb = lr * 128;
+    bf16x8 hf[MT];
+
+#pragma nounroll
+    for (int pr = 0; pr < NITEM / 2; ++pr) {
+        const int pairbase = pr * (8 * 2048);
+        rs_static_for<8>([&](auto POS) {
+            constexpr int pos = decltype(POS)::value, e = pos >> 2, l = pos & 3;
+            const int i = 2 * pr + e;
+            const unsigned char* la = lds + (i & 3) * SLOT + rb;
+            if constexpr (l == 0) {
+                if (i == 0) rs_vmwait<C::wait_item0>(); else rs_vmwait<C::wait_item>();
+                FWN_RING_BARRIER();
+            }
+            crs_wwait2<C::wait_kstep(pos)>(wq[pos][0], wq[pos][1]);
+            if constexpr (l == 0) {
+#pragma unroll
+                for (int mi = 0; mi < MT; ++mi) hf[mi] = *(const bf16x8*)(la + mi * 4096 + xv);
+            }
+            int kon = ((l + 1) * 32) ^ xv;
+            asm volatile("" : "+v"(kon));
+            __builtin_amdgcn_sched_barrier(0);
+            rs_static_for<2 * MT>([&](auto S) {
+                constexpr int s = decltype(S)::value, mi = s >> 1, cg = s & 1;
+                acc[mi][cg] = mfma32(hf[mi], wq[pos][cg], acc[mi][cg]);
+                if constexpr (cg == 1 && l < 3) hf[mi] = *(const bf16x8*)(la + mi * 4096 + kon);
+                if constexpr (l == 0 && s < PPW) issue_piece(i + AHEAD, s);
+                if constexpr (s == WS) issue_w(std::integral_constant<int, pos + R - 1>{}, std::integral_constant<int, 0>{}, pairbase);
+                if constexpr (s == WS + 1) issue_w(std::integral_constant<int, pos + R - 1>{}, std::integral_constant<int, 1>{}, pairbase);
+                __builtin_amdgcn_sched_barrier(0);
+            });
+        });
+    }
+    // the look-ahead loads and pieces past the K range (out of range: zeros) must have landed before the registers / the LDS
+    // are anyone else's; the P loads below are the compiler's own, with nothing of ours in flight
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+    crs_touch_all<0, R>(wq);
+
+    // ---- epilogue (GateProb::epilogue_impl's hoisted-P arm, the same expression on the same pairs): register r of tile
+    // (mi, cg) = row m0 + 32 mi + acc_row_c(r) + 4 lh, packed column 64 wv + 32 cg + lr = filter | gate of channel 32 wv + lr
+    const srd_t sp = make_srd(p.P, (uint32_t)((size_t)M * 512 * 4));
+    const srd_t so = make_srd(p.o, (uint32_t)((size_t)M * FWN_HID * 2));
+    const int rbase = m0 + 4 * lh;
+    const uint32_t vp = (uint32_t)(rbase * 512 + wv * 64 + lr) * 4u;
+    const uint32_t voff = (uint32_t)(rbase * FWN_HID + wv * 32 + lr) * 2u;
+#pragma unroll
+    for (int mi = 0; mi < MT; ++mi) {
+        float pf[16], pg[16];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const uint32_t sro = (uint32_t)((mi * 32 + acc_row_c(r)) * 512 * 4);
+            pf[r] = buf_load_f32(sp, vp, sro);
+            pg[r] = buf_load_f32(sp, vp, sro + 128);
+        }
+#pragma unroll
+        for (int r = 0; r < 16; r += 2) {
+            const f32x2 y = gated_unit2(
+                f32x2{acc[mi][0][r], acc[mi][0][r + 1]} + f32x2{pf[r], pf[r + 1]},
+                f32x2{acc[mi][1][r], acc[mi][1][r + 1]} + f32x2{pg[r], pg[r + 1]});
+            buf_store_bf16(so, voff, (uint32_t)((mi * 32 + acc_row_c(r)) * FWN_HID * 2), y.x);
+            buf_store_bf16(so, voff, (uint32_t)((mi * 32 + acc_row_c(r + 1)) * FWN_HID * 2), y.y);
+        }
     }
 }
 

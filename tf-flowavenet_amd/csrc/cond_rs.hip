@@ -67,3 +67,23 @@ void fwn_launch_cond_rs(const void* ca, const void* ca_odd, const void* Ws, floa
     if (mt == 4) hipLaunchKernelGGL((cond_rs_kernel<4>), grid, dim3(512), 0, st, a);
     else hipLaunchKernelGGL((cond_rs_kernel<3>), grid, dim3(512), 0, st, a);
 }
+
+// ---- the hoisted gate from the fragment stream of Wd (gate_hs_kernel).  The caller has checked fwn_gate_hs_ok (flow_kernels.hip:
+// the rows of the ring path's un-split 64 x 128 tile).  rows / cols = 0: the shipped tile (profiles/r07_notes.md: the least
+// workgroups x launch time among the instantiations and the fatter ring tiles).
+#ifndef FWN_GATE_HS_ROWS
+#define FWN_GATE_HS_ROWS 64
+#define FWN_GATE_HS_COLS 256
+#endif
+int fwn_launch_gate_hs(const void* h, const void* Wds, const float* bias, const float* P, void* o, int M, int Ti, int dil,
+                       int rows, int cols, hipStream_t st) {
+    if (rows == 0 && cols == 0) { rows = FWN_GATE_HS_ROWS; cols = FWN_GATE_HS_COLS; }
+    if ((rows != 64 && rows != 96 && rows != 128) || (cols != 512 && cols != 256)) return 0;
+    GateHsArgs a{(const bf16*)h, (const bf16*)Wds, bias, P, (bf16*)o, M, Ti, dil};
+    const int grid = ((M + rows - 1) / rows) * (512 / cols);
+#define GATE_HS(MT, NW) hipLaunchKernelGGL((gate_hs_kernel<MT, NW>), dim3(grid), dim3(64 * NW), 0, st, a)
+    if (cols == 512) { if (rows == 64) GATE_HS(2, 8); else if (rows == 96) GATE_HS(3, 8); else GATE_HS(4, 8); }
+    else { if (rows == 64) GATE_HS(2, 4); else if (rows == 96) GATE_HS(3, 4); else GATE_HS(4, 4); }
+#undef GATE_HS
+    return grid;
+}

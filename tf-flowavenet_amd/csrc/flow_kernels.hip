@@ -887,18 +887,19 @@ template <class Prob>
 static void launch_ring(const Prob& p, int M, int N, int ksteps, hipStream_t st) {
     // 16-wave workgroups (4 waves per SIMD) hide the barrier / LDS latency of the K loop best
     // (tools/bench_gemm.hip): 256x256 reaches ~0.8 PF on the block-1 gate, 8-wave tiles ~0.7.
-    const int FILL = 192;    // workgroups needed before a fatter tile pays (256 CUs)
+    // (the FILL rule itself is fwn_ring_tile_for, fwn_internal.h: the hoisted streamed gate's range is derived from it)
+    const fwn_ring_tile tile = fwn_ring_tile_for(M, N, Prob::ALLOW_256);
     if constexpr (Prob::ALLOW_256) {
-        if (N % 256 == 0 && ((M + 255) / 256) * (N / 256) >= FILL) {
+        if (tile == FWN_RING_256x256) {
             RING_LAUNCH(256, 256, 4, 4, 64, 2);
             return;
         }
     }
-    if (((M + 255) / 256) * (N / 128) >= FILL) {
+    if (tile == FWN_RING_256x128) {
         RING_LAUNCH(256, 128, 8, 2, 64, 3);
-    } else if (((M + 127) / 128) * (N / 128) >= FILL) {
+    } else if (tile == FWN_RING_128x128) {
         RING_LAUNCH(128, 128, 4, 2, 64, 3);
-    } else if (((M + 63) / 64) * (N / 128) >= FILL) {
+    } else if (tile == FWN_RING_64x128) {
         RING_LAUNCH(64, 128, 2, 2, 64, 4);
     } else {
         // A launch this small is a latency chain: per K chunk every wave pays its DMA issues (~100+ cycles a piece), a
@@ -944,7 +945,25 @@ void fwn_launch_front(const float* xa, const float* an_a, const void* W, const v
 }
 
 // (the register-streamed gate - gate_rs.h - and its dispatch rule live in gate_rs.hip: fwn_launch_gate_rs)
-void fwn_launch_gate(const void* h, const void* ca, const float* P, const void* Wd, const void* Wc, const void* Wgs,
+// The hoisted streamed gate (cond_rs.h gate_hs_kernel) serves exactly the rows at which the code below would reach launch_ring's
+// un-split 64 x 128 tile: its summation order is that tile's.  (Fewer rows take the split-K tile, whose four partial sums
+// flow_persist_kernel reproduces; more rows the tap-sharing or fatter tiles.)
+bool fwn_gate_hs_ok(int M, int Ti, int dil) {
+    return dil <= FWN_HALO_MAXDIL && Ti >= 2 * dil && fwn_ring_tile_for(M, 512, GateProb::ALLOW_256) == FWN_RING_64x128;
+}
+int fwn_launch_gate_ring_tile(const void* h, const float* P, const void* Wd, const float* bias, void* o, int M, int Ti, int dil,
+                              int rows, hipStream_t st) {
+    typedef GateProb Prob;
+    GateProb p{(const bf16*)h, nullptr, P, (const bf16*)Wd, nullptr, bias, (bf16*)o, M, Ti, dil, 0, 0};
+    const int N = 512;
+    if (rows == 64) RING_LAUNCH(64, 128, 2, 2, 64, 4);
+    else if (rows == 128) RING_LAUNCH(128, 128, 4, 2, 64, 3);
+    else if (rows == 256) RING_LAUNCH(256, 128, 8, 2, 64, 3);
+    else return 0;
+    return ((M + rows - 1) / rows) * 4;
+}
+
+void fwn_launch_gate(const void* h, const void* ca, const float* P, const void* Wd, const void* Wc, const void* Wgs, const void* Wds,
                      const float* bias, void* o, int M, int Ti, int dil, int cin, int kcpad, void* aux,
                      hipStream_t st) {
     if (Wgs && fwn_gate_stream_ok(M, Ti, dil, cin, ca != nullptr && P == nullptr, aux != nullptr)) {
@@ -973,6 +992,7 @@ void fwn_launch_gate(const void* h, const void* ca, const float* P, const void* 
         hipLaunchKernelGGL((gate_halo_kernel<128, 128, GateProb>), dim3(t128 * 4), dim3(512), 0, st, p, 4);
         return;
     }
+    if (P && !ca && !aux && Wds && fwn_gate_hs_ok(M, Ti, dil) && fwn_launch_gate_hs(h, Wds, bias, P, o, M, Ti, dil, 0, 0, st) > 0) return;
     launch_ring(p, M, 512, (768 + (ca ? kcpad : 0)) / 16, st);
 }
 

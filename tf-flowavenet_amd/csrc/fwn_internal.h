@@ -9,9 +9,30 @@ void fwn_launch_front(const float* xa, const float* an_a, const void* W, const v
 // fwn_gate_stream_ok says so
 int fwn_launch_gate_clock(const void* h, const void* ca, const void* Wgs, const float* bias, void* o, int M, int Ti, int dil, int cin,
                           unsigned long long* clk, hipStream_t st);
-void fwn_launch_gate(const void* h, const void* ca, const float* P, const void* Wd, const void* Wc, const void* Wgs,
+// Wds: Wd alone in the conditioning kernel's fragment order (fwn_launch_cond_stream_pack, kcpad = 768) or nullptr; used with a
+// hoisted P where fwn_gate_hs_ok says so
+void fwn_launch_gate(const void* h, const void* ca, const float* P, const void* Wd, const void* Wc, const void* Wgs, const void* Wds,
                      const float* bias, void* o, int M, int Ti, int dil, int cin, int kcpad, void* aux,
                      hipStream_t st);
+// The tile launch_ring (flow_kernels.hip) picks for an M x N product: the largest that still yields about one workgroup per CU.
+enum fwn_ring_tile { FWN_RING_256x256, FWN_RING_256x128, FWN_RING_128x128, FWN_RING_64x128, FWN_RING_SPLITK };
+inline fwn_ring_tile fwn_ring_tile_for(int M, int N, bool allow256) {
+    const int FILL = 192;    // workgroups needed before a fatter tile pays (256 CUs)
+    if (allow256 && N % 256 == 0 && ((M + 255) / 256) * (N / 256) >= FILL) return FWN_RING_256x256;
+    if (((M + 255) / 256) * (N / 128) >= FILL) return FWN_RING_256x128;
+    if (((M + 127) / 128) * (N / 128) >= FILL) return FWN_RING_128x128;
+    if (((M + 63) / 64) * (N / 128) >= FILL) return FWN_RING_64x128;
+    return FWN_RING_SPLITK;  // 64 x 64 tiles, the K range dealt over wave groups (flow_persist_kernel reproduces their partial sums)
+}
+// cond_rs.hip: the hoisted gate from the fragment stream of Wd (gate_hs_kernel, cond_rs.h).  fwn_gate_hs_ok: the shape is one the
+// ring path would give its un-split 64 x 128 tile; rows / cols: the workgroup tile (64 | 96 | 128 rows x 512 | 256 columns),
+// 0 / 0 = the shipped one.  Returns the number of workgroups launched, 0 if there is no such tile.
+bool fwn_gate_hs_ok(int M, int Ti, int dil);
+int fwn_launch_gate_hs(const void* h, const void* Wds, const float* bias, const float* P, void* o, int M, int Ti, int dil,
+                       int rows, int cols, hipStream_t st);
+// measurement control: the same gate on a given ring tile (rows 64 | 128 | 256, 128 columns); 0 if there is no such tile
+int fwn_launch_gate_ring_tile(const void* h, const float* P, const void* Wd, const float* bias, void* o, int M, int Ti, int dil,
+                              int rows, hipStream_t st);
 long fwn_gate_stream_size(int cin);        // bytes, 0: no kernel for this cin
 int fwn_gate_stream_min_rows();
 int fwn_gate_stream_ok(int M, int Ti, int dil, int cin, bool fused_cond, bool aux);

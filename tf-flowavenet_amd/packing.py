@@ -336,12 +336,12 @@ class PackedModel:
 
 def pack_model(params, hp, device="cuda", cond_mode: int = 0, refresh: bool = False,
                gate_fp8: bool = False, persist_mode: int = 0, chain_mode: int = 0, tail_stream: bool = True,
-               cond_stream: bool = True) -> PackedModel:
+               cond_stream: bool = True, gate_hs_stream: bool = True) -> PackedModel:
     """Pack ``params`` (reference layouts, fp32; NumPy or device tensors) for the kernels (K10): the work is recorded
     into a ``PackPlan`` over the parameters as views of one flat fp32 device vector (``weights.flat_views``: the
     optimiser's masters as they are, anything else copied once) and run once.
-    refresh=False (inference): the fragment-order streams derived from the packed weights - gate (``Wgs``), hoisted
-    conditioning (``cond_stream``) and the fp8 gate - are packed once more and the plan is dropped: the model keeps only
+    refresh=False (inference): the fragment-order streams derived from the packed weights - gate (``Wgs``), hoisted gate
+    (``Wds``, ``gate_hs_stream``), hoisted conditioning (``cond_stream``) and the fp8 gate - are packed once more and the plan is dropped: the model keeps only
     its own buffers.  refresh=True (training): none of those streams, and ``pm.plan`` is kept - ``pm.plan.refresh()``
     repeats the work after the parameters changed in place (their descriptors keep ``tail_kernel`` and the ring gates)."""
     import torch
@@ -548,6 +548,17 @@ def pack_model(params, hp, device="cuda", cond_mode: int = 0, refresh: bool = Fa
                 _lib.check(lib.fwn_pack_gate_stream(wd.data_ptr(), wc.data_ptr(), cin, kcpad, wgs.data_ptr(), stream),
                            "fwn_pack_gate_stream")
                 d.Wgs[l] = wgs.data_ptr()
+        # Wd[l] alone in the conditioning kernel's fragment order (K = 768, one matrix): the gate with a hoisted P at the rows
+        # of the ring path's un-split 64 x 128 tile (csrc/cond_rs.h gate_hs_kernel); 768 KiB per (flow, layer)
+        ds_bytes = int(lib.fwn_cond_stream_bytes(3 * FILTER)) if gate_hs_stream else 0
+        if ds_bytes:
+            wds_all = pm.keep(torch.empty(len(gate_streams) * ds_bytes, dtype=torch.uint8, device=dev))
+            pm.weight_bytes += len(gate_streams) * ds_bytes
+            for n, (d, l, wd, wc, cin, kcpad) in enumerate(gate_streams):
+                wds = wds_all[n * ds_bytes:(n + 1) * ds_bytes]
+                _lib.check(lib.fwn_pack_cond_stream(wd.data_ptr(), GATE_N * 3 * FILTER, 3 * FILTER, 1, wds.data_ptr(), stream),
+                           "fwn_pack_cond_stream")
+                d.Wds[l] = wds.data_ptr()
         for i, wc_blk, kcpad in cond_blocks:
             cs_bytes = int(lib.fwn_cond_stream_bytes(kcpad)) if (cond_stream and kcpad >= 640 and i < 16) else 0
             if cs_bytes:
