@@ -559,15 +559,35 @@ def test_streamed_conditioning_equals_the_ring_projection_bit_for_bit(full_model
 
 @pytest.mark.parametrize("blk,m", [(0, 50000), (0, 13000), (6, 13000), (7, 12500), (2, 7000), (7, 7000), (3, 2000), (5, 700), (6, 300), (7, 150)])
 def test_tail_train_keeps_s_u_z_and_equals_the_plain_tail(full_model, blk, m):
-    """fwn_tail_train (the tail as the training step's forward half runs it) at every tail variant - 256-row and 128-row
-    register-chained kernel, N-split + chained kernel, three ring GEMMs; 1, 2 and 4 ZeroConv pair tiles: the planes and the
-    log-det partials are the bits fwn_tail gives, and what it keeps for the backward matches fp64 arithmetic on the
+    """fwn_tail_train (the tail as the training step's forward half runs it) on the model's own packed operands: the planes
+    and the log-det partials are the bits fwn_tail gives, and what it keeps for the backward matches fp64 arithmetic on the
     reference's weights (modules.py:175-180,51-56): S = ReLU(sum_l skip_l(o_l)), U = ReLU(final(S)), Z = ZeroConv(U) before
-    its exp(3 scale) factor, columns = (log_s | t) in plane channel order."""
+    its exp(3 scale) factor, columns = (log_s | t) in plane channel order.
+    An inference pack carries the fragment stream Wts for every flow with one ZeroConv pair tile (Ch <= 32), so the forms
+    these cases run (tail_form of tests/test_infer_stage_refs.py) are: (0, 50000) the 256-row register-chained kernel, one pair
+    tile; (0, 13000), (2, 7000), (3, 2000) the register-streamed tail with 4, 2 and 1 row tiles; (6, 13000), (7, 12500) the
+    128-row register-chained kernel with 2 and 4 pair tiles; (7, 7000) N-split + chained kernel, 4 pair tiles; (5, 700),
+    (6, 300), (7, 150) the three ring GEMMs with 1, 2 and 4 pair tiles.  The 128-row kernel and the N-split chain with ONE
+    pair tile are what the same rows take without Wts: the test below."""
+    _tail_train_case(full_model, blk, m, True)
+
+
+@pytest.mark.parametrize("blk,m", [(0, 13000), (2, 7000)])
+def test_tail_train_without_the_fragment_stream_keeps_s_u_z(full_model, blk, m):
+    """The same on a descriptor copy with Wts = NULL (fwn.h: "NULL = not packed"; packing.pack_model(tail_stream=False)):
+    13 000 rows of block 0 run the 128-row register-chained kernel, 7 000 rows of block 2 the N-split + chained kernel, both
+    with one ZeroConv pair tile - the forms whose S / U / Z the cases above no longer reach."""
+    _tail_train_case(full_model, blk, m, False)
+
+
+def _tail_train_case(full_model, blk, m, keep_stream):
     hp, model, _, _, _ = full_model
     lib = _lib.load()
     L, ch = hp.n_layer, 1 << blk
-    d = model._packed.flow_descs[blk * hp.n_flow]
+    d = _lib.FlowDesc.from_buffer_copy(model._packed.flow_descs[blk * hp.n_flow])
+    if not keep_stream:
+        assert d.Wts and m < 49152
+        d.Wts = None
     p64 = onp.to_f64(W.synthetic_params(hp, 1234))
     wp = W.flow_prefix(blk, 0) + "/WaveNet"
     rng = np.random.default_rng(blk * 1000 + m)

@@ -489,8 +489,13 @@ __global__ __launch_bounds__(64 * NW) void tail_kernel(TailArgs a) {
                         zl[e] = __builtin_bit_cast(unsigned int, acc[2 * pt][4 * g + e] + bzl[pt * 64 + j0 + e]);
                         zt[e] = __builtin_bit_cast(unsigned int, acc[2 * pt + 1][4 * g + e] + bzl[pt * 64 + 32 + j0 + e]);
                     }
+                    // The t half's offset Ch * 4 goes into the VGPR offset, not into soffset: with an SGPR soffset hipcc pads no
+                    // wait state between a 16-byte store and a VALU write of its data registers (it takes the hazard to exist
+                    // only without one), and gfx950 then stored the NEXT group's log_s sum in element 1 of this t group now and
+                    // then (NPT >= 2, waves 4 - 7 of the 256-row form: DESIGN.md "Toolchain pitfalls").
+                    const uint32_t zoff_t = zoff != FWN_OOB ? zoff + (uint32_t)tsoff : FWN_OOB;
                     __builtin_amdgcn_raw_buffer_store_b128(zl, sz, zoff, 0, 0);
-                    __builtin_amdgcn_raw_buffer_store_b128(zt, sz, zoff, tsoff, 0);
+                    __builtin_amdgcn_raw_buffer_store_b128(zt, sz, zoff_t, 0, 0);
                 }
             } else {
 #pragma unroll
