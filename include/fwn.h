@@ -740,6 +740,38 @@ int fwn_model_synthesize(const fwn_model_desc* m, int64_t B, int64_t T, const fl
                          const uint32_t* clip_id_dev, float temp, const int32_t* len_dev, void* workspace, size_t workspace_bytes,
                          int16_t* pcm_out, float* wav_out, float* z_out, void* stream);
 
+/* ---- device-resident corpus (additive; FWN_VERSION unchanged): a training batch drawn and gathered on the device.
+ *
+ * Layout.  audio: flat fp32, all utterances back to back; mel: flat fp32 [total_frames][num_mels]; frame_off: DEVICE int64
+ * [n_utt + 1], non-decreasing.  Utterance u owns frames [frame_off[u], frame_off[u+1]) of mel and the samples from
+ * hop * frame_off[u] of audio: the loader keeps min(mel frames, audio samples / hop) frames of each utterance, so one table
+ * serves both arrays.  Every offset is int64 (a corpus of more than 2^31 samples is the ordinary case); one utterance holds
+ * fewer than 2^31 frames.
+ *
+ * The draw (this library's own stream, like fwn_latent_normal's; restated in NumPy by tests/corpus_ref.py).  d = the uint64 at
+ * *counter_dev.  Slot b < B takes r = Philox4x32-10(counter = (d & 0xffffffff, d >> 32, b, stream_id), key = (seed &
+ * 0xffffffff, seed >> 32)) and of it
+ *     u = (r0 * n_utt) >> 32                                   (64-bit product), n = frame_off[u+1] - frame_off[u];
+ *     n > F :  start = (r1 * (n - F)) >> 32, frames = F        (a crop from [0, n - F), the range of dataset.py:73)
+ *     n <= F:  start = 0, frames = (n / unit_frames) * unit_frames      (the whole utterance, floored to the unit)
+ * The multiply-high map x -> (r * x) >> 32 of a uniform 32-bit r onto [0, x) is onto, monotone in r (r = 0 -> 0, r = 2^32 - 1
+ * -> x - 1) and gives every value either floor(2^32 / x) or that plus one of the 2^32 words: a value's probability differs from
+ * 1 / x by less than 2^-32, i.e. by a relative x / 2^32 at most (3e-6 for 13 100 utterances).  A slot's pick depends on (seed,
+ * stream_id, d, b) only - not on B: the first slots of a larger batch are the smaller batch.
+ *
+ * Outputs, every element written by every call: x [B][F * hop] = the audio from sample hop * (frame_off[u] + start), c [B][F]
+ * [num_mels] = the mel rows from frame_off[u] + start, both +0.0f past the clip's frames; len [B] int32 = frames * hop;
+ * picks (may be NULL) [B][2] int32 = (u, start).  After the gather a one-lane kernel stores d + 1 to *counter_dev: the counter
+ * moves on the device, in stream order, without atomics, and no lane of the draw can see the new value.  Nothing is allocated or
+ * synchronised; two kernel launches on `stream`, capturable into a hipGraph whose every replay draws the next batch.
+ * 16-byte loads and stores for a row whose source, destination and lengths are 16-byte multiples (hop or num_mels a
+ * multiple of 4 with aligned bases), dwords otherwise.  Refusals (FWN_ERR_ARG, before any launch): a null audio, mel,
+ * frame_off, counter_dev, x, c or len; B, F, n_utt, hop, num_mels or unit_frames < 1; B >= 65536; n_utt >= 2^31; F * hop or
+ * F * num_mels >= 2^31; pointers off their element's alignment (4 bytes; 8 for frame_off and counter_dev). */
+int fwn_corpus_draw(const float* audio, const float* mel, const int64_t* frame_off, int64_t n_utt, int hop, int num_mels,
+                    int unit_frames, int64_t B, int64_t F, uint64_t seed, uint32_t stream_id, uint64_t* counter_dev, float* x,
+                    float* c, int32_t* len, int32_t* picks, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -255,6 +255,7 @@ SIGNATURES = {
     "fwn_pcm16": (C.c_int, [vp, vp, i64, i64, vp, vp]),
     "fwn_synthesize_workspace_bytes": (C.c_size_t, [C.POINTER(ModelDesc), i64, i64, C.c_int]),
     "fwn_model_synthesize": (C.c_int, [C.POINTER(ModelDesc), i64, i64, vp, C.c_uint64, vp, C.c_float, vp, vp, C.c_size_t, vp, vp, vp, vp]),
+    "fwn_corpus_draw": (C.c_int, [vp, vp, vp, i64, C.c_int, C.c_int, C.c_int, i64, i64, C.c_uint64, C.c_uint32, vp, vp, vp, vp, vp, vp]),
 }
 
 _lib = None

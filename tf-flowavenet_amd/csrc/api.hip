@@ -1424,4 +1424,25 @@ int fwn_model_synthesize(const fwn_model_desc* m, int64_t B, int64_t T, const fl
     return check_launch("fwn_model_synthesize");
 }
 
+// ---- device-resident corpus: one training batch drawn and gathered on the device (include/fwn.h) ----
+int fwn_corpus_draw(const float* audio, const float* mel, const int64_t* frame_off, int64_t n_utt, int hop, int num_mels,
+                    int unit_frames, int64_t B, int64_t F, uint64_t seed, uint32_t stream_id, uint64_t* counter_dev, float* x, float* c,
+                    int32_t* len, int32_t* picks, void* stream) {
+    REQUIRE(audio && mel && frame_off && counter_dev && x && c && len, "fwn_corpus_draw: null pointer");
+    REQUIRE(B >= 1 && F >= 1 && n_utt >= 1 && hop >= 1 && num_mels >= 1 && unit_frames >= 1,
+            "fwn_corpus_draw: B, F, n_utt, hop, num_mels and unit_frames must be positive (B %lld, F %lld, n_utt %lld, hop %d, num_mels %d, "
+            "unit_frames %d)", (long long)B, (long long)F, (long long)n_utt, hop, num_mels, unit_frames);
+    REQUIRE(B < 65536, "fwn_corpus_draw: B=%lld slots (at most 65535 per call)", (long long)B);
+    REQUIRE(n_utt < ((int64_t)1 << 31), "fwn_corpus_draw: n_utt=%lld utterances (fewer than 2^31)", (long long)n_utt);
+    REQUIRE(F * hop < ((int64_t)1 << 31) && F * num_mels < ((int64_t)1 << 31),
+            "fwn_corpus_draw: a row of F=%lld frames exceeds 2^31 elements", (long long)F);
+    REQUIRE(((((uintptr_t)audio) | ((uintptr_t)mel) | ((uintptr_t)x) | ((uintptr_t)c) | ((uintptr_t)len) | ((uintptr_t)picks)) & 3) == 0,
+            "fwn_corpus_draw: audio, mel, x, c, len and picks must be 4-byte aligned");
+    REQUIRE(((((uintptr_t)frame_off) | ((uintptr_t)counter_dev)) & 7) == 0, "fwn_corpus_draw: frame_off and counter_dev must be 8-byte aligned");
+    fwn_launch_corpus_draw(audio, mel, (const long long*)frame_off, (long)n_utt, hop, num_mels, unit_frames, (long)B, (long)F,
+                           (unsigned long long)seed, (unsigned)stream_id, (unsigned long long*)counter_dev, x, c, len, picks,
+                           (hipStream_t)stream);
+    return check_launch("fwn_corpus_draw");
+}
+
 }  // extern "C"

@@ -552,6 +552,61 @@ __global__ __launch_bounds__(256) void latent_normal_kernel(float* __restrict__ 
     }
 }
 
+// ---- training: a batch drawn from the device-resident corpus ---------------------------------------------------
+// include/fwn.h fwn_corpus_draw has the layout and the stream's definition (tests/corpus_ref.py restates it).  blockIdx.y =
+// slot b.  Every workgroup of a slot derives the slot's pick itself - one Philox call and two table reads, uniform over the
+// workgroup - from the counter as it stands: nothing in this launch writes it (corpus_advance_kernel does, behind it in
+// stream order).  The workgroups of a slot then stride over the row of x and the row of c: [0, keep) copied from the corpus,
+// [keep, total) +0.  A row goes in 16-byte pieces where source, destination, keep and total are all 16-byte multiples - so a
+// piece is either wholly inside the clip or wholly past it - and in dwords otherwise.  The first workgroup of a slot writes
+// len and picks.  The table is the caller's: a negative frame count is read as 0, and no start leaves [0, n - F).
+__device__ __forceinline__ void corpus_copy_row(const float* src, float* dst, long keep, long total, long first, long stride) {
+    if ((((uintptr_t)src | (uintptr_t)dst) & 15) == 0 && ((keep | total) & 3) == 0) {
+        for (long q = first; q < (total >> 2); q += stride) {
+            const long i = q * 4;
+            *(float4*)(dst + i) = i < keep ? *(const float4*)(src + i) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        }
+    } else {
+        for (long i = first; i < total; i += stride) dst[i] = i < keep ? src[i] : 0.0f;
+    }
+}
+__global__ __launch_bounds__(256) void corpus_draw_kernel(const float* __restrict__ audio, const float* __restrict__ mel,
+                                                          const long long* __restrict__ frame_off, unsigned long long n_utt, int hop,
+                                                          int num_mels, int unit_frames, long F, unsigned k0, unsigned k1,
+                                                          unsigned stream_id, const unsigned long long* counter,
+                                                          float* __restrict__ x, float* __restrict__ c, int* __restrict__ len,
+                                                          int* __restrict__ picks) {
+    const unsigned b = blockIdx.y;
+    const unsigned long long d = *counter;
+    const uint4 r = philox4x32_10(make_uint4((unsigned)(d & 0xffffffffull), (unsigned)(d >> 32), b, stream_id), k0, k1);
+    const long long u = (long long)(((unsigned long long)r.x * n_utt) >> 32);            // n_utt < 2^32: no overflow
+    const long long f0 = frame_off[u];
+    long long n = frame_off[u + 1] - f0;
+    if (n < 0) n = 0;
+    long long start = 0, frames;
+    if (n > F) {
+        start = (long long)__umul64hi((unsigned long long)r.y << 32, (unsigned long long)(n - F));      // (r1 (n - F)) >> 32
+        frames = F;
+    } else {
+        frames = n / unit_frames * unit_frames;
+    }
+    const long long row0 = f0 + start;
+    const long first = (long)blockIdx.x * 256 + threadIdx.x, stride = (long)gridDim.x * 256;
+    corpus_copy_row(audio + row0 * hop, x + (long long)b * F * hop, (long)(frames * hop), F * hop, first, stride);
+    corpus_copy_row(mel + row0 * num_mels, c + (long long)b * F * num_mels, (long)(frames * num_mels), F * num_mels, first, stride);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        len[b] = (int)(frames * hop);
+        if (picks) {
+            picks[2 * b] = (int)u;
+            picks[2 * b + 1] = (int)start;
+        }
+    }
+}
+// one lane, behind the gather in stream order: the draw counter moves on (a plain load and a plain vector store)
+__global__ void corpus_advance_kernel(unsigned long long* counter) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) *counter = *counter + 1ull;
+}
+
 // ---- synthesis: fp32 waveform -> 16-bit PCM ------------------------------------------------------------------
 // x [B][T] fp32 -> pcm [B][T] int16 = rint((double)clamp(x, -1, 1) * 32767.0), NaN -> 0: synthesize.write_wav's float64 NumPy
 // arithmetic bit for bit (the fp64 product of an fp32 value and 32767 is exact, so the one rounding is rint's half-to-even;
@@ -1085,6 +1140,18 @@ void fwn_launch_pcm16(const float* x, short* pcm, long B, long T, const int* len
     const long want = (T * 2 + 16383) / 16384, cap = B < 2048 ? 2048 / B : 1;              // four 16-byte stores per thread
     const long gx = want < 1 ? 1 : (want > cap ? cap : want);
     hipLaunchKernelGGL(pcm16_kernel, dim3((unsigned)gx, (unsigned)B), dim3(256), 0, st, x, pcm, T, len);
+}
+void fwn_launch_corpus_draw(const float* audio, const float* mel, const long long* frame_off, long n_utt, int hop, int num_mels,
+                            int unit_frames, long B, long F, unsigned long long seed, unsigned stream_id, unsigned long long* counter,
+                            float* x, float* c, int* len, int* picks, hipStream_t st) {
+    // the longer of the two rows at four 16-byte stores per thread, at most ~2048 workgroups over all slots (fwn_launch_mask_rows)
+    const long widest = F * (hop > num_mels ? hop : num_mels);
+    const long want = (widest * 4 + 16383) / 16384, cap = B < 2048 ? 2048 / B : 1;
+    const long gx = want < 1 ? 1 : (want > cap ? cap : want);
+    hipLaunchKernelGGL(corpus_draw_kernel, dim3((unsigned)gx, (unsigned)B), dim3(256), 0, st, audio, mel, frame_off,
+                       (unsigned long long)n_utt, hop, num_mels, unit_frames, F, (unsigned)(seed & 0xffffffffull), (unsigned)(seed >> 32),
+                       stream_id, counter, x, c, len, picks);
+    hipLaunchKernelGGL(corpus_advance_kernel, dim3(1), dim3(64), 0, st, counter);
 }
 void fwn_launch_fill_neg_shift(float* plane, long nclip, long rows, int Ch, const float* shift, const int* len, int nlen,
                                int samples_per_row, hipStream_t st) {

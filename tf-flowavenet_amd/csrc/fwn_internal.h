@@ -163,6 +163,11 @@ void fwn_launch_mask_rows(void* base, long nclip, long rows, long row_bytes, con
 void fwn_launch_latent_normal(float* z, long B, long T, unsigned long long seed, const unsigned* clip_id, float temp, const int* len,
                               hipStream_t st);
 void fwn_launch_pcm16(const float* x, short* pcm, long B, long T, const int* len, hipStream_t st);
+// training data (aux_kernels.hip): slot b of x [B][F hop] / c [B][F][num_mels] / len [B] / picks [B][2] drawn from the flat corpus
+// by Philox keyed on (seed, stream_id, *counter, b), then *counter + 1 from one lane of a second launch (fwn.h fwn_corpus_draw)
+void fwn_launch_corpus_draw(const float* audio, const float* mel, const long long* frame_off, long n_utt, int hop, int num_mels,
+                            int unit_frames, long B, long F, unsigned long long seed, unsigned stream_id, unsigned long long* counter,
+                            float* x, float* c, int* len, int* picks, hipStream_t st);
 // ragged forward (aux_kernels.hip).  -shift[tau] into rows [len / samples_per_row, rows) of every clip of a [nclip][rows][Ch]
 // fp32 plane: the front conv's on-the-fly ActNorm then gives exact zeros there.  Clamped like fwn_launch_mask_rows.
 void fwn_launch_fill_neg_shift(float* plane, long nclip, long rows, int Ch, const float* shift, const int* len, int nlen,

@@ -25,6 +25,14 @@ data-dependent init batch is drawn from full-length crops (``Dataset.next_full``
 than ``max_time_steps``; where it has none - prompts, commands, digits - the init takes a ragged batch drawn like a training
 batch (``Dataset.next_init``, ``Trainer.ddi(x, c, lengths=)``: ActNorm statistics over the clips' own samples), and the
 init-step update runs with those lengths.  ``--ragged_init`` takes the ragged init batch on any corpus.
+
+``--device_corpus``: the eligible training utterances are uploaded once (``corpus.DeviceCorpus``: audio and mels back to back and
+a table of frame offsets) and every training batch is drawn and gathered there by ``fwn_corpus_draw`` on the training stream -
+the same eligibility, crop range and short-utterance rule as ``Dataset``, but a Philox stream of this project's own keyed by
+(seed, rank, draw counter), so the batches are not those of a run without the flag.  The counter lives on the device, moves by
+one per draw, and goes into every checkpoint as ``__data/draw_counter``: a restored run continues the data stream where it
+stopped (the host ``Dataset`` of a run without the flag starts its draws over).  The init batch, the held-out loss and the
+evaluation sample stay with the host ``Dataset``.  Every rank of a data-parallel run holds the whole corpus.
 """
 from __future__ import annotations
 
@@ -191,9 +199,13 @@ class Dataset:
         return np.array(mel[:frames]), np.array(audio[:frames * hp.hop_size])   # copies, not views of the map
 
 
-def save_checkpoint(path, trainer):
+def save_checkpoint(path, trainer, corpus=None):
+    """corpus: a ``corpus.DeviceCorpus`` - its draw counter goes in as ``__data/draw_counter`` (uint64), so that a restored run
+    continues the data stream where this one stopped."""
     views = trainer.opt.master_views()
     out = {k: v.detach().cpu().numpy() for k, v in views.items()}
+    if corpus is not None:
+        out[DRAW_COUNTER_KEY] = np.asarray(corpus.counter, dtype=np.uint64)
     out["__opt/m"] = trainer.opt.m.cpu().numpy()
     out["__opt/v"] = trainer.opt.v.cpu().numpy()
     out["__opt/global_step"] = np.asarray(trainer.opt.global_step, dtype=np.int64)
@@ -203,6 +215,9 @@ def save_checkpoint(path, trainer):
         f.flush()
         os.fsync(f.fileno())
     os.replace(tmp, path)
+
+
+DRAW_COUNTER_KEY = "__data/draw_counter"      # optional: written and read with --device_corpus only
 
 
 def checkpoint_files(save_dir):
@@ -221,9 +236,10 @@ def _checkpoint_step(path):
     return int(re.search(r"ckpt-(\d+)\.npz$", path).group(1))
 
 
-def restore_checkpoint(save_dir, trainer):
+def restore_checkpoint(save_dir, trainer, corpus=None):
     """Highest-step readable ``flowavenet_model.ckpt-<step>.npz`` -> masters, Adam slots, global step.  Returns the
-    step or None.
+    step or None.  corpus: a ``corpus.DeviceCorpus`` - its draw counter is set from ``__data/draw_counter`` where the file has
+    one (a checkpoint written without ``--device_corpus`` has none: the counter stays); without a corpus the entry is ignored.
 
     Only a file that cannot be READ (truncated by a crash: zip / EOF / OS errors) is skipped, with a message.  A file
     that reads but does not fit this model - a missing parameter, another shape: different hparams - raises: silently
@@ -264,7 +280,7 @@ def restore_checkpoint(save_dir, trainer):
         m, v_, gs = torch.from_numpy(arrays["__opt/m"]), torch.from_numpy(arrays["__opt/v"]), int(arrays["__opt/global_step"])
         if m.numel() != trainer.opt.m.numel() or v_.numel() != trainer.opt.v.numel():
             raise ValueError("checkpoint {}: Adam slots of {} elements, the model has {}".format(path, m.numel(), trainer.opt.m.numel()))
-        got = (path, loaded, m, v_, gs)
+        got = (path, loaded, m, v_, gs, int(arrays[DRAW_COUNTER_KEY]) if DRAW_COUNTER_KEY in names else None)
         break
     if multi:
         mine = torch.tensor([got[4] if got else -1], dtype=torch.int64, device=trainer.opt.m.device)
@@ -275,9 +291,11 @@ def restore_checkpoint(save_dir, trainer):
             raise RuntimeError("ranks disagree on the checkpoint to restore (steps {} .. {}; this rank: {}): every rank "
                                "must read the same file of {}".format(int(lo), int(hi), int(mine), save_dir))
     if got is not None:
-        path, loaded, m, v_, gs = got
+        path, loaded, m, v_, gs, draws = got
         views = trainer.opt.master_views()
         print("Loading checkpoint {}".format(path))
+        if corpus is not None and draws is not None:
+            corpus.set_counter(draws)
         for k, v in views.items():
             v.copy_(loaded[k])
         trainer.opt.m.copy_(m)
@@ -316,9 +334,15 @@ def train(log_dir, args, hparams, input_path, device="cuda", params=None):
     if params is None:     # the reference's initialisers: he-uniform convs, g = 1, ZeroConv1d all zeros (modules.py:21-22,47-49)
         params = weights.synthetic_params(hparams, hparams.tf_random_seed if seed is None else seed, zero_conv="zeros")
     trainer = Trainer(hparams, params, device=device)
+    # --device_corpus: the training split goes to the device once and every training batch is drawn there (corpus.py); the
+    # init batch, the held-out loss and the evaluation sample stay with the host Dataset
+    corpus = None
+    if bool(getattr(args, "device_corpus", False)):
+        from .corpus import DeviceCorpus
+        corpus = DeviceCorpus(dataset, hparams, seed=seed, rank=rank, device=device)
     step = None
     if args.restore:
-        step = restore_checkpoint(save_dir, trainer)
+        step = restore_checkpoint(save_dir, trainer, corpus)
     if step is None:
         if rank == 0:
             print("Starting new training!" if not args.restore else "No checkpoint found.")
@@ -348,9 +372,17 @@ def train(log_dir, args, hparams, input_path, device="cuda", params=None):
     while step < args.train_steps:
         start_time = time.time()
         clip_lengths = []
+        # (device corpus: the lengths are on the device; they are kept - a clone per micro-batch, no read - only for an update
+        # that writes a summary)
+        keep_lengths = ragged and rank == 0 and (step + 1) % args.summary_interval == 0
         for micro in range(accum_steps):
             run = trainer.step if micro == accum_steps - 1 else trainer.accumulate
-            if ragged:
+            if corpus is not None:
+                audios, mels, lens = corpus.draw(hparams.batch_size)
+                out = run(audios, mels, lengths=lens)
+                if keep_lengths:
+                    clip_lengths.append(lens.tensor.clone())
+            elif ragged:
                 mels, audios, lens = dataset.next_train()
                 out = run(audios, mels, lengths=lens)
                 clip_lengths.extend(lens)
@@ -370,6 +402,8 @@ def train(log_dir, args, hparams, input_path, device="cuda", params=None):
                    "losses/logdet": float(logdet), "learning_rate": learning_rate(step - 1),
                    "gradient_global_norm": float(gnorm), "accum_steps": accum_steps}
             if ragged:
+                if corpus is not None:
+                    clip_lengths = torch.cat(clip_lengths).cpu().numpy()
                 rec["mean_clip_length"] = float(np.mean(clip_lengths))
             log(train_logdir, rec)
             model = FloWaveNet(hparams, device=device, cond_mode=1).load_params(trainer.opt.master_views())
@@ -386,7 +420,7 @@ def train(log_dir, args, hparams, input_path, device="cuda", params=None):
                 rec["mean_clip_length"] = float(np.mean(tl))
             log(test_logdir, rec)
         if rank == 0 and (step % args.checkpoint_interval == 0 or step == args.train_steps):
-            save_checkpoint("%s-%d.npz" % (checkpoint_path, step), trainer)
+            save_checkpoint("%s-%d.npz" % (checkpoint_path, step), trainer, corpus)
         if rank == 0 and step % args.eval_interval == 0:
             print("\nEvaluating at step {}".format(step))                     # predict_random_samples, train.py:114-139
             mel, wav = dataset.eval_sample()
@@ -428,6 +462,11 @@ def main(argv=None):
     parser.add_argument("--accum_steps", type=positive, default=1,
                         help="micro-batches per optimiser update: the gradients of K batches are summed and averaged into one "
                              "clip / Adam update (effective batch K x batch_size x ranks); steps and every interval count updates")
+    parser.add_argument("--device_corpus", action="store_true",
+                        help="upload the training utterances to the GPU once and draw every training batch there (a Philox stream "
+                             "keyed by seed, rank and a draw counter on the device: not the host draws of a run without the flag); "
+                             "checkpoints then carry the counter and a restored run continues the data stream; every rank holds the "
+                             "whole corpus; combines with --ragged and --accum_steps")
     args = parser.parse_args(argv)
     import torch
     import torch.distributed as dist

@@ -622,6 +622,8 @@ class Trainer:
         views = self.opt.master_views()
         m = FloWaveNet(self.hp, init=True, device=self.device, cond_mode=1, group=self.opt.group).load_params(views)
         xx = torch.as_tensor(x).to(self.device)
+        if isinstance(lengths, DeviceLengths):      # the init runs once and validates on the host: read them back
+            lengths = lengths.tensor.cpu().tolist()
         if lengths is not None:
             m.forward_init(xx.reshape(xx.shape[0], -1, 1), torch.as_tensor(c).to(self.device), lengths)
         else:
@@ -640,7 +642,9 @@ class Trainer:
         lengths: a ragged batch (``GradEngine.loss_and_grads``): loss, log_p and logdet are then the means over the clips of
         the per-clip values, which ``per_clip`` holds afterwards as ``(log_p [B], logdet [B])`` (None after a plain step).
         The recorded step keeps the lengths in a static device buffer beside x and c - one recording per shape serves every
-        batch, whatever its lengths.
+        batch, whatever its lengths.  ``lengths=DeviceLengths(t)``: an int32 device tensor [B] of lengths that are legal by
+        construction (``corpus.DeviceCorpus.draw``) - nothing is validated or read on the host, the recorded step copies them
+        device to device; ``accumulate`` and ``ddi`` take them too (``ddi`` reads them back: it runs once).
         With ``pending`` = n micro-batches accumulated (``accumulate``): this batch is the last of the update.  Its gradient
         takes the pending sum in, block range by block range as the ranges become final - ``opt.g`` = ((g_0 + g_1) + ...) + g_n
         in call order -, then exchange, norm and clip / Adam run as ever with the loss scale n + 1.  loss, log_p and logdet
@@ -689,11 +693,15 @@ class Trainer:
 
     def _admit(self, x, lengths):
         """What is checked on the host before anything is launched: the lengths of a ragged batch (-> list of ints) and, with
-        micro-batches pending, that this one holds as many clips as they did."""
+        micro-batches pending, that this one holds as many clips as they did.  ``DeviceLengths`` pass as they are: whoever
+        built them (``corpus.DeviceCorpus.draw``) made them legal, and reading them here would cost a synchronisation."""
         import torch
         xs = torch.as_tensor(x)
         b = int(xs.shape[0]) if xs.dim() else 0
-        if lengths is not None:
+        if isinstance(lengths, DeviceLengths):
+            if getattr(self.hp, "gate_fp8", False):
+                raise ValueError("gate_fp8 hparams take no lengths: the e4m3 copies of h are not masked")
+        elif lengths is not None:
             lengths = self.engine.check_lengths(lengths, b, int(xs.numel() // max(1, b)))
         if self.pending and b != self._pending_b:
             raise ValueError("gradient accumulation: this micro-batch holds %d clips, the %d pending ones hold %d each (the mean "
@@ -740,7 +748,8 @@ class Trainer:
                 raise RuntimeError("Trainer: the recorded step needs a GradEngine with side_stream=True")
             xs = torch.empty(tuple(x.shape), dtype=torch.float32, device=dev)
             cs = torch.empty(tuple(c.shape), dtype=torch.float32, device=dev)
-            ls = torch.empty(len(lengths), dtype=torch.int32, device=dev) if lengths is not None else None
+            nlen = lengths.tensor.numel() if isinstance(lengths, DeviceLengths) else len(lengths) if lengths is not None else 0
+            ls = torch.empty(nlen, dtype=torch.int32, device=dev) if lengths is not None else None
             params, gv = self.opt.master_views(), self.opt.grad_views()
             segs, pool = [], torch.cuda.graph_pool_handle()
             side = torch.cuda.Stream(dev)
@@ -796,7 +805,9 @@ class Trainer:
             rec = table[key] = dict(xs=xs, cs=cs, ls=ls, segs=segs, out=(loss, log_p, logdet, gnorm), per_clip=per_clip)
         rec["xs"].copy_(x.reshape(rec["xs"].shape), non_blocking=True)
         rec["cs"].copy_(c, non_blocking=True)
-        if rec["ls"] is not None:
+        if isinstance(lengths, DeviceLengths):      # already on the device: a copy in stream order, nothing read on the host
+            rec["ls"].copy_(lengths.tensor, non_blocking=True)
+        elif rec["ls"] is not None:
             rec["ls"].copy_(torch.tensor(lengths, dtype=torch.int32), non_blocking=False)
         self.per_clip = rec["per_clip"]
         if micro is None:
