@@ -740,6 +740,48 @@ int fwn_model_synthesize(const fwn_model_desc* m, int64_t B, int64_t T, const fl
                          const uint32_t* clip_id_dev, float temp, const int32_t* len_dev, void* workspace, size_t workspace_bytes,
                          int16_t* pcm_out, float* wav_out, float* z_out, void* stream);
 
+/* ---- windowed synthesis (additive; FWN_VERSION unchanged): a clip of any length, or one whose mel is still arriving, as
+ * windows with real context on both sides, each a plain rectangular fwn_model_reverse; only the cores are kept.  The planning
+ * (which windows, how much context: tf_flowavenet_amd/windowing.py) is the host's; this is the device code around the pass.
+ * Every table below is a DEVICE array read by the kernels; nothing is allocated or synchronised, so a call is capturable.
+ *
+ * fwn_latent_normal_at: fwn_latent_normal with a per-row start.  Row r of z [n][L] holds samples start[r] .. start[r] + L of
+ * clip clip_id[r]'s stream (clip_id_dev NULL: clip r), bit for bit the slice of what fwn_latent_normal writes for that clip:
+ * sample i = start + j from counter (i / 4, 0, clip_id, 0), lane i % 4, the same fp32 evaluation.  start_dev: DEVICE int64 [n],
+ * any value >= 0 (a negative one is read as 0), not only multiples of 4; start + L <= 2^34 is the caller's to keep.  len_dev
+ * (may be NULL) as in fwn_latent_normal, relative to the row: samples at j >= len[r] are +0.0f.  n < 65536; z 4-byte aligned.
+ *
+ * fwn_window_gather: row r of dst [n][rows][row_floats] fp32 = the rows * row_floats floats of src from row src_row_dev[r]
+ * (DEVICE int64 [n]; 64-bit addressing: src is a flat buffer of rows of row_floats floats - for the mel, row_floats = num_mels
+ * and the offset is the clip's first frame plus lo / hop).  16-byte accesses for a row of dst whose source and destination are
+ * both 16-byte aligned (and whose size is a multiple of 16 bytes), dwords otherwise.  One launch.  rows * row_floats < 2^31.
+ *
+ * fwn_window_scatter_pcm16: for row r of x [n][L] fp32, pcm[out_off[r] + i] = pcm16(x[r][core_off[r] + i]) for i < core_len[r]
+ * - fwn_pcm16's arithmetic bit for bit - and, if wav != NULL, wav[out_off[r] + i] = x[r][core_off[r] + i].  pcm or wav may be
+ * NULL, not both.  core_off_dev / core_len_dev: DEVICE int32 [n], clamped into the row on the device; out_off_dev: DEVICE int64
+ * [n], element offsets into the flat int16 / fp32 buffers (the caller's to keep inside them).  Nothing outside the cores is
+ * written.  One launch.
+ *
+ * fwn_model_synthesize_windows: one group of n windows of L samples on one stream - fwn_latent_normal_at (start_dev, clip_id_dev;
+ * no len) -> fwn_window_gather (mel_flat, mel_row_dev, rows L / hop of num_mels floats) -> fwn_model_reverse(m, n, L) ->
+ * fwn_window_scatter_pcm16 (pcm_flat; wav_flat may be NULL).  z, the waveform and the gathered mel live in the workspace behind
+ * the inverse pass's own: fwn_synthesize_windows_workspace_bytes(m, n, L) - a function of (n, L) alone, never of a clip's
+ * length; 0 for a descriptor or shape the call would refuse.  Refusals (FWN_ERR_ARG, before anything is launched): those of
+ * fwn_model_synthesize without lengths (the inverse pass's own, odd n_block * n_flow, n >= 32768), a null mel_flat, workspace,
+ * pcm_flat or table, a table off its element's alignment (8 bytes for the int64 ones, 4 for the others), a workspace off 256
+ * bytes.  Speed: tools/bench_windowed.py. */
+int fwn_latent_normal_at(float* z, int64_t n, int64_t L, uint64_t seed, const uint32_t* clip_id_dev, const int64_t* start_dev,
+                         float temp, const int32_t* len_dev, void* stream);
+int fwn_window_gather(const float* src, const int64_t* src_row_dev, float* dst, int64_t n, int64_t rows, int64_t row_floats,
+                      void* stream);
+int fwn_window_scatter_pcm16(const float* x, int64_t n, int64_t L, const int32_t* core_off_dev, const int32_t* core_len_dev,
+                             const int64_t* out_off_dev, int16_t* pcm, float* wav, void* stream);
+size_t fwn_synthesize_windows_workspace_bytes(const fwn_model_desc* m, int64_t n, int64_t L);
+int fwn_model_synthesize_windows(const fwn_model_desc* m, int64_t n, int64_t L, const float* mel_flat, const int64_t* mel_row_dev,
+                                 const uint32_t* clip_id_dev, const int64_t* start_dev, const int32_t* core_off_dev,
+                                 const int32_t* core_len_dev, const int64_t* out_off_dev, uint64_t seed, float temp, void* workspace,
+                                 size_t workspace_bytes, int16_t* pcm_flat, float* wav_flat, void* stream);
+
 /* ---- device-resident corpus (additive; FWN_VERSION unchanged): a training batch drawn and gathered on the device.
  *
  * Layout.  audio: flat fp32, all utterances back to back; mel: flat fp32 [total_frames][num_mels]; frame_off: DEVICE int64

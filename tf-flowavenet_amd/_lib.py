@@ -255,6 +255,12 @@ SIGNATURES = {
     "fwn_pcm16": (C.c_int, [vp, vp, i64, i64, vp, vp]),
     "fwn_synthesize_workspace_bytes": (C.c_size_t, [C.POINTER(ModelDesc), i64, i64, C.c_int]),
     "fwn_model_synthesize": (C.c_int, [C.POINTER(ModelDesc), i64, i64, vp, C.c_uint64, vp, C.c_float, vp, vp, C.c_size_t, vp, vp, vp, vp]),
+    "fwn_latent_normal_at": (C.c_int, [vp, i64, i64, C.c_uint64, vp, vp, C.c_float, vp, vp]),
+    "fwn_window_gather": (C.c_int, [vp, vp, vp, i64, i64, i64, vp]),
+    "fwn_window_scatter_pcm16": (C.c_int, [vp, i64, i64, vp, vp, vp, vp, vp, vp]),
+    "fwn_synthesize_windows_workspace_bytes": (C.c_size_t, [C.POINTER(ModelDesc), i64, i64]),
+    "fwn_model_synthesize_windows": (C.c_int, [C.POINTER(ModelDesc), i64, i64, vp, vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_float, vp,
+                                               C.c_size_t, vp, vp, vp]),
     "fwn_corpus_draw": (C.c_int, [vp, vp, vp, i64, C.c_int, C.c_int, C.c_int, i64, i64, C.c_uint64, C.c_uint32, vp, vp, vp, vp, vp, vp]),
 }
 

@@ -1424,6 +1424,85 @@ int fwn_model_synthesize(const fwn_model_desc* m, int64_t B, int64_t T, const fl
     return check_launch("fwn_model_synthesize");
 }
 
+// ---- windowed synthesis: one group of n windows of L samples - latent slices, mel rows, the inverse pass, the cores (include/fwn.h) ----
+#define ALIGNED8(p) ((((uintptr_t)(p)) & 7) == 0)
+#define ALIGNED4(p) ((((uintptr_t)(p)) & 3) == 0)
+int fwn_latent_normal_at(float* z, int64_t n, int64_t L, uint64_t seed, const uint32_t* clip_id_dev, const int64_t* start_dev, float temp,
+                         const int32_t* len_dev, void* stream) {
+    REQUIRE(z && start_dev && n > 0 && n < 65536 && L > 0, "fwn_latent_normal_at: bad argument");
+    REQUIRE(ALIGNED4(z) && ALIGNED4(clip_id_dev) && ALIGNED4(len_dev), "fwn_latent_normal_at: z, clip_id_dev and len_dev must be 4-byte aligned");
+    REQUIRE(ALIGNED8(start_dev), "fwn_latent_normal_at: start_dev must be 8-byte aligned");
+    REQUIRE(L <= ((int64_t)1 << 34), "fwn_latent_normal_at: L=%lld exceeds the 2^32 quads one clip's counter word numbers", (long long)L);
+    fwn_launch_latent_normal_at(z, (long)n, (long)L, (unsigned long long)seed, clip_id_dev, (const long long*)start_dev, temp, len_dev,
+                                (hipStream_t)stream);
+    return check_launch("fwn_latent_normal_at");
+}
+int fwn_window_gather(const float* src, const int64_t* src_row_dev, float* dst, int64_t n, int64_t rows, int64_t row_floats, void* stream) {
+    REQUIRE(src && src_row_dev && dst, "fwn_window_gather: null pointer");
+    REQUIRE(n > 0 && n < 65536 && rows > 0 && row_floats > 0, "fwn_window_gather: n, rows and row_floats must be positive, n < 65536");
+    REQUIRE(rows < ((int64_t)1 << 31) && row_floats < ((int64_t)1 << 31) && rows * row_floats < ((int64_t)1 << 31),
+            "fwn_window_gather: a window of %lld rows of %lld floats exceeds 2^31 elements", (long long)rows, (long long)row_floats);
+    REQUIRE(ALIGNED4(src) && ALIGNED4(dst), "fwn_window_gather: src and dst must be 4-byte aligned");
+    REQUIRE(ALIGNED8(src_row_dev), "fwn_window_gather: src_row_dev must be 8-byte aligned");
+    fwn_launch_window_gather(src, (const long long*)src_row_dev, (long)row_floats, dst, (long)n, (long)(rows * row_floats), (hipStream_t)stream);
+    return check_launch("fwn_window_gather");
+}
+int fwn_window_scatter_pcm16(const float* x, int64_t n, int64_t L, const int32_t* core_off_dev, const int32_t* core_len_dev,
+                             const int64_t* out_off_dev, int16_t* pcm, float* wav, void* stream) {
+    REQUIRE(x && core_off_dev && core_len_dev && out_off_dev && (pcm || wav), "fwn_window_scatter_pcm16: null pointer");
+    REQUIRE(n > 0 && n < 65536 && L > 0 && L < ((int64_t)1 << 31), "fwn_window_scatter_pcm16: n in [1, 65535] and L in [1, 2^31)");
+    REQUIRE(ALIGNED4(x) && ALIGNED4(wav) && (((uintptr_t)pcm) & 1) == 0 && ALIGNED4(core_off_dev) && ALIGNED4(core_len_dev),
+            "fwn_window_scatter_pcm16: x, wav and the int32 tables must be 4-byte, pcm 2-byte aligned");
+    REQUIRE(ALIGNED8(out_off_dev), "fwn_window_scatter_pcm16: out_off_dev must be 8-byte aligned");
+    fwn_launch_window_scatter(x, (long)n, (long)L, core_off_dev, core_len_dev, (const long long*)out_off_dev, (short*)pcm, wav,
+                              (hipStream_t)stream);
+    return check_launch("fwn_window_scatter_pcm16");
+}
+// the inverse pass's own workspace first (so model_pass carves it as ever), then z, the waveform and the windows' mel rows:
+// all of (n, L) alone
+static size_t windows_mel_bytes(const fwn_model_desc* m, int64_t n, int64_t L) {
+    return align_up((size_t)n * (size_t)(L / hop_of(m)) * m->num_mels * 4);
+}
+size_t fwn_synthesize_windows_workspace_bytes(const fwn_model_desc* m, int64_t n, int64_t L) {
+    if (check_model(m, n, L) != FWN_OK || n >= 32768 || ((m->n_block * m->n_flow) & 1)) return 0;
+    return carve(m, n, L, PASS_REVERSE).total + 2 * synth_extra(n, L) + windows_mel_bytes(m, n, L);
+}
+int fwn_model_synthesize_windows(const fwn_model_desc* m, int64_t n, int64_t L, const float* mel_flat, const int64_t* mel_row_dev,
+                                 const uint32_t* clip_id_dev, const int64_t* start_dev, const int32_t* core_off_dev,
+                                 const int32_t* core_len_dev, const int64_t* out_off_dev, uint64_t seed, float temp, void* workspace,
+                                 size_t workspace_bytes, int16_t* pcm_flat, float* wav_flat, void* stream) {
+    // everything the inverse pass would refuse is refused here, before the latent fill is enqueued
+    int rc = check_model(m, n, L);
+    if (rc) return rc;
+    REQUIRE(mel_flat && workspace && pcm_flat, "fwn_model_synthesize_windows: null pointer");
+    REQUIRE(mel_row_dev && clip_id_dev && start_dev && core_off_dev && core_len_dev && out_off_dev, "fwn_model_synthesize_windows: null table");
+    REQUIRE(ALIGNED8(mel_row_dev) && ALIGNED8(start_dev) && ALIGNED8(out_off_dev),
+            "fwn_model_synthesize_windows: the int64 tables (mel_row_dev, start_dev, out_off_dev) must be 8-byte aligned");
+    REQUIRE(ALIGNED4(clip_id_dev) && ALIGNED4(core_off_dev) && ALIGNED4(core_len_dev),
+            "fwn_model_synthesize_windows: the 32-bit tables (clip_id_dev, core_off_dev, core_len_dev) must be 4-byte aligned");
+    REQUIRE((((uintptr_t)workspace) & 255) == 0, "fwn_model_synthesize_windows: workspace must be 256-byte aligned");
+    REQUIRE(ALIGNED4(mel_flat) && ALIGNED4(wav_flat) && (((uintptr_t)pcm_flat) & 1) == 0,
+            "fwn_model_synthesize_windows: mel_flat and wav_flat must be 4-byte, pcm_flat 2-byte aligned");
+    REQUIRE(n < 32768, "fwn_model_synthesize_windows: n=%lld windows (at most 32767 per call)", (long long)n);
+    REQUIRE(((m->n_block * m->n_flow) & 1) == 0,
+            "fwn_model_synthesize_windows: reverse with odd n_block*n_flow ends in swapped channel order (model.py:199,254); unsupported");
+    const size_t base = carve(m, n, L, PASS_REVERSE).total, extra = synth_extra(n, L), need = base + 2 * extra + windows_mel_bytes(m, n, L);
+    if (workspace_bytes < need)
+        return fail(FWN_ERR_WORKSPACE, "fwn_model_synthesize_windows: workspace %zu < required %zu bytes", workspace_bytes, need);
+    float* z = (float*)((char*)workspace + base);
+    float* wav = (float*)((char*)workspace + base + extra);
+    float* mel = (float*)((char*)workspace + base + 2 * extra);
+    hipStream_t st = (hipStream_t)stream;
+    fwn_launch_latent_normal_at(z, (long)n, (long)L, (unsigned long long)seed, clip_id_dev, (const long long*)start_dev, temp, nullptr, st);
+    fwn_launch_window_gather(mel_flat, (const long long*)mel_row_dev, (long)m->num_mels, mel, (long)n, (long)(L / hop_of(m)) * m->num_mels, st);
+    rc = check_launch("fwn_model_synthesize_windows (latent, mel rows)");
+    if (rc) return rc;
+    rc = model_pass(PASS_REVERSE, m, n, L, z, mel, nullptr, workspace, base, nullptr, nullptr, nullptr, nullptr, wav, stream);
+    if (rc) return rc;
+    fwn_launch_window_scatter(wav, (long)n, (long)L, core_off_dev, core_len_dev, (const long long*)out_off_dev, (short*)pcm_flat, wav_flat, st);
+    return check_launch("fwn_model_synthesize_windows");
+}
+
 // ---- device-resident corpus: one training batch drawn and gathered on the device (include/fwn.h) ----
 int fwn_corpus_draw(const float* audio, const float* mel, const int64_t* frame_off, int64_t n_utt, int hop, int num_mels,
                     int unit_frames, int64_t B, int64_t F, uint64_t seed, uint32_t stream_id, uint64_t* counter_dev, float* x, float* c,

@@ -651,6 +651,120 @@ __global__ __launch_bounds__(256) void pcm16_kernel(const float* __restrict__ x,
     }
 }
 
+// ---- windowed synthesis: the latent of a window, the mel rows of a window, the cores of a group (include/fwn.h) ----------
+// z [n][L] fp32: row r holds samples start[r] .. start[r] + L of clip clip_id[r]'s stream - latent_normal_kernel with a
+// per-row start.  Sample i = start + j still comes from counter (i / 4, 0, clip, 0), lane i % 4, through the same
+// philox4x32_10 and box_muller, so a row is bit for bit the slice of what latent_normal_kernel writes for that clip.  The
+// lanes of a row stride over the QUADS OF THE STREAM that overlap the window (the first and the last may be partial when
+// start or start + L is no multiple of 4); a quad wholly inside the row goes as one 16-byte store where its address is
+// 16-byte aligned, as dwords otherwise.  j >= len[r] (clamped to [0, L]) is +0.  A negative start is read as 0.
+__global__ __launch_bounds__(256) void latent_normal_at_kernel(float* __restrict__ z, long L, unsigned k0, unsigned k1,
+                                                               const unsigned* __restrict__ clip_id,
+                                                               const long long* __restrict__ start, float temp,
+                                                               const int* __restrict__ len) {
+    const long r = blockIdx.y;
+    long keep = len ? (long)len[r] : L;
+    keep = keep < 0 ? 0 : (keep > L ? L : keep);
+    const unsigned clip = clip_id ? clip_id[r] : (unsigned)r;
+    long long s0 = start[r];
+    if (s0 < 0) s0 = 0;
+    float* row = z + (size_t)r * L;
+    const long long q0 = s0 >> 2, nq = ((s0 + L + 3) >> 2) - q0;
+    for (long long g = (long long)blockIdx.x * 256 + threadIdx.x; g < nq; g += (long long)gridDim.x * 256) {
+        const long long q = q0 + g;
+        const long j0 = (long)(q * 4 - s0);                      // the quad's first sample, relative to the row: -3 .. L - 1
+        float v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        if (j0 < keep) {                                          // a quad wholly past the row's length draws nothing
+            const uint4 w = philox4x32_10(make_uint4((unsigned)q, 0u, clip, 0u), k0, k1);
+            box_muller(w.x, w.y, temp, v[0], v[1]);
+            box_muller(w.z, w.w, temp, v[2], v[3]);
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (j0 + e >= keep) v[e] = 0.0f;
+        }
+        float* p = row + j0;
+        if (j0 >= 0 && j0 + 4 <= L && (((uintptr_t)p) & 15) == 0) {
+            *(float4*)p = make_float4(v[0], v[1], v[2], v[3]);
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (j0 + e >= 0 && j0 + e < L) p[e] = v[e];
+        }
+    }
+}
+
+// dst [n][count] fp32: row r = the count floats of src from float offset src_row[r] * row_floats (64-bit: the source is a flat
+// buffer of whole clips, or of many).  16-byte pieces where source and destination rows are both 16-byte aligned and count
+// is a multiple of 4, dwords otherwise (corpus_copy_row's rule).  A negative offset is read as 0.
+__global__ __launch_bounds__(256) void window_gather_kernel(const float* __restrict__ src, const long long* __restrict__ src_row,
+                                                            long row_floats, float* __restrict__ dst, long count) {
+    const long r = blockIdx.y;
+    long long s0 = src_row[r];
+    if (s0 < 0) s0 = 0;
+    const float* s = src + (size_t)s0 * (size_t)row_floats;
+    float* d = dst + (size_t)r * count;
+    const long first = (long)blockIdx.x * 256 + threadIdx.x, stride = (long)gridDim.x * 256;
+    if ((((uintptr_t)s | (uintptr_t)d) & 15) == 0 && (count & 3) == 0) {
+        for (long q = first; q < (count >> 2); q += stride) *(float4*)(d + q * 4) = *(const float4*)(s + q * 4);
+    } else {
+        for (long i = first; i < count; i += stride) d[i] = s[i];
+    }
+}
+
+// The cores of a group: for row r of x [n][L] fp32, the core_len[r] samples from core_off[r] go to pcm + out_off[r] as 16-bit
+// PCM (pcm16_of: fwn_pcm16's arithmetic) and / or to wav + out_off[r] as they are.  The core is clamped into the row here -
+// core_off to [0, L], core_len to [0, L - core_off] - so no table value reads outside x; out_off is the caller's (64-bit).
+// Nothing outside [out_off, out_off + core_len) is written.  PCM: pcm16_kernel's scheme on the core - between the first and
+// the last 16-byte boundary of the destination one lane turns eight samples into one 16-byte store where x is 16-byte
+// aligned there too, single samples on either side and everywhere where the phases disagree.  Waveform: 16-byte pieces
+// between the destination's boundaries where the source agrees, dwords otherwise.
+__global__ __launch_bounds__(256) void window_scatter_kernel(const float* __restrict__ x, long L, const int* __restrict__ core_off,
+                                                             const int* __restrict__ core_len,
+                                                             const long long* __restrict__ out_off, short* __restrict__ pcm,
+                                                             float* __restrict__ wav) {
+    const long r = blockIdx.y;
+    long off = core_off[r], n = core_len[r];
+    off = off < 0 ? 0 : (off > L ? L : off);
+    n = n < 0 ? 0 : (n > L - off ? L - off : n);
+    const float* xr = x + (size_t)r * L + off;
+    const long long o0 = out_off[r];
+    const long first = (long)blockIdx.x * 256 + threadIdx.x, stride = (long)gridDim.x * 256;
+    if (pcm) {
+        short* pr = pcm + o0;
+        long a0 = (long)(((16 - (((uintptr_t)pr) & 15)) & 15) >> 1);
+        if (a0 > n) a0 = n;
+        long a1 = a0 + ((n - a0) & ~7L);
+        if ((((uintptr_t)(xr + a0)) & 15) != 0) a1 = a0 = 0;     // phases disagree: everything goes through the side loop
+        for (long g = first; g < ((a1 - a0) >> 3); g += stride) {
+            const long i0 = a0 + g * 8;
+            union { short s[8]; uint4 u; } o;
+            const float4 lo = *(const float4*)(xr + i0), hi = *(const float4*)(xr + i0 + 4);
+            const float v[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+#pragma unroll
+            for (int e = 0; e < 8; ++e) o.s[e] = pcm16_of(v[e]);
+            *(uint4*)(pr + i0) = o.u;
+        }
+        const long nside = a0 + (n - a1);                         // head [0, a0) and tail [a1, n)
+        for (long j = first; j < nside; j += stride) {
+            const long i = j < a0 ? j : a1 + (j - a0);
+            pr[i] = pcm16_of(xr[i]);
+        }
+    }
+    if (wav) {
+        float* wr = wav + o0;
+        long a0 = (long)(((16 - (((uintptr_t)wr) & 15)) & 15) >> 2);
+        if (a0 > n) a0 = n;
+        long a1 = a0 + ((n - a0) & ~3L);
+        if ((((uintptr_t)(xr + a0)) & 15) != 0) a1 = a0 = 0;
+        for (long g = first; g < ((a1 - a0) >> 2); g += stride) *(float4*)(wr + a0 + g * 4) = *(const float4*)(xr + a0 + g * 4);
+        const long nside = a0 + (n - a1);
+        for (long j = first; j < nside; j += stride) {
+            const long i = j < a0 ? j : a1 + (j - a0);
+            wr[i] = xr[i];
+        }
+    }
+}
+
 // ---- ragged forward: the rows past each clip's end of a flow's x_a plane hold -shift --------------------
 // The front conv applies ActNorm on the fly, (v + shift[tau]) * scale[tau]: a zero in a padded row would reach its +-1 taps
 // as shift * scale, where a clip on its own is zero-padded AFTER ActNorm.  (-s + s) is exactly +0, so with -shift[tau] in
@@ -1140,6 +1254,27 @@ void fwn_launch_pcm16(const float* x, short* pcm, long B, long T, const int* len
     const long want = (T * 2 + 16383) / 16384, cap = B < 2048 ? 2048 / B : 1;              // four 16-byte stores per thread
     const long gx = want < 1 ? 1 : (want > cap ? cap : want);
     hipLaunchKernelGGL(pcm16_kernel, dim3((unsigned)gx, (unsigned)B), dim3(256), 0, st, x, pcm, T, len);
+}
+// windowed synthesis: the grids of the three launches above them (four 16-byte stores per thread, at most ~2048 workgroups)
+void fwn_launch_latent_normal_at(float* z, long n, long L, unsigned long long seed, const unsigned* clip_id, const long long* start,
+                                 float temp, const int* len, hipStream_t st) {
+    const long want = (L * 4 + 16383) / 16384, cap = n < 2048 ? 2048 / n : 1;
+    const long gx = want < 1 ? 1 : (want > cap ? cap : want);
+    hipLaunchKernelGGL(latent_normal_at_kernel, dim3((unsigned)gx, (unsigned)n), dim3(256), 0, st, z, L, (unsigned)(seed & 0xffffffffull),
+                       (unsigned)(seed >> 32), clip_id, start, temp, len);
+}
+void fwn_launch_window_gather(const float* src, const long long* src_row, long row_floats, float* dst, long n, long count,
+                              hipStream_t st) {
+    const long want = (count * 4 + 16383) / 16384, cap = n < 2048 ? 2048 / n : 1;
+    const long gx = want < 1 ? 1 : (want > cap ? cap : want);
+    hipLaunchKernelGGL(window_gather_kernel, dim3((unsigned)gx, (unsigned)n), dim3(256), 0, st, src, src_row, row_floats, dst, count);
+}
+void fwn_launch_window_scatter(const float* x, long n, long L, const int* core_off, const int* core_len, const long long* out_off,
+                               short* pcm, float* wav, hipStream_t st) {
+    const long want = (L * (wav ? 4 : 2) + 16383) / 16384, cap = n < 2048 ? 2048 / n : 1;
+    const long gx = want < 1 ? 1 : (want > cap ? cap : want);
+    hipLaunchKernelGGL(window_scatter_kernel, dim3((unsigned)gx, (unsigned)n), dim3(256), 0, st, x, L, core_off, core_len, out_off, pcm,
+                       wav);
 }
 void fwn_launch_corpus_draw(const float* audio, const float* mel, const long long* frame_off, long n_utt, int hop, int num_mels,
                             int unit_frames, long B, long F, unsigned long long seed, unsigned stream_id, unsigned long long* counter,

@@ -163,6 +163,16 @@ void fwn_launch_mask_rows(void* base, long nclip, long rows, long row_bytes, con
 void fwn_launch_latent_normal(float* z, long B, long T, unsigned long long seed, const unsigned* clip_id, float temp, const int* len,
                               hipStream_t st);
 void fwn_launch_pcm16(const float* x, short* pcm, long B, long T, const int* len, hipStream_t st);
+// windowed synthesis (aux_kernels.hip; fwn.h has the contracts): row r of z [n][L] = samples start[r] .. start[r] + L of clip
+// clip_id[r]'s latent stream; row r of dst [n][count] = count floats of src from src_row[r] * row_floats; the core
+// [core_off[r], core_off[r] + core_len[r]) of row r of x [n][L] -> pcm + out_off[r] (int16) and / or wav + out_off[r] (fp32).
+// Every table is read on the device.
+void fwn_launch_latent_normal_at(float* z, long n, long L, unsigned long long seed, const unsigned* clip_id, const long long* start,
+                                 float temp, const int* len, hipStream_t st);
+void fwn_launch_window_gather(const float* src, const long long* src_row, long row_floats, float* dst, long n, long count,
+                              hipStream_t st);
+void fwn_launch_window_scatter(const float* x, long n, long L, const int* core_off, const int* core_len, const long long* out_off,
+                               short* pcm, float* wav, hipStream_t st);
 // training data (aux_kernels.hip): slot b of x [B][F hop] / c [B][F][num_mels] / len [B] / picks [B][2] drawn from the flat corpus
 // by Philox keyed on (seed, stream_id, *counter, b), then *counter + 1 from one lane of a second launch (fwn.h fwn_corpus_draw)
 void fwn_launch_corpus_draw(const float* audio, const float* mel, const long long* frame_off, long n_utt, int hop, int num_mels,

@@ -66,7 +66,8 @@ class FloWaveNet:
         self._gate_hs_stream = bool(gate_hs_stream)
         self._packed = None
         self._ws = {}
-        self._lib = _lib.load()     # fails loudly when libfwn.so is missing
+        self._wws = {}              # windowed synthesis: workspaces of several shapes side by side (_window_workspace)
+        self._lib = _lib.load()    # fails loudly when libfwn.so is missing
         self.hop = int(np.prod(hparams.upsample_scales))
         if self.hop != hparams.hop_size:
             raise ValueError("prod(upsample_scales)=%d must equal hop_size=%d (model.py:231)"
@@ -322,13 +323,18 @@ class FloWaveNet:
         import torch
         if clip_ids is None:
             return None
+        return torch.from_numpy(np.asarray(self._clip_id_values(clip_ids, b), dtype=np.uint32).view(np.int32)).to(self._device)
+
+    @staticmethod
+    def _clip_id_values(clip_ids, b):
+        """``clip_ids`` -> list of B ints in [0, 2^32), validated on the host."""
         vals = clip_ids.detach().cpu().tolist() if hasattr(clip_ids, "detach") else np.asarray(clip_ids).tolist()
         if not isinstance(vals, list) or len(vals) != b:
             raise ValueError("clip_ids must hold one id per clip (B=%d), got %r" % (b, vals))
         for v in vals:
             if int(v) != v or not 0 <= v < (1 << 32):
                 raise ValueError("clip ids are integers in [0, 2^32), got %r" % (v,))
-        return torch.from_numpy(np.asarray([int(v) for v in vals], dtype=np.uint32).view(np.int32)).to(self._device)
+        return [int(v) for v in vals]
 
     def sample_z(self, b, t, seed, clip_ids=None, lengths=None, temp=None):
         """The latent of ``b`` clips of ``t`` samples, drawn on the device: fp32 [b, t, 1] = temp * N(0,1) (``temp``: default
@@ -399,6 +405,127 @@ class FloWaveNet:
         off = (-ws.data_ptr()) % 256
         return ws.data_ptr() + off, ws.numel() - off
 
+    # ------------------------------------------------------------------ windowed synthesis
+    def _window_workspace(self, kind, n, length):
+        """Scratch of one group of ``n`` windows of ``length`` samples (``kind``: "reverse" - the plain inverse pass's - or
+        "synth" - with z, the waveform and the windows' mel rows behind it).  A cache of its own, keyed by shape and stream: a
+        long clip alternates between a few shapes (first, middle, end windows) and ``_workspace`` keeps one shape only.  The
+        eight most recently used are kept; a size depends on (n, length) alone, never on a clip's length."""
+        import torch
+        key = (kind, n, length, self._stream())
+        ws = self._wws.pop(key, None)
+        if ws is None:
+            name = "fwn_synthesize_windows_workspace_bytes" if kind == "synth" else "fwn_workspace_bytes"
+            nbytes = getattr(self._lib, name)(C.byref(self._packed.model_desc), n, length)
+            if nbytes == 0:
+                _lib.check(-1, name)
+            while len(self._wws) >= 8:
+                del self._wws[next(iter(self._wws))]
+            ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=self._device)
+        self._wws[key] = ws                  # (re-)inserted last: the dict's order is the order of use
+        off = (-ws.data_ptr()) % 256
+        return ws.data_ptr() + off, ws.numel() - off
+
+    def reverse_windowed(self, z, c, window, batch=8, halo=None, g=None):
+        """``reverse(z, c)`` of clips of any length, window by window: z [B,T,1], c [B,T/hop,num_mels] -> x [B,T,1] fp32, T a
+        multiple of lcm(hop_size, 2^n_block).  ``windowing.plan_windows(T, window, hparams, halo)`` cuts every clip into cores
+        of ``window`` samples with ``windowing.halo_samples`` of real context on both sides; windows of equal length - of all
+        clips - share a plain rectangular inverse pass, ``batch`` at a time, and each core is copied into the result.  With the
+        default halo the result is the whole-clip pass's to rounding (exactly, in exact arithmetic: the halo covers the
+        network's receptive field), and T is bounded by memory for z, c and x only, not by what one pass can address.
+        ``halo`` (a multiple of the unit; 0 = hard cuts) is for experiments.  Host sequencing only: slices, the inverse pass,
+        copies."""
+        import torch
+        from . import windowing
+        self._check_g(g)
+        b, t, z32, c32 = self._prep(z, c, "z")
+        plans = [windowing.plan_windows(t, window, self._hparams, halo)] * b
+        x = torch.empty(b, t, 1, dtype=torch.float32, device=self._device)
+        for group in windowing.group_windows(plans, batch, self._hparams):
+            spans = [(clip,) + plans[clip][k] for clip, k in group]
+            length = spans[0][2] - spans[0][1]
+            zg = torch.stack([z32[clip, lo:hi] for clip, lo, hi, _, _ in spans])
+            cg = torch.stack([c32[clip, lo // self.hop:hi // self.hop] for clip, lo, hi, _, _ in spans])
+            xg = torch.empty(len(spans), length, 1, dtype=torch.float32, device=self._device)
+            wsp, wsn = self._window_workspace("reverse", len(spans), length)
+            rc = self._lib.fwn_model_reverse(C.byref(self._packed.model_desc), len(spans), length, zg.data_ptr(), cg.data_ptr(),
+                                             wsp, wsn, xg.data_ptr(), self._stream())
+            _lib.check(rc, "fwn_model_reverse")
+            for row, (clip, lo, _, a, e) in enumerate(spans):
+                x[clip, a:e] = xg[row, a - lo:e - lo]
+        return x
+
+    def _windows_call(self, mel_flat, rows, length, seed, temp, pcm_flat, wav_flat):
+        """One ``fwn_model_synthesize_windows`` group.  rows: per window ``(clip_id, start, mel_row, core_off, core_len, out_off)``
+        - the window is samples [start, start + length) of clip ``clip_id``'s latent stream, its mel rows start at row
+        ``mel_row`` of ``mel_flat``, and ``core_len`` samples from ``core_off`` of its waveform go to element ``out_off`` of
+        ``pcm_flat`` (and ``wav_flat``).  The six tables go up as one buffer: the int64 ones first, so all are aligned."""
+        import torch
+        n = len(rows)
+        t64 = np.asarray([[r[1] for r in rows], [r[2] for r in rows], [r[5] for r in rows]], dtype=np.int64)
+        t32 = np.asarray([[r[0] for r in rows], [r[3] for r in rows], [r[4] for r in rows]], dtype=np.int64).astype(np.uint32)
+        tab = torch.from_numpy(np.concatenate([t64.reshape(-1).view(np.uint8), t32.reshape(-1).view(np.uint8)])).to(self._device)
+        p64, p32 = tab.data_ptr(), tab.data_ptr() + 24 * n
+        assert p64 % 8 == 0
+        wsp, wsn = self._window_workspace("synth", n, length)
+        rc = self._lib.fwn_model_synthesize_windows(C.byref(self._packed.model_desc), n, length, mel_flat.data_ptr(), p64 + 8 * n,
+                                                    p32, p64, p32 + 4 * n, p32 + 8 * n, p64 + 16 * n, int(seed) % (1 << 64),
+                                                    float(temp), wsp, wsn, pcm_flat.data_ptr(),
+                                                    None if wav_flat is None else wav_flat.data_ptr(), self._stream())
+        _lib.check(rc, "fwn_model_synthesize_windows")
+
+    def _temp(self, temp):
+        return float(self._hparams.temp if temp is None else temp)
+
+    def synthesize_windowed(self, c, seed, clip_ids=None, window=None, batch=8, temp=None, return_wav=False, halo=None):
+        """``synthesize`` for clips of any length: c [B,F,num_mels] -> 16-bit PCM, ``torch.int16`` [B, F*hop] on the device, F*hop
+        a multiple of lcm(hop_size, 2^n_block).  The clips are cut by ``windowing.plan_windows(F*hop, window, hparams, halo)``
+        (``window`` in samples; default 65 536 rounded up to the unit); windows of equal length, of all clips, share a call,
+        ``batch`` at a time, and each call is ``fwn_model_synthesize_windows``: the window's slice of the clip's latent stream,
+        its mel rows gathered from ``c``, the plain inverse pass, the cores written into the result as PCM - all on the device.
+        z is exactly ``sample_z``'s stream of (seed, clip id) (``clip_ids``: None = 0 .. B-1), so a clip's latent depends on
+        neither ``window`` nor ``batch``; the waveform is the whole-clip pass's to rounding (``reverse_windowed``).  No ceiling
+        on T other than memory for the mel and the PCM, and 2^34 samples per clip.  The scratch depends on (batch, window)
+        alone.  ``return_wav`` adds the fp32 waveform [B,T,1]."""
+        import torch
+        from . import windowing
+        if self._packed is None:
+            raise RuntimeError("no parameters loaded: call load_params() / init_synthetic() first")
+        hp = self._hparams
+        if c.dim() != 3 or c.shape[2] != hp.num_mels:
+            raise ValueError("c must have shape [B, T/hop, %d], got %r" % (hp.num_mels, tuple(c.shape)))
+        b, frames = int(c.shape[0]), int(c.shape[1])
+        t = frames * self.hop
+        if window is None:
+            unit = windowing.unit_samples(hp)
+            window = -(-65536 // unit) * unit
+        if b < 1:
+            raise ValueError("c holds no clip")
+        if t > (1 << 34):
+            raise ValueError("T=%d exceeds the 2^34 samples one clip's latent stream numbers" % t)
+        plans = [windowing.plan_windows(t, window, hp, halo)] * b
+        ids = list(range(b)) if clip_ids is None else self._clip_id_values(clip_ids, b)
+        c32 = c.to(device=torch.device(self._device), dtype=torch.float32).contiguous()
+        pcm = torch.empty(b, t, dtype=torch.int16, device=self._device)
+        wav = torch.empty(b, t, 1, dtype=torch.float32, device=self._device) if return_wav else None
+        for group in windowing.group_windows(plans, batch, self._hparams):
+            rows, length = [], None
+            for clip, k in group:
+                lo, hi, a, e = plans[clip][k]
+                length = hi - lo
+                rows.append((ids[clip], lo, clip * frames + lo // self.hop, a - lo, e - a, clip * t + a))
+            self._windows_call(c32, rows, length, seed, self._temp(temp), pcm, wav)
+        return (pcm, wav) if return_wav else pcm
+
+    def stream(self, seed, clip_id=0, window=None, temp=None, halo=None):
+        """Synthesis of one clip whose mel arrives while it is being made: -> a ``SynthesisStream`` with ``push(frames)`` and
+        ``finish()``.  Fed the frames of ``c`` in any split, the concatenated output is ``synthesize_windowed(c, seed, [clip_id],
+        window, batch=1)`` bit for bit (the same windows, one call each); core k comes out of the push that delivers frame
+        ``(b_k + H) / hop``."""
+        if self._packed is None:
+            raise RuntimeError("no parameters loaded: call load_params() / init_synthetic() first")
+        return SynthesisStream(self, seed, clip_id, window, temp, halo)
+
     def upsample(self, c):
         """c [B,F,num_mels] -> [B,F*hop,num_mels] fp32 (model.py:398-404)."""
         import torch
@@ -417,6 +544,75 @@ class FloWaveNet:
         return cur
 
     __call__ = forward
+
+
+class SynthesisStream:
+    """``FloWaveNet.stream``: 16-bit PCM of one clip while its mel is still arriving.  ``push(frames)`` takes [f, num_mels] (a
+    tensor or an array, any f >= 0) and returns the PCM of the cores that became computable with them, one ``torch.int16``
+    tensor on the device, possibly empty; ``finish()`` returns the rest (``ValueError`` if the frame total is no multiple of
+    lcm(hop_size, 2^n_block) / hop_size).  One ``fwn_model_synthesize_windows`` call per window; the object keeps only the
+    mel frames a later window still needs - at most (window + 2 H) / hop plus one push (``windowing.StreamPlanner``)."""
+
+    def __init__(self, model, seed, clip_id=0, window=None, temp=None, halo=None):
+        from . import windowing
+        hp = model._hparams
+        if window is None:
+            unit = windowing.unit_samples(hp)
+            window = -(-65536 // unit) * unit
+        self._model = model
+        self._plan = windowing.StreamPlanner(hp, window, halo)
+        self._seed = int(seed)
+        self._clip = FloWaveNet._clip_id_values([clip_id], 1)[0]
+        self._temp = model._temp(temp)
+        self._buf = None             # device [capacity, num_mels]: frames _base .. _base + _n of the clip
+        self._base = 0
+        self._n = 0
+
+    @property
+    def retained_frames(self):
+        return self._n
+
+    def _append(self, frames):
+        import torch
+        m = self._model
+        f = torch.as_tensor(frames).to(device=torch.device(m._device), dtype=torch.float32)
+        if f.dim() != 2 or f.shape[1] != m._hparams.num_mels:
+            raise ValueError("frames must have shape [f, %d], got %r" % (m._hparams.num_mels, tuple(f.shape)))
+        need = self._n + int(f.shape[0])
+        if self._buf is None or need > self._buf.shape[0]:
+            grown = torch.empty(max(need, 2 * (0 if self._buf is None else self._buf.shape[0])), m._hparams.num_mels,
+                                dtype=torch.float32, device=m._device)
+            if self._n:
+                grown[:self._n] = self._buf[:self._n]
+            self._buf = grown
+        self._buf[self._n:need] = f
+        self._n = need
+        return int(f.shape[0])
+
+    def _run(self, windows):
+        import torch
+        m = self._model
+        out = []
+        for lo, hi, a, e in windows:
+            pcm = torch.empty(e - a, dtype=torch.int16, device=m._device)
+            m._windows_call(self._buf, [(self._clip, lo, lo // m.hop - self._base, a - lo, e - a, 0)], hi - lo, self._seed, self._temp,
+                            pcm, None)
+            out.append(pcm)
+        drop = self._plan.first_frame - self._base      # frames no later window reads
+        if drop > 0:
+            drop = min(drop, self._n)
+            self._buf[:self._n - drop] = self._buf[drop:self._n].clone()
+            self._base += drop
+            self._n -= drop
+        if not out:
+            return torch.empty(0, dtype=torch.int16, device=m._device)
+        return out[0] if len(out) == 1 else torch.cat(out)
+
+    def push(self, frames):
+        return self._run(self._plan.push(self._append(frames)))
+
+    def finish(self):
+        return self._run(self._plan.finish())
 
 
 def check_lengths(lengths, b, t, hop, n_block):

@@ -13,6 +13,9 @@ lengths=)`` gives every clip what it gives alone), and draws each clip's ``z`` f
 audio does not depend on the batch it lands in.  ``--device_rng`` (opt-in) keeps the arithmetic on the device
 (``FloWaveNet.synthesize``): z comes from a Philox4x32-10 stream keyed by (``--seed``, the clip's index in sorted file-name order) -
 a stream of this package's own - with or without ``--ragged``, only the mel goes up and only 16-bit PCM comes down.
+``--window SAMPLES`` (opt-in) synthesizes every clip longer than that window by window (``windowing.plan_windows``: each window
+with the network's receptive field of real context on both sides, so the seams are exact) - no clip is too long for one call
+any more - and writes its wav core by core; the other clips take the paths above.
 """
 from __future__ import annotations
 
@@ -125,13 +128,17 @@ def synthesize(args, hparams, model=None):
     os.makedirs(args.output_dir, exist_ok=True)
     names = sorted(f for f in os.listdir(args.mels_dir) if f.endswith(".npy"))
     mels = {n: np.load(os.path.join(args.mels_dir, n)).astype(np.float32) for n in names}
+    done = set()                                     # --window: the clips longer than it, written window by window
+    if getattr(args, "window", None) is not None:
+        done = _synthesize_windowed(args, hparams, model, names, mels, window_samples(args.window, hparams))
     if getattr(args, "device_rng", False):
-        return _synthesize_device(args, hparams, model, names, mels)
+        return _synthesize_device(args, hparams, model, names, mels, done)
     if getattr(args, "ragged", False):
-        return _synthesize_ragged(args, hparams, model, names, mels)
+        return _synthesize_ragged(args, hparams, model, names, mels, done)
     by_len = {}
     for n in names:
-        by_len.setdefault(mels[n].shape[0], []).append(n)
+        if n not in done:
+            by_len.setdefault(mels[n].shape[0], []).append(n)
     gen = torch.Generator(device="cpu").manual_seed(int(args.seed))
     hop = hparams.hop_size
     align = max(1, (1 << hparams.n_block) // np.gcd(1 << hparams.n_block, hop))
@@ -152,14 +159,16 @@ def synthesize(args, hparams, model=None):
     return names
 
 
-def _synthesize_ragged(args, hparams, model, names, mels):
+def _synthesize_ragged(args, hparams, model, names, mels, done=()):
     """``--ragged``: clips of similar length share a call (``plan_batches``).  Each clip is edge-padded to the model's
     alignment as without the flag - that is its ``length`` - and zero-padded from there to the group's T; clip k (in sorted
-    file-name order) draws its z from ``torch.Generator().manual_seed(seed + k)``."""
+    file-name order) draws its z from ``torch.Generator().manual_seed(seed + k)``.  ``done``: names ``--window`` has written."""
     import torch
     hop = hparams.hop_size
     frames = [mels[n].shape[0] for n in names]
-    for group in plan_batches(frames, int(args.batch), float(getattr(args, "max_pad_frac", 0.25)), hparams):
+    keep = [k for k, n in enumerate(names) if n not in done]
+    for group in plan_batches([frames[k] for k in keep], int(args.batch), float(getattr(args, "max_pad_frac", 0.25)), hparams):
+        group = [keep[j] for j in group]
         own = [_aligned_frames(frames[k], hparams) for k in group]        # frames of each clip after its own edge padding
         top = max(own)
         c = np.zeros((len(group), top, hparams.num_mels), dtype=np.float32)
@@ -237,17 +246,65 @@ def synthesize_device(model, hparams, mel_list, groups, seed, ragged, emit):
         flush()
 
 
-def _synthesize_device(args, hparams, model, names, mels):
+def _synthesize_device(args, hparams, model, names, mels, done=()):
     """``--device_rng``: clip k (in sorted file-name order) has clip id k under ``--seed``, with and without ``--ragged`` - the
-    same seed gives a clip the same z in either mode; the padding rules are those of the host paths."""
+    same seed gives a clip the same z in either mode; the padding rules are those of the host paths.  ``done``: names
+    ``--window`` has written (they keep their index: the other clips' ids do not move)."""
     mel_list = [mels[n] for n in names]
-    groups = device_batches([m.shape[0] for m in mel_list], args, hparams)
+    keep = [k for k, n in enumerate(names) if n not in done]
+    groups = [[keep[j] for j in g] for g in device_batches([mel_list[k].shape[0] for k in keep], args, hparams)]
 
     def emit(k, pcm):
         write_wav_pcm(os.path.join(args.output_dir, names[k][:-4] + ".wav"), pcm, hparams.sample_rate)
 
     synthesize_device(model, hparams, mel_list, groups, int(args.seed), bool(getattr(args, "ragged", False)), emit)
     return names
+
+
+def window_samples(window, hparams):
+    """``--window SAMPLES`` rounded up to a multiple of lcm(hop_size, 2^n_block), the unit every window edge sits on."""
+    from .windowing import unit_samples
+    unit = unit_samples(hparams)
+    if int(window) < 1:
+        raise ValueError("--window must be a positive number of samples, got %r" % (window,))
+    return -(-int(window) // unit) * unit
+
+
+def _synthesize_windowed(args, hparams, model, names, mels, window):
+    """``--window``: every clip longer than ``window`` samples (after its edge padding), one at a time, through
+    ``FloWaveNet.synthesize_windowed`` (``--device_rng``: clip id = the clip's index in sorted file-name order, as without the
+    flag) or ``FloWaveNet.reverse_windowed`` (z drawn on the host from ``torch.Generator().manual_seed(seed + index)``, the
+    per-clip generator of ``--ragged``), ``--batch`` windows per call.  The result stays on the device and comes down core by
+    core into ``wave``'s incremental ``writeframes``: the host never holds more than one window of audio, and no clip is too
+    long for one call.  -> the set of names written."""
+    import torch
+    from .windowing import plan_windows
+    hop = hparams.hop_size
+    device_rng = bool(getattr(args, "device_rng", False))
+    done = set()
+    for k, name in enumerate(names):
+        frames = int(mels[name].shape[0])
+        own = _aligned_frames(frames, hparams)
+        if own * hop <= window:
+            continue
+        c = torch.from_numpy(np.pad(mels[name], ((0, own - frames), (0, 0)), mode="edge")[None]).cuda()
+        if device_rng:
+            audio = model.synthesize_windowed(c, int(args.seed), clip_ids=[k], window=window, batch=int(args.batch))[0]
+        else:
+            gen = torch.Generator(device="cpu").manual_seed(int(args.seed) + k)
+            z = torch.randn(1, own * hop, 1, generator=gen) * hparams.temp
+            audio = model.reverse_windowed(z.cuda(), c, window, batch=int(args.batch))[0, :, 0]
+        with wave.open(os.path.join(args.output_dir, name[:-4] + ".wav"), "wb") as w:
+            w.setnchannels(1)
+            w.setsampwidth(2)
+            w.setframerate(int(hparams.sample_rate))
+            for _, _, a, b in plan_windows(own * hop, window, hparams):
+                part = audio[a:min(b, frames * hop)].cpu().numpy()
+                if not device_rng:                   # write_wav's arithmetic
+                    part = (np.clip(part.astype(np.float64), -1.0, 1.0) * 32767.0).round()
+                w.writeframes(np.ascontiguousarray(part, dtype="<i2").tobytes())
+        done.add(name)
+    return done
 
 
 def main(argv=None):
@@ -266,6 +323,10 @@ def main(argv=None):
     parser.add_argument("--device_rng", action="store_true",
                         help="draw z on the device (Philox4x32-10 keyed by --seed and the clip's index: not the default z) and "
                              "bring 16-bit PCM back instead of fp32")
+    # absent from the namespace unless given: without the flag the arguments are what they were
+    parser.add_argument("--window", type=int, default=argparse.SUPPRESS, metavar="SAMPLES",
+                        help="synthesize clips longer than SAMPLES (rounded up to lcm(hop_size, 2^n_block)) window by window, each "
+                             "with the network's receptive field of real context on both sides: no length limit, same audio")
     args = parser.parse_args(argv)
     synthesize(args, hparams)
 
