@@ -782,6 +782,62 @@ int fwn_model_synthesize_windows(const fwn_model_desc* m, int64_t n, int64_t L, 
                                  const int32_t* core_len_dev, const int64_t* out_off_dev, uint64_t seed, float temp, void* workspace,
                                  size_t workspace_bytes, int16_t* pcm_flat, float* wav_flat, void* stream);
 
+/* ---- windowed forward (additive; FWN_VERSION unchanged): log_p, logdet and the latent of a clip of any length, as the windows
+ * of windowed synthesis (the forward pass has the inverse pass's receptive field: the same halo, the same plans), each a plain
+ * rectangular forward pass in the form that keeps every tail's ZeroConv output - the ragged forward's, on full-length rows, so
+ * without a fill or a mask launch.  A window's own log_p / logdet would include its halo; the sums below go over the cores only
+ * and are added per clip.  For a clip of t samples cut into windows with cores [a, b):
+ *     log_p  = 0.5 (-log 2 pi - sum_windows sum_core z^2 / t)
+ *     logdet = sum_flows mean_C(3 logs) + sum_windows sum_flows sum_{core rows, c} (-log_s) / t
+ * (a flow of block i has t / 2^(i+1) rows of 2^i log_s channels, so the reference's mean(-log_s) / 2 is sum(-log_s) / t at every
+ * block; core edges are multiples of lcm(hop, 2^n_block), so a core is whole rows everywhere).  Every sum is fp64 in an order
+ * the launches fix - no atomics - so two identical calls give identical bits.  Every table below is a DEVICE array read and
+ * clamped by the kernels; nothing is allocated or synchronised, so a call is capturable.
+ *
+ * fwn_window_logdet_rows: fwn_ragged_logdet_rows with a per-window start.  For window r of Z [n][rows][2 Ch]: the fp64 chunk sums
+ * of -Z[row][c] ez(c) over rows [core_off[r] / samples_per_row, + core_len[r] / samples_per_row) -> acc[r][0 .. nslot - 1), the
+ * ActNorm term (an may be NULL) -> acc[r][nslot - 1], nslot = fwn_ragged_logdet_slots(n).  The start is clamped to [0, rows] and
+ * the count to what is left, on the device; no row outside the range is loaded.  core_off_dev / core_len_dev: DEVICE int32 [n],
+ * samples.  fwn_ragged_logdet_rows itself is unchanged.
+ *
+ * fwn_window_sums: window r's partial sums -> part[slot[r]][0 .. 4) fp64 (a negative slot writes nothing): [0] the sum of z^2
+ * over elements [core_off / 2, (core_off + core_len) / 2) of both final planes [2][n][L / 2] (one contiguous range per plane;
+ * clamped into the window, nothing outside is loaded), [1] the sum over the nflows flows, in flow order, of their chunk sums in
+ * acc [nflows][n][nslot], [2] the sum over the flows of acc[f][r][nslot - 1] / (2 << (f / n_flow)) - the ActNorm terms, the
+ * same for every window -, [3] the core's length.  slot_dev: DEVICE int32 [n]; part is the caller's table, as large as its
+ * largest slot says.
+ *
+ * fwn_window_scatter_latent: the cores of the final planes in TIME order - z_flat[out_off[r] + i] = sample core_off[r] + i of
+ * window r for i < core_len[r], where sample s lives in plane (s & 1) ^ swapped at element s / 2 (swapped: n_block * n_flow is
+ * odd).  This is the reference's final `out` un-squeezed n_block times, the latent fwn_model_reverse takes.  out_off_dev:
+ * DEVICE int64 [n], element offsets (the caller's to keep inside z_flat); nothing outside the cores is written.
+ *
+ * fwn_forward_windows_finish: one launch after the last group.  Clip c's windows are slots [slot0[c], slot0[c] + nwin[c]) of
+ * part, in window order; they are added in that order, whatever groups they ran in, and out2B [2][n_clips] fp32 = (log_p,
+ * logdet) per clip as fwn_model_forward_ragged lays it out; t is the sum of the cores' lengths.
+ *
+ * fwn_model_forward_windows: one group of n windows of L samples on one stream - fwn_window_gather of the audio (x_flat, rows
+ * of hop floats from row x_row[r]: 64-bit) and of the mel (mel_flat, rows of num_mels floats from mel_row[r]) -> the pass ->
+ * fwn_window_sums into acc[slot[r]] -> fwn_window_scatter_latent (z_flat may be NULL: no latent; then z_out_off_dev may be too).
+ * acc: the caller's fp64 table [.][4] for fwn_forward_windows_finish.  fwn_forward_windows_workspace_bytes(m, n, L) is a
+ * function of (n, L) alone and 0 for what the call refuses.  Refusals (FWN_ERR_ARG, before anything is launched): those of
+ * fwn_model_forward's shape checks, a null x_flat, mel_flat, acc, workspace or table, a table off its element's alignment (8
+ * bytes for the int64 ones and acc, 4 for the others), a workspace off 256 bytes, n >= 32768, a gate_fp8 descriptor.  Speed:
+ * tools/bench_windowed_forward.py. */
+int fwn_window_logdet_rows(const float* Z, int64_t n, int64_t rows, int Ch, const float* ez, const float* an, const int32_t* core_off_dev,
+                           const int32_t* core_len_dev, int32_t samples_per_row, double* acc, void* stream);
+int fwn_window_sums(const float* planes, int64_t n, int64_t L, const int32_t* core_off_dev, const int32_t* core_len_dev, const double* acc,
+                    int nflows, int n_flow, const int32_t* slot_dev, double* part, void* stream);
+int fwn_window_scatter_latent(const float* planes, int64_t n, int64_t L, int swapped, const int32_t* core_off_dev,
+                              const int32_t* core_len_dev, const int64_t* out_off_dev, float* z_flat, void* stream);
+int fwn_forward_windows_finish(const double* part, const int32_t* clip_slot0_dev, const int32_t* clip_nwin_dev, int64_t n_clips,
+                               float* out2B, void* stream);
+size_t fwn_forward_windows_workspace_bytes(const fwn_model_desc* m, int64_t n, int64_t L);
+int fwn_model_forward_windows(const fwn_model_desc* m, int64_t n, int64_t L, const float* x_flat, const int64_t* x_row_dev,
+                              const float* mel_flat, const int64_t* mel_row_dev, const int32_t* core_off_dev, const int32_t* core_len_dev,
+                              const int32_t* slot_dev, double* acc, const int64_t* z_out_off_dev, float* z_flat, void* workspace,
+                              size_t workspace_bytes, void* stream);
+
 /* ---- device-resident corpus (additive; FWN_VERSION unchanged): a training batch drawn and gathered on the device.
  *
  * Layout.  audio: flat fp32, all utterances back to back; mel: flat fp32 [total_frames][num_mels]; frame_off: DEVICE int64

@@ -261,6 +261,12 @@ SIGNATURES = {
     "fwn_synthesize_windows_workspace_bytes": (C.c_size_t, [C.POINTER(ModelDesc), i64, i64]),
     "fwn_model_synthesize_windows": (C.c_int, [C.POINTER(ModelDesc), i64, i64, vp, vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_float, vp,
                                                C.c_size_t, vp, vp, vp]),
+    "fwn_window_logdet_rows": (C.c_int, [vp, i64, i64, C.c_int, vp, vp, vp, vp, C.c_int32, vp, vp]),
+    "fwn_window_sums": (C.c_int, [vp, i64, i64, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp]),
+    "fwn_window_scatter_latent": (C.c_int, [vp, i64, i64, C.c_int, vp, vp, vp, vp, vp]),
+    "fwn_forward_windows_finish": (C.c_int, [vp, vp, vp, i64, vp, vp]),
+    "fwn_forward_windows_workspace_bytes": (C.c_size_t, [C.POINTER(ModelDesc), i64, i64]),
+    "fwn_model_forward_windows": (C.c_int, [C.POINTER(ModelDesc), i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]),
     "fwn_corpus_draw": (C.c_int, [vp, vp, vp, i64, C.c_int, C.c_int, C.c_int, i64, i64, C.c_uint64, C.c_uint32, vp, vp, vp, vp, vp, vp]),
 }
 

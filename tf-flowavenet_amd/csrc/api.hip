@@ -562,10 +562,14 @@ struct FlowChain {
 // A flow of a ragged forward pass (fwn_model_forward_ragged): where its tail keeps Z = (log_s | t) [M][2 Ch] fp32 and where
 // the per-clip sums of -log_s go ([B][fwn_ragged_logdet_nslot(B)] fp64).
 // mom_part: a ragged init pass (fwn_model_forward_init_ragged) - scratch of the masked moments, fwn_ragged_moments_nslot chunks.
+// core_off / core_len: a windowed forward pass (fwn_model_forward_windows) - no lengths; the sums go over each window's core
+// rows [core_off / (2 Ch), + core_len / (2 Ch)) instead (DEVICE int32 [B], samples).
 struct FlowRagged {
     float* z;
     double* acc;
     double* mom_part;
+    const int32_t* core_off;
+    const int32_t* core_len;
 };
 // One flow's run.  Zero-initialise, then set by name; what stays zero is absent.
 struct FlowRun {
@@ -662,7 +666,10 @@ static int flow_run_impl(const FlowRun& a) {
     fwn_launch_tail(a.o, (long)M * 256, d->L, d->Wskip, d->bskip, d->Wfinal, d->bfinal, d->Wzero, d->bzero,
                     d->ezero, d->an, a.xa, a.xb, inverse ? nullptr : a.partial, M, d->Ch, d->npt, inverse, hn, hc, (chain || a.rg) ? &tc : nullptr,
                     d->Wts, st);
-    if (a.rg) fwn_launch_ragged_logdet(a.rg->z, (long)a.B, Ti, d->Ch, d->ezero, d->an, a.len, (int)a.B, 2 * d->Ch, a.rg->acc, st);
+    if (a.rg && a.rg->core_off)
+        fwn_launch_window_logdet(a.rg->z, (long)a.B, Ti, d->Ch, d->ezero, d->an, a.rg->core_off, a.rg->core_len, 2 * d->Ch, a.rg->acc, st);
+    else if (a.rg)
+        fwn_launch_ragged_logdet(a.rg->z, (long)a.B, Ti, d->Ch, d->ezero, d->an, a.len, (int)a.B, 2 * d->Ch, a.rg->acc, st);
     return check_launch("fwn_flow_run");
 }
 
@@ -1223,16 +1230,23 @@ int fwn_model_persist_status(const fwn_model_desc* m, int64_t B, int64_t T, cons
 // Forward with len: every flow's x_a plane gets -shift in those rows before its front conv and its tail keeps Z (flow_run_impl),
 // the per-clip log-det sums of all flows and the per-clip prior end in out2 [2][B] (the tails' own partials are ignored).
 // PASS_INIT_RAGGED: that pass with init 2 - every flow's moments over the clips' own rows.
+// PASS_FORWARD_WINDOWS (wc): the ragged forward's form - a launch per stage, every tail keeps Z - on full-length rows, so no
+// fill or mask is launched (len NULL); each flow's -log_s sums go over the window's core rows, and the pass ends with the planes
+// at home in the workspace: the prior, the per-clip sums and the latent are the caller's (fwn_model_forward_windows).
+struct WindowCores {
+    const int32_t* off;      // DEVICE int32 [B]: each window's core, in samples from the window's start
+    const int32_t* len;
+};
 static int model_pass(PassKind kind, const fwn_model_desc* m, int64_t B, int64_t T, const float* in, const float* mel, const int32_t* len,
                       void* workspace, size_t workspace_bytes, fwn_reduce_fn reduce, void* user, float* out2, float* z_planes, float* x_out,
-                      void* stream) {
+                      void* stream, const WindowCores* wc = nullptr) {
     const PassTraits pt = pass_traits(kind);
     const char* what = pt.what;
     const bool reverse = pt.reverse;
     const int init = pt.init;
     int rc = check_model(m, B, T);
     if (rc) return rc;
-    REQUIRE(in && mel && workspace && (reverse ? x_out : out2), "%s: null pointer", what);
+    REQUIRE(in && mel && workspace && (reverse ? (void*)x_out : wc ? (void*)wc->off : (void*)out2), "%s: null pointer", what);
     REQUIRE((((uintptr_t)workspace) & 255) == 0, "workspace must be 256-byte aligned");
     REQUIRE(!reverse || ((m->n_block * m->n_flow) & 1) == 0,
             "reverse with odd n_block*n_flow ends in swapped channel order (model.py:199,254); unsupported");
@@ -1298,7 +1312,7 @@ static int model_pass(PassKind kind, const fwn_model_desc* m, int64_t B, int64_t
             unsigned* sync = (!init && b.one_launch) ? (unsigned*)(ws + c.sync + (size_t)(i * nf + j) * c.sync_stride) : nullptr;
             FlowChain ch = flow_chain(m, d, next, M, init != 0, pl.spare, have_h0, b.chained && !sync);
             const FlowRagged rg{(float*)(ws + c.zsave), (double*)(ws + c.acc) + (size_t)(i * nf + j) * B * fwn_ragged_logdet_nslot((long)B),
-                                pt.mompart ? (double*)(ws + c.mompart) : nullptr};
+                                pt.mompart ? (double*)(ws + c.mompart) : nullptr, wc ? wc->off : nullptr, wc ? wc->len : nullptr};
             FlowRun fr;
             memset(&fr, 0, sizeof(fr));
             fr.d = d; fr.B = B; fr.T = T; fr.xa = pl.at[p]; fr.xb = pl.at[p ^ 1]; fr.ca = ca; fr.P = P;
@@ -1325,6 +1339,7 @@ static int model_pass(PassKind kind, const fwn_model_desc* m, int64_t B, int64_t
         fwn_launch_merge(planes, B, T, x_out, st);
         rows.zero(x_out, (long)T, 4, 1);
     } else {
+        if (wc) return check_launch(what);
         if (len) fwn_launch_ragged_finish(planes, (long)B, (long)T, (const double*)(ws + c.acc), m->n_block * nf, nf, len, out2, st);
         else fwn_launch_prior(planes, (long)(B * T), partial, poff, 1.0 / (double)(B * T), out2, st);
         if (z_planes) {
@@ -1501,6 +1516,94 @@ int fwn_model_synthesize_windows(const fwn_model_desc* m, int64_t n, int64_t L, 
     if (rc) return rc;
     fwn_launch_window_scatter(wav, (long)n, (long)L, core_off_dev, core_len_dev, (const long long*)out_off_dev, (short*)pcm_flat, wav_flat, st);
     return check_launch("fwn_model_synthesize_windows");
+}
+
+// ---- windowed forward: one group of n windows of L samples - audio and mel rows, the pass, the cores' sums and latent (include/fwn.h) ----
+int fwn_window_logdet_rows(const float* Z, int64_t n, int64_t rows, int Ch, const float* ez, const float* an, const int32_t* core_off_dev,
+                           const int32_t* core_len_dev, int32_t samples_per_row, double* acc, void* stream) {
+    REQUIRE(Z && ez && core_off_dev && core_len_dev && acc && n > 0 && n < 65536 && rows > 0 && samples_per_row > 0,
+            "fwn_window_logdet_rows: bad argument");
+    REQUIRE(Ch >= 1 && (Ch & (Ch - 1)) == 0, "fwn_window_logdet_rows: Ch=%d must be a power of two", Ch);
+    REQUIRE(ALIGNED4(Z) && ALIGNED8(acc) && ALIGNED4(core_off_dev) && ALIGNED4(core_len_dev), "fwn_window_logdet_rows: misaligned buffer");
+    REQUIRE(rows <= ((int64_t)1 << 31) / samples_per_row, "fwn_window_logdet_rows: rows * samples_per_row exceeds 2^31");
+    fwn_launch_window_logdet(Z, (long)n, (long)rows, Ch, ez, an, core_off_dev, core_len_dev, samples_per_row, acc, (hipStream_t)stream);
+    return check_launch("fwn_window_logdet_rows");
+}
+int fwn_window_sums(const float* planes, int64_t n, int64_t L, const int32_t* core_off_dev, const int32_t* core_len_dev, const double* acc,
+                    int nflows, int n_flow, const int32_t* slot_dev, double* part, void* stream) {
+    REQUIRE(planes && core_off_dev && core_len_dev && acc && slot_dev && part, "fwn_window_sums: null pointer");
+    REQUIRE(n > 0 && n < 65536 && L > 0 && L < ((int64_t)1 << 31) && L % 2 == 0 && nflows >= 0 && n_flow >= 1,
+            "fwn_window_sums: n in [1, 65535], L even in [2, 2^31), nflows >= 0, n_flow >= 1");
+    REQUIRE(ALIGNED4(planes) && ALIGNED4(core_off_dev) && ALIGNED4(core_len_dev) && ALIGNED4(slot_dev) && ALIGNED8(acc) && ALIGNED8(part),
+            "fwn_window_sums: misaligned buffer");
+    fwn_launch_window_sums(planes, (long)n, (long)L, core_off_dev, core_len_dev, acc, nflows, n_flow, slot_dev, part, (hipStream_t)stream);
+    return check_launch("fwn_window_sums");
+}
+int fwn_window_scatter_latent(const float* planes, int64_t n, int64_t L, int swapped, const int32_t* core_off_dev,
+                              const int32_t* core_len_dev, const int64_t* out_off_dev, float* z_flat, void* stream) {
+    REQUIRE(planes && core_off_dev && core_len_dev && out_off_dev && z_flat, "fwn_window_scatter_latent: null pointer");
+    REQUIRE(n > 0 && n < 65536 && L > 0 && L < ((int64_t)1 << 31) && L % 2 == 0, "fwn_window_scatter_latent: n in [1, 65535], L even in [2, 2^31)");
+    REQUIRE(ALIGNED4(planes) && ALIGNED4(z_flat) && ALIGNED4(core_off_dev) && ALIGNED4(core_len_dev),
+            "fwn_window_scatter_latent: planes, z_flat and the int32 tables must be 4-byte aligned");
+    REQUIRE(ALIGNED8(out_off_dev), "fwn_window_scatter_latent: out_off_dev must be 8-byte aligned");
+    fwn_launch_window_latent(planes, (long)n, (long)L, swapped ? 1 : 0, core_off_dev, core_len_dev, (const long long*)out_off_dev, z_flat,
+                             (hipStream_t)stream);
+    return check_launch("fwn_window_scatter_latent");
+}
+int fwn_forward_windows_finish(const double* part, const int32_t* clip_slot0_dev, const int32_t* clip_nwin_dev, int64_t n_clips, float* out2B,
+                               void* stream) {
+    REQUIRE(part && clip_slot0_dev && clip_nwin_dev && out2B && n_clips > 0 && n_clips < ((int64_t)1 << 31), "fwn_forward_windows_finish: bad argument");
+    REQUIRE(ALIGNED8(part) && ALIGNED4(clip_slot0_dev) && ALIGNED4(clip_nwin_dev) && ALIGNED4(out2B), "fwn_forward_windows_finish: misaligned buffer");
+    fwn_launch_windows_finish(part, clip_slot0_dev, clip_nwin_dev, (long)n_clips, out2B, (hipStream_t)stream);
+    return check_launch("fwn_forward_windows_finish");
+}
+// the pass's own workspace first (model_pass carves it as ever; its mel region receives the windows' mel rows - a pass without
+// lengths reads the mel it is given and never copies it), then the windows' audio
+size_t fwn_forward_windows_workspace_bytes(const fwn_model_desc* m, int64_t n, int64_t L) {
+    if (check_model(m, n, L) != FWN_OK || n >= 32768 || m->gate_fp8) return 0;
+    return carve(m, n, L, PASS_FORWARD_WINDOWS).total + synth_extra(n, L);
+}
+int fwn_model_forward_windows(const fwn_model_desc* m, int64_t n, int64_t L, const float* x_flat, const int64_t* x_row_dev,
+                              const float* mel_flat, const int64_t* mel_row_dev, const int32_t* core_off_dev, const int32_t* core_len_dev,
+                              const int32_t* slot_dev, double* acc, const int64_t* z_out_off_dev, float* z_flat, void* workspace,
+                              size_t workspace_bytes, void* stream) {
+    // everything the pass would refuse is refused here, before the gathers are enqueued
+    int rc = check_model(m, n, L);
+    if (rc) return rc;
+    REQUIRE(x_flat && mel_flat && workspace && acc, "fwn_model_forward_windows: null pointer");
+    REQUIRE(x_row_dev && mel_row_dev && core_off_dev && core_len_dev && slot_dev && (z_out_off_dev || !z_flat),
+            "fwn_model_forward_windows: null table");
+    REQUIRE(ALIGNED8(x_row_dev) && ALIGNED8(mel_row_dev) && ALIGNED8(z_out_off_dev) && ALIGNED8(acc),
+            "fwn_model_forward_windows: the int64 tables (x_row_dev, mel_row_dev, z_out_off_dev) and acc must be 8-byte aligned");
+    REQUIRE(ALIGNED4(core_off_dev) && ALIGNED4(core_len_dev) && ALIGNED4(slot_dev),
+            "fwn_model_forward_windows: the int32 tables (core_off_dev, core_len_dev, slot_dev) must be 4-byte aligned");
+    REQUIRE((((uintptr_t)workspace) & 255) == 0, "fwn_model_forward_windows: workspace must be 256-byte aligned");
+    REQUIRE(ALIGNED4(x_flat) && ALIGNED4(mel_flat) && ALIGNED4(z_flat), "fwn_model_forward_windows: x_flat, mel_flat and z_flat must be 4-byte aligned");
+    REQUIRE(n < 32768, "fwn_model_forward_windows: n=%lld windows (at most 32767 per call)", (long long)n);
+    REQUIRE(!m->gate_fp8, "fwn_model_forward_windows: windows go with a model without fp8 gates (the pass is the ragged forward's form)");
+    const Carve c = carve(m, n, L, PASS_FORWARD_WINDOWS);
+    const size_t need = c.total + synth_extra(n, L);
+    if (workspace_bytes < need)
+        return fail(FWN_ERR_WORKSPACE, "fwn_model_forward_windows: workspace %zu < required %zu bytes", workspace_bytes, need);
+    char* ws = (char*)workspace;
+    float* xg = (float*)(ws + c.total);
+    float* mel = (float*)(ws + c.mel);
+    hipStream_t st = (hipStream_t)stream;
+    const int hop = hop_of(m);
+    fwn_launch_window_gather(x_flat, (const long long*)x_row_dev, (long)hop, xg, (long)n, (long)L, st);
+    fwn_launch_window_gather(mel_flat, (const long long*)mel_row_dev, (long)m->num_mels, mel, (long)n, (long)(L / hop) * m->num_mels, st);
+    rc = check_launch("fwn_model_forward_windows (audio, mel rows)");
+    if (rc) return rc;
+    const WindowCores wc{core_off_dev, core_len_dev};
+    rc = model_pass(PASS_FORWARD_WINDOWS, m, n, L, xg, mel, nullptr, workspace, c.total, nullptr, nullptr, nullptr, nullptr, nullptr, stream, &wc);
+    if (rc) return rc;
+    const float* planes = (const float*)(ws + c.planes);
+    fwn_launch_window_sums(planes, (long)n, (long)L, core_off_dev, core_len_dev, (const double*)(ws + c.acc), m->n_block * m->n_flow,
+                           m->n_flow, slot_dev, acc, st);
+    if (z_flat)
+        fwn_launch_window_latent(planes, (long)n, (long)L, (m->n_block * m->n_flow) & 1, core_off_dev, core_len_dev,
+                                 (const long long*)z_out_off_dev, z_flat, st);
+    return check_launch("fwn_model_forward_windows");
 }
 
 // ---- device-resident corpus: one training batch drawn and gathered on the device (include/fwn.h) ----

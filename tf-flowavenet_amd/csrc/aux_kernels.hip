@@ -914,8 +914,184 @@ __global__ __launch_bounds__(256) void ragged_finish_kernel(const float* __restr
     }
 }
 
+// ---- windowed forward: the sums and the latent of a group's cores (include/fwn.h) --------------------------
+// ragged_logdet_kernel with a per-window start: window c's rows [core_off[c] / spr, core_off[c] / spr + core_len[c] / spr) of
+// Z [n][rows][2 Ch] - the start clamped to [0, rows], the count to what is left - and no row outside that range is loaded.
+// The same chunks, the same fp64 sums in the order the grid fixes, the same slots (acc[c][chunk], the ActNorm term in
+// acc[c][nslot - 1]).  16-byte loads as there; at Ch = 1 (two rows per 16 bytes) a range that starts on an odd row takes
+// its first row as a dword, and so does one that ends on one its last.
+__global__ __launch_bounds__(256) void window_logdet_kernel(const float* __restrict__ Z, long rows, int Ch,
+                                                            const float* __restrict__ ez, const float* __restrict__ an,
+                                                            const int* __restrict__ core_off, const int* __restrict__ core_len,
+                                                            int spr, double* __restrict__ acc, int nslot) {
+    __shared__ double red[256];
+    const long c = blockIdx.y;
+    long r0 = (long)core_off[c] / spr, keep = (long)core_len[c] / spr;
+    r0 = r0 < 0 ? 0 : (r0 > rows ? rows : r0);
+    keep = keep < 0 ? 0 : (keep > rows - r0 ? rows - r0 : keep);
+    const float* zc = Z + ((size_t)c * rows + (size_t)r0) * 2 * Ch;
+    const long stride = (long)gridDim.x * 256, first = (long)blockIdx.x * 256 + threadIdx.x;
+    double s = 0.0;
+    if (Ch >= 4 && ((uintptr_t)zc & 15) == 0) {
+        const int upr = Ch >> 2;                              // 16-byte pieces of log_s per row
+        const long n = keep * upr;
+        for (long i = first; i < n; i += stride) {
+            const long row = i / upr;
+            const int t0 = (int)(i - row * upr) * 4;
+            const float4 v = *(const float4*)(zc + (size_t)row * 2 * Ch + t0);
+            const float* e = ez + (t0 >> 5) * 64 + (t0 & 31);
+            s -= (double)v.x * (double)e[0] + (double)v.y * (double)e[1] + (double)v.z * (double)e[2] + (double)v.w * (double)e[3];
+        }
+    } else if (Ch == 2 && ((uintptr_t)zc & 15) == 0) {
+        const double e0 = ez[0], e1 = ez[1];
+        for (long i = first; i < keep; i += stride) {
+            const float4 v = *(const float4*)(zc + (size_t)i * 4);                    // log_s 0, log_s 1, t 0, t 1
+            s -= (double)v.x * e0 + (double)v.y * e1;
+        }
+    } else if (Ch == 1 && ((uintptr_t)zc & 7) == 0) {
+        const double e0 = ez[0];
+        const long head = (((uintptr_t)zc & 15) != 0 && keep > 0) ? 1 : 0;            // an odd first row
+        const float* zp = zc + head * 2;
+        const long left = keep - head;
+        for (long i = first; i < (left >> 1); i += stride) {
+            const float4 v = *(const float4*)(zp + (size_t)i * 4);                    // two rows of (log_s, t)
+            s -= (double)v.x * e0 + (double)v.z * e0;
+        }
+        if (first == 0) {
+            if (head) s -= (double)zc[0] * e0;
+            if (left & 1) s -= (double)zp[(size_t)(left - 1) * 2] * e0;
+        }
+    } else {
+        const long n = keep * Ch;
+        for (long i = first; i < n; i += stride) {
+            const long row = i / Ch;
+            const int tau = (int)(i - row * Ch);
+            s -= (double)zc[(size_t)row * 2 * Ch + tau] * (double)ez_of(ez, tau);
+        }
+    }
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int st = 128; st > 0; st >>= 1) {
+        if (threadIdx.x < st) red[threadIdx.x] += red[threadIdx.x + st];
+        __syncthreads();
+    }
+    double* out = acc + (size_t)c * nslot;
+    if (threadIdx.x == 0) out[blockIdx.x] = red[0];
+    if (an && blockIdx.x == 0) {
+        double a = 0.0;
+        for (int tau = threadIdx.x; tau < Ch; tau += 256) a += (double)an[3 * Ch + tau] + (double)an[7 * Ch + tau];
+        __syncthreads();
+        red[threadIdx.x] = a;
+        __syncthreads();
+        for (int st = 128; st > 0; st >>= 1) {
+            if (threadIdx.x < st) red[threadIdx.x] += red[threadIdx.x + st];
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) out[nslot - 1] = red[0];
+    }
+}
+
+// One workgroup per window c of a group: its four partial sums -> out[slot[c]][0 .. 4) fp64 (a negative slot writes nothing):
+//   [0] sum of z^2 over the core's elements [off / 2, (off + len) / 2) of both final planes [2][n][L / 2] (off = core_off[c]
+//       clamped to [0, L], len = core_len[c] to [0, L - off]; nothing outside is loaded),
+//   [1] sum over the flows, in flow order, of their chunk sums of -log_s (acc [nflows][n][nslot], window_logdet_kernel's),
+//   [2] sum over the flows of their ActNorm terms, sum_tau(3 logs) / (2 Ch) - the same for every window,
+//   [3] len, the number of samples these sums cover.
+// fp64 throughout, in an order the launch fixes: no atomics.
+__global__ __launch_bounds__(256) void window_sums_kernel(const float* __restrict__ planes, long n, long L,
+                                                          const int* __restrict__ core_off, const int* __restrict__ core_len,
+                                                          const double* __restrict__ acc, int nflows, int n_flow, int nslot,
+                                                          const int* __restrict__ slot, double* __restrict__ out) {
+    __shared__ double r1[256], r2[256];
+    const long c = blockIdx.x, hL = L >> 1;
+    long off = core_off[c], len = core_len[c];
+    off = off < 0 ? 0 : (off > L ? L : off);
+    len = len < 0 ? 0 : (len > L - off ? L - off : len);
+    const long e0 = off >> 1, e1 = (off + len) >> 1;
+    double s = 0.0, ld = 0.0, an = 0.0;
+    for (int q = 0; q < 2; ++q) {
+        const float* z = planes + ((size_t)q * n + c) * hL;
+        long a0 = e0 + (long)(((16 - ((uintptr_t)(z + e0) & 15)) & 15) >> 2);         // the first 16-byte boundary inside the core
+        if (a0 > e1) a0 = e1;
+        const long a1 = a0 + ((e1 - a0) & ~3L);
+        for (long k = threadIdx.x; k < ((a1 - a0) >> 2); k += 256) {
+            const float4 v = *(const float4*)(z + a0 + k * 4);
+            s += (double)v.x * v.x + (double)v.y * v.y + (double)v.z * v.z + (double)v.w * v.w;
+        }
+        const long nside = (a0 - e0) + (e1 - a1);                                      // head [e0, a0) and tail [a1, e1)
+        for (long j = threadIdx.x; j < nside; j += 256) {
+            const long i = j < a0 - e0 ? e0 + j : a1 + (j - (a0 - e0));
+            s += (double)z[i] * z[i];
+        }
+    }
+    for (int f = 0; f < nflows; ++f) {
+        const double* a = acc + ((size_t)f * n + c) * nslot;
+        for (int k = threadIdx.x; k < nslot - 1; k += 256) ld += a[k];
+        if (threadIdx.x == 0) an += a[nslot - 1] / (double)(2 << (f / n_flow));
+    }
+    r1[threadIdx.x] = s;
+    r2[threadIdx.x] = ld;
+    __syncthreads();
+    for (int st = 128; st > 0; st >>= 1) {
+        if (threadIdx.x < st) { r1[threadIdx.x] += r1[threadIdx.x + st]; r2[threadIdx.x] += r2[threadIdx.x + st]; }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0 && slot[c] >= 0) {
+        double* o = out + (size_t)slot[c] * 4;
+        o[0] = r1[0]; o[1] = r2[0]; o[2] = an; o[3] = (double)len;
+    }
+}
+
+// The cores of a group's latent in TIME order: sample s of window c lives in plane (s & 1) ^ swapped at element s / 2 (the
+// planes hold the even and the odd samples; every flow exchanges them, so after an odd number of flows they are swapped -
+// z_planes_to_squeezed followed by n_block un-squeezes is exactly this), and z[out_off[c] + i] = sample core_off[c] + i for
+// i < core_len[c], the core clamped into the window as above.  A lane takes a pair of samples - one element of either
+// plane, one 8-byte store where the core starts on an even sample and the destination is 8-byte aligned, single samples
+// otherwise.  Nothing outside [out_off, out_off + core_len) is written.
+__global__ __launch_bounds__(256) void window_latent_kernel(const float* __restrict__ planes, long n, long L, int swapped,
+                                                            const int* __restrict__ core_off, const int* __restrict__ core_len,
+                                                            const long long* __restrict__ out_off, float* __restrict__ z) {
+    const long c = blockIdx.y, hL = L >> 1;
+    long off = core_off[c], len = core_len[c];
+    off = off < 0 ? 0 : (off > L ? L : off);
+    len = len < 0 ? 0 : (len > L - off ? L - off : len);
+    const float* even = planes + ((size_t)(swapped ? 1 : 0) * n + c) * hL;             // where the even samples are
+    const float* odd = planes + ((size_t)(swapped ? 0 : 1) * n + c) * hL;
+    float* zr = z + out_off[c];
+    const long first = (long)blockIdx.x * 256 + threadIdx.x, stride = (long)gridDim.x * 256;
+    if ((off & 1) == 0 && ((uintptr_t)zr & 7) == 0) {
+        const long e0 = off >> 1;
+        for (long k = first; k < (len >> 1); k += stride) *(float2*)(zr + 2 * k) = make_float2(even[e0 + k], odd[e0 + k]);
+        if ((len & 1) && first == 0) zr[len - 1] = even[e0 + (len >> 1)];
+    } else {
+        for (long i = first; i < len; i += stride) {
+            const long sidx = off + i;
+            zr[i] = ((sidx & 1) ? odd : even)[sidx >> 1];
+        }
+    }
+}
+
+// Per clip c: the partial sums of its windows, slots [slot0[c], slot0[c] + nwin[c]) of part [.][4] (window_sums_kernel), added
+// in window order by one lane - so the result depends on neither the grouping nor the order the groups ran in - and
+// out[0][c] = log_p = 0.5 (-log 2 pi - sum z^2 / t), out[1][c] = logdet = ActNorm term (the first window's) + sum(-log_s) / t,
+// t = the samples the windows cover.  fwn_model_forward_ragged's layout of out2B.
+__global__ __launch_bounds__(64) void windows_finish_kernel(const double* __restrict__ part, const int* __restrict__ slot0,
+                                                            const int* __restrict__ nwin, long nclip, float* __restrict__ out) {
+    const long c = (long)blockIdx.x * 64 + threadIdx.x;
+    if (c >= nclip) return;
+    const long s0 = slot0[c] < 0 ? 0 : slot0[c], nw = nwin[c] < 0 ? 0 : nwin[c];
+    double z2 = 0.0, ls = 0.0, t = 0.0;
+    for (long k = 0; k < nw; ++k) {
+        const double* p = part + (size_t)(s0 + k) * 4;
+        z2 += p[0]; ls += p[1]; t += p[3];
+    }
+    const double an = nw > 0 ? part[(size_t)s0 * 4 + 2] : 0.0, inv = 1.0 / (t > 0.0 ? t : 1.0);
+    out[c] = (float)(0.5 * (-1.8378770664093453 - z2 * inv));
+    out[nclip + c] = (float)(an + ls * inv);
+}
+
 // ---- ActNorm data-dependent init for one flow -----------------------------------------------
-// One workgroup per (plane role, channel).  an[role][0..3][tau] = shift b, scale exp(3 logs),
+// One workgroup per (plane role, channel). an[role][0..3][tau] = shift b, scale exp(3 logs),
 // inverse scale, 3*logs.  model.py:55-56 (b = -mean), :65-71 (logs from mean((x+b)^2)).
 __device__ double block_sum(double v, double* red) {
     const int tid = threadIdx.x;
@@ -1310,6 +1486,29 @@ void fwn_launch_ragged_finish(const float* planes, long nclip, long T, const dou
                               float* out2B, hipStream_t st) {
     hipLaunchKernelGGL(ragged_finish_kernel, dim3((unsigned)nclip), dim3(256), 0, st, planes, nclip, T, acc, nflows, n_flow,
                        fwn_ragged_logdet_nslot(nclip), len, out2B);
+}
+// windowed forward: fwn_launch_ragged_logdet's grid (the same chunks and slots) for the core-restricted sums, one workgroup per
+// window for its partial sums, window_scatter's grid for the latent, one lane per clip for the finish
+void fwn_launch_window_logdet(const float* Z, long n, long rows, int Ch, const float* ez, const float* an, const int* core_off,
+                              const int* core_len, int samples_per_row, double* acc, hipStream_t st) {
+    const int nslot = fwn_ragged_logdet_nslot(n);
+    hipLaunchKernelGGL(window_logdet_kernel, dim3((unsigned)(nslot - 1), (unsigned)n), dim3(256), 0, st, Z, rows, Ch, ez, an, core_off,
+                       core_len, samples_per_row, acc, nslot);
+}
+void fwn_launch_window_sums(const float* planes, long n, long L, const int* core_off, const int* core_len, const double* acc,
+                            int nflows, int n_flow, const int* slot, double* out, hipStream_t st) {
+    hipLaunchKernelGGL(window_sums_kernel, dim3((unsigned)n), dim3(256), 0, st, planes, n, L, core_off, core_len, acc, nflows, n_flow,
+                       fwn_ragged_logdet_nslot(n), slot, out);
+}
+void fwn_launch_window_latent(const float* planes, long n, long L, int swapped, const int* core_off, const int* core_len,
+                              const long long* out_off, float* z, hipStream_t st) {
+    const long want = (L * 4 + 16383) / 16384, cap = n < 2048 ? 2048 / n : 1;
+    const long gx = want < 1 ? 1 : (want > cap ? cap : want);
+    hipLaunchKernelGGL(window_latent_kernel, dim3((unsigned)gx, (unsigned)n), dim3(256), 0, st, planes, n, L, swapped, core_off, core_len,
+                       out_off, z);
+}
+void fwn_launch_windows_finish(const double* part, const int* slot0, const int* nwin, long nclip, float* out2B, hipStream_t st) {
+    hipLaunchKernelGGL(windows_finish_kernel, dim3((unsigned)((nclip + 63) / 64)), dim3(64), 0, st, part, slot0, nwin, nclip, out2B);
 }
 void fwn_launch_ddi_moments(const float* xa, const float* xb, int M, int Ch, double* mom, hipStream_t st) {
     hipLaunchKernelGGL(ddi_moments_kernel, dim3(2 * Ch), dim3(256), 0, st, xa, xb, M, Ch, mom);

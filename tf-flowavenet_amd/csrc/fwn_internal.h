@@ -191,6 +191,19 @@ void fwn_launch_ragged_logdet(const float* Z, long nclip, long rows, int Ch, con
                               int nlen, int samples_per_row, double* acc, hipStream_t st);
 void fwn_launch_ragged_finish(const float* planes, long nclip, long T, const double* acc, int nflows, int n_flow, const int* len,
                               float* out2B, hipStream_t st);
+// windowed forward (aux_kernels.hip; fwn.h has the contracts).  fwn_launch_window_logdet: fwn_launch_ragged_logdet over rows
+// [core_off[c] / samples_per_row, + core_len[c] / samples_per_row) of window c, the same slots.  fwn_launch_window_sums: window
+// c's partial sums (z^2 over its core of the final planes [2][n][L / 2], -log_s and the ActNorm terms over acc
+// [nflows][n][nslot], the core's length) -> out[slot[c]][0 .. 4) fp64.  fwn_launch_window_latent: the cores of the planes in
+// time order -> z + out_off[c] (swapped: n_block * n_flow is odd).  fwn_launch_windows_finish: per clip, its windows' sums
+// part[slot0[c] .. slot0[c] + nwin[c])[4] in window order -> out2B [2][nclip].  Every table is read and clamped on the device.
+void fwn_launch_window_logdet(const float* Z, long n, long rows, int Ch, const float* ez, const float* an, const int* core_off,
+                              const int* core_len, int samples_per_row, double* acc, hipStream_t st);
+void fwn_launch_window_sums(const float* planes, long n, long L, const int* core_off, const int* core_len, const double* acc,
+                            int nflows, int n_flow, const int* slot, double* out, hipStream_t st);
+void fwn_launch_window_latent(const float* planes, long n, long L, int swapped, const int* core_off, const int* core_len,
+                              const long long* out_off, float* z, hipStream_t st);
+void fwn_launch_windows_finish(const double* part, const int* slot0, const int* nwin, long nclip, float* out2B, hipStream_t st);
 void fwn_launch_ddi(const float* xa, const float* xb, int M, int Ch, float* an, hipStream_t st);
 void fwn_launch_ddi_moments(const float* xa, const float* xb, int M, int Ch, double* mom, hipStream_t st);
 void fwn_launch_ddi_from_moments(const double* mom, int Ch, float* an, hipStream_t st);

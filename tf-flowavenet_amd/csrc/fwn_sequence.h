@@ -30,6 +30,7 @@ enum PassKind {
     PASS_INIT_RAGGED,        // fwn_model_forward_init_ragged
     PASS_TRAIN,              // fwn_train_loss_and_grads
     PASS_TRAIN_RAGGED,       // fwn_train_loss_and_grads_ragged
+    PASS_FORWARD_WINDOWS,    // fwn_model_forward_windows: the ragged forward's form on full-length windows (no lengths: no fills)
 };
 struct PassTraits {
     const char* what;        // the entry point's name in error messages
@@ -51,6 +52,7 @@ inline PassTraits pass_traits(PassKind k) {
     case PASS_INIT_RAGGED:    return {"fwn_model_forward_init_ragged", false, 2, true, true, true};
     case PASS_TRAIN:          return {"fwn_train_loss_and_grads", false, 0, false, false, false};
     case PASS_TRAIN_RAGGED:   return {"fwn_train_loss_and_grads_ragged", false, 0, true, true, false};
+    case PASS_FORWARD_WINDOWS: return {"fwn_model_forward_windows", false, 0, true, true, false};
     default:                  return {"fwn_model_forward", false, 0, false, false, false};
     }
 }

@@ -407,15 +407,17 @@ class FloWaveNet:
 
     # ------------------------------------------------------------------ windowed synthesis
     def _window_workspace(self, kind, n, length):
-        """Scratch of one group of ``n`` windows of ``length`` samples (``kind``: "reverse" - the plain inverse pass's - or
-        "synth" - with z, the waveform and the windows' mel rows behind it).  A cache of its own, keyed by shape and stream: a
+        """Scratch of one group of ``n`` windows of ``length`` samples (``kind``: "reverse" - the plain inverse pass's -,
+        "synth" - with z, the waveform and the windows' mel rows behind it - or "forward" - the windowed forward pass's, with
+        every tail's ZeroConv output, the per-window sums and the windows' audio and mel rows).  A cache of its own, keyed by shape and stream: a
         long clip alternates between a few shapes (first, middle, end windows) and ``_workspace`` keeps one shape only.  The
         eight most recently used are kept; a size depends on (n, length) alone, never on a clip's length."""
         import torch
         key = (kind, n, length, self._stream())
         ws = self._wws.pop(key, None)
         if ws is None:
-            name = "fwn_synthesize_windows_workspace_bytes" if kind == "synth" else "fwn_workspace_bytes"
+            name = {"synth": "fwn_synthesize_windows_workspace_bytes", "forward": "fwn_forward_windows_workspace_bytes"}.get(
+                kind, "fwn_workspace_bytes")
             nbytes = getattr(self._lib, name)(C.byref(self._packed.model_desc), n, length)
             if nbytes == 0:
                 _lib.check(-1, name)
@@ -526,6 +528,93 @@ class FloWaveNet:
             raise RuntimeError("no parameters loaded: call load_params() / init_synthetic() first")
         return SynthesisStream(self, seed, clip_id, window, temp, halo)
 
+    # ------------------------------------------------------------------ windowed forward
+    def _default_window(self):
+        from . import windowing
+        unit = windowing.unit_samples(self._hparams)
+        return -(-65536 // unit) * unit
+
+    def _check_windowed_forward(self):
+        if self._packed is None:
+            raise RuntimeError("no parameters loaded: call load_params() / init_synthetic() first")
+        if self._gate_fp8:
+            raise ValueError("a gate_fp8 model takes no windows: the windowed forward runs the ragged forward's form of the pass")
+        if self._init:
+            raise ValueError("init=True takes no windows: the data-dependent ActNorm init needs the moments of the whole batch")
+
+    def _forward_windows_call(self, x_flat, mel_flat, rows, length, acc, z_flat):
+        """One ``fwn_model_forward_windows`` group.  rows: per window ``(x_row, mel_row, core_off, core_len, slot, z_off)`` - the
+        window's audio starts at row ``x_row`` of ``x_flat`` (rows of hop samples), its mel at row ``mel_row`` of ``mel_flat``;
+        the sums over ``core_len`` samples from ``core_off`` go to ``acc[slot]``, and that core of the latent, in time order, to
+        element ``z_off`` of ``z_flat`` (None: no latent).  The six tables go up as one buffer, the int64 ones first."""
+        import torch
+        n = len(rows)
+        t64 = np.asarray([[r[0] for r in rows], [r[1] for r in rows], [r[5] for r in rows]], dtype=np.int64)
+        t32 = np.asarray([[r[2] for r in rows], [r[3] for r in rows], [r[4] for r in rows]], dtype=np.int32)
+        tab = torch.from_numpy(np.concatenate([t64.reshape(-1).view(np.uint8), t32.reshape(-1).view(np.uint8)])).to(self._device)
+        p64, p32 = tab.data_ptr(), tab.data_ptr() + 24 * n
+        assert p64 % 8 == 0
+        wsp, wsn = self._window_workspace("forward", n, length)
+        rc = self._lib.fwn_model_forward_windows(C.byref(self._packed.model_desc), n, length, x_flat.data_ptr(), p64,
+                                                 mel_flat.data_ptr(), p64 + 8 * n, p32, p32 + 4 * n, p32 + 8 * n, acc.data_ptr(),
+                                                 p64 + 16 * n, None if z_flat is None else z_flat.data_ptr(), wsp, wsn,
+                                                 self._stream())
+        _lib.check(rc, "fwn_model_forward_windows")
+
+    def _forward_windows_finish(self, acc, slot0, nwin):
+        """``fwn_forward_windows_finish``: clip c's windows are slots ``slot0[c] .. slot0[c] + nwin[c]`` of ``acc`` -> fp32 [2, B]."""
+        import torch
+        b = len(slot0)
+        tab = torch.from_numpy(np.asarray([slot0, nwin], dtype=np.int32)).to(self._device)
+        out = torch.empty(2, b, dtype=torch.float32, device=self._device)
+        rc = self._lib.fwn_forward_windows_finish(acc.data_ptr(), tab.data_ptr(), tab.data_ptr() + 4 * b, b, out.data_ptr(),
+                                                  self._stream())
+        _lib.check(rc, "fwn_forward_windows_finish")
+        return out
+
+    def forward_windowed(self, x, c, window=None, batch=8, return_z=False, halo=None, g=None):
+        """``forward(x, c)`` of clips of any length, window by window: x [B,T,1], c [B,T/hop,num_mels] -> ``(log_p [B], logdet
+        [B])`` fp32, entry b what ``forward`` gives for clip b alone (to rounding); T a multiple of lcm(hop_size, 2^n_block), at
+        most 2^34.  The forward pass has the inverse pass's receptive field, so the clips are cut as for synthesis -
+        ``windowing.plan_windows(T, window, hparams, halo)``, ``window`` in samples (default: ``synthesize_windowed``'s) - and
+        windows of equal length, of all clips, share a ``fwn_model_forward_windows`` call, ``batch`` at a time: audio and mel
+        rows gathered on the device, the rectangular pass, and the fp64 sums of z^2 and -log_s over each window's CORE only
+        (a window's own scalars would include its halo).  One more launch adds every clip's windows in window order: the
+        result depends on neither ``batch`` nor the order of the calls, and two identical calls give identical bits.
+        ``return_z`` adds z [B,T,1] fp32 in TIME order - the latent ``reverse`` / ``reverse_windowed(z, c, window)`` take and
+        invert.  No ceiling on T other than memory for x, c and z; the scratch depends on (batch, window) alone.  ``halo`` (0
+        = hard cuts) is for experiments.  ``init=True`` and ``gate_fp8`` models raise ``ValueError``."""
+        import torch
+        from . import windowing
+        self._check_g(g)
+        self._check_windowed_forward()
+        b, t, x32, c32 = self._prep(x, c, "x")
+        if t > (1 << 34):
+            raise ValueError("T=%d exceeds 2^34 samples per clip" % t)
+        if window is None:
+            window = self._default_window()
+        plan = windowing.plan_windows(t, window, self._hparams, halo)
+        plans, nwin, frames = [plan] * b, len(plan), t // self.hop
+        acc = torch.zeros(b * nwin, 4, dtype=torch.float64, device=self._device)
+        z = torch.empty(b, t, 1, dtype=torch.float32, device=self._device) if return_z else None
+        for group in windowing.group_windows(plans, batch, self._hparams):
+            rows, length = [], None
+            for clip, k in group:
+                lo, hi, a, e = plans[clip][k]
+                length = hi - lo
+                rows.append((clip * frames + lo // self.hop, clip * frames + lo // self.hop, a - lo, e - a, clip * nwin + k,
+                             clip * t + a))
+            self._forward_windows_call(x32, c32, rows, length, acc, z)
+        out = self._forward_windows_finish(acc, [clip * nwin for clip in range(b)], [nwin] * b)
+        return (out[0], out[1], z) if return_z else (out[0], out[1])
+
+    def forward_stream(self, window=None, halo=None, return_z=True):
+        """The likelihood and the latent of one clip that is still arriving: -> a ``ForwardStream`` with ``push(x_samples,
+        c_frames)`` and ``finish()``.  Fed the clip in any split, the concatenated z cores and the scalars are
+        ``forward_windowed(x, c, window, batch=1, return_z=True)`` bit for bit (the same windows, one call each)."""
+        self._check_windowed_forward()
+        return ForwardStream(self, window, halo, return_z)
+
     def upsample(self, c):
         """c [B,F,num_mels] -> [B,F*hop,num_mels] fp32 (model.py:398-404)."""
         import torch
@@ -613,6 +702,98 @@ class SynthesisStream:
 
     def finish(self):
         return self._run(self._plan.finish())
+
+
+class ForwardStream:
+    """``FloWaveNet.forward_stream``: log_p, logdet and the time-ordered latent of one clip while it is still arriving - the twin
+    of ``SynthesisStream`` over the same ``windowing.StreamPlanner``.  ``push(x_samples, c_frames)`` takes f * hop samples (any
+    shape holding that many) and their f mel frames [f, num_mels] (tensors or arrays, any f >= 0) and returns the z of the cores
+    that became computable, one fp32 tensor on the device, possibly empty (always empty without ``return_z``); ``finish()``
+    returns ``(z_rest, log_p, logdet)``, the scalars fp32 0-dim tensors (``ValueError`` if the frame total is no multiple of
+    lcm(hop_size, 2^n_block) / hop_size, or nothing was pushed).  One ``fwn_model_forward_windows`` call per window; window k's
+    sums wait in slot k of a device table until ``finish`` adds them in window order.  The object keeps only the audio and mel
+    a later window still needs - at most (window + 2 H) / hop frames plus one push."""
+
+    def __init__(self, model, window=None, halo=None, return_z=True):
+        from . import windowing
+        self._model = model
+        self._plan = windowing.StreamPlanner(model._hparams, model._default_window() if window is None else window, halo)
+        self._return_z = bool(return_z)
+        self._x = None               # device [capacity, hop]: the audio of frames _base .. _base + _n of the clip
+        self._c = None               # device [capacity, num_mels]: those frames
+        self._base = 0
+        self._n = 0
+        self._acc = None             # device [capacity, 4] fp64: window k's partial sums in row k
+        self._k = 0                  # windows run
+
+    @property
+    def retained_frames(self):
+        return self._n
+
+    @staticmethod
+    def _grown(buf, used, need, like):
+        """``buf`` with room for ``need`` rows (doubling), its first ``used`` rows kept; ``like``: a tensor of the row's shape and dtype."""
+        import torch
+        if buf is not None and need <= buf.shape[0]:
+            return buf
+        grown = torch.empty((max(need, 2 * (0 if buf is None else buf.shape[0])),) + tuple(like.shape[1:]), dtype=like.dtype,
+                            device=like.device)
+        if used:
+            grown[:used] = buf[:used]
+        return grown
+
+    def _append(self, x_samples, c_frames):
+        import torch
+        m = self._model
+        dev = torch.device(m._device)
+        f = torch.as_tensor(c_frames).to(device=dev, dtype=torch.float32)
+        if f.dim() != 2 or f.shape[1] != m._hparams.num_mels:
+            raise ValueError("c_frames must have shape [f, %d], got %r" % (m._hparams.num_mels, tuple(f.shape)))
+        xs = torch.as_tensor(x_samples).to(device=dev, dtype=torch.float32).reshape(-1)
+        if xs.numel() != int(f.shape[0]) * m.hop:
+            raise ValueError("%d frames go with %d samples (hop_size=%d), got %d" % (f.shape[0], f.shape[0] * m.hop, m.hop, xs.numel()))
+        xs = xs.reshape(-1, m.hop)
+        need = self._n + int(f.shape[0])
+        self._x = self._grown(self._x, self._n, need, xs)
+        self._c = self._grown(self._c, self._n, need, f)
+        self._x[self._n:need] = xs
+        self._c[self._n:need] = f
+        self._n = need
+        return int(f.shape[0])
+
+    def _run(self, windows):
+        import torch
+        m = self._model
+        out = []
+        for lo, hi, a, e in windows:
+            z = torch.empty(e - a, dtype=torch.float32, device=m._device) if self._return_z else None
+            if self._acc is None or self._k == self._acc.shape[0]:
+                self._acc = self._grown(self._acc, self._k, self._k + 1, torch.empty(1, 4, dtype=torch.float64, device=m._device))
+            row = lo // m.hop - self._base
+            m._forward_windows_call(self._x, self._c, [(row, row, a - lo, e - a, self._k, 0)], hi - lo, self._acc, z)
+            self._k += 1
+            if z is not None:
+                out.append(z)
+        drop = self._plan.first_frame - self._base      # frames no later window reads
+        if drop > 0:
+            drop = min(drop, self._n)
+            for buf in (self._x, self._c):
+                buf[:self._n - drop] = buf[drop:self._n].clone()
+            self._base += drop
+            self._n -= drop
+        if not out:
+            return torch.empty(0, dtype=torch.float32, device=m._device)
+        return out[0] if len(out) == 1 else torch.cat(out)
+
+    def push(self, x_samples, c_frames):
+        return self._run(self._plan.push(self._append(x_samples, c_frames)))
+
+    def finish(self):
+        z = self._run(self._plan.finish())
+        if not self._k:
+            raise ValueError("finish: nothing was pushed")
+        out = self._model._forward_windows_finish(self._acc, [0], [self._k])
+        return z, out[0, 0], out[1, 0]
 
 
 def check_lengths(lengths, b, t, hop, n_block):

@@ -10,6 +10,12 @@ largest number of frames whose samples divide by 2^n_block (model.py:226); one s
 
 Each line of ``--out``: ``{"name": <audio file>, "samples": <samples scored>, "log_p": .., "logdet": .., "nll": -(log_p + logdet)}``
 (nats per sample, train.py:56-60), in the order of ``train.txt``.
+
+``--window SAMPLES`` (opt-in) scores every utterance longer than that through ``FloWaveNet.forward_windowed`` - window by
+window with the network's receptive field of real context on both sides, the sums taken over the cores only - so no utterance
+is too long for one call any more.  The other utterances keep their calls: the plan is made as without the flag (over
+everything one call can address), a group of long utterances only is skipped, and a group that mixes both runs as it would
+have - its short members' records are bit for bit those of a run without the flag, its long members' come from the windows.
 """
 from __future__ import annotations
 
@@ -19,7 +25,7 @@ import os
 
 import numpy as np
 
-from .synthesize import load_checkpoint, plan_batches
+from .synthesize import load_checkpoint, max_clips_per_call, plan_batches, window_samples
 
 
 def read_metadata(base_dir):
@@ -47,6 +53,17 @@ def plan(frame_counts, batch, max_pad_frac, hparams):
     return kept, groups
 
 
+def windowed_plan(frame_counts, window, hparams):
+    """``--window``: (long, planned) - the indices of the utterances whose cropped length exceeds ``window`` samples, and the
+    frame counts the ordinary plan is made over: as given, but 0 for a long utterance that exceeds what one call can address
+    (without the flag the plan would refuse it; every other utterance is planned as without the flag).  Pure host code."""
+    hop = hparams.hop_size
+    long_ones = {k for k, f in enumerate(frame_counts) if cropped_frames(f, hparams) * hop > int(window)}
+    planned = [0 if k in long_ones and max_clips_per_call(hparams, cropped_frames(f, hparams) * hop) < 1 else f
+               for k, f in enumerate(frame_counts)]
+    return long_ones, planned
+
+
 def score(args, hparams, model=None):
     import torch
     from .model import FloWaveNet
@@ -57,11 +74,25 @@ def score(args, hparams, model=None):
     audios = [np.load(os.path.join(args.base_dir, "audios", a)).astype(np.float32).reshape(-1) for a, _ in meta]
     mels = [np.load(os.path.join(args.base_dir, "mels", m)).astype(np.float32) for _, m in meta]
     frames = [min(mel.shape[0], len(au) // hop) for au, mel in zip(audios, mels)]
-    kept, groups = plan(frames, int(args.batch), float(args.max_pad_frac), hparams)
-    for k in sorted(set(range(len(meta))) - set(kept)):
+    # --window: the utterances longer than it are scored window by window; the plan is made over what it is made without the flag
+    long_ones, planned, window = set(), frames, None
+    if getattr(args, "window", None) is not None:
+        window = window_samples(args.window, hparams)
+        long_ones, planned = windowed_plan(frames, window, hparams)
+    kept, groups = plan(planned, int(args.batch), float(args.max_pad_frac), hparams)
+    for k in sorted(set(range(len(meta))) - set(kept) - long_ones):
         print("Skipping {}: {} frames are fewer than the model's alignment".format(meta[k][0], frames[k]))
     records = {}
+    for k in sorted(long_ones):
+        f = cropped_frames(frames[k], hparams)
+        x = torch.from_numpy(audios[k][None, :f * hop, None]).cuda()
+        c = torch.from_numpy(mels[k][None, :f]).cuda()
+        log_p, logdet = model.forward_windowed(x, c, window=window, batch=int(args.batch))
+        lp, ld = float(log_p[0]), float(logdet[0])
+        records[k] = {"name": meta[k][0], "samples": f * hop, "log_p": lp, "logdet": ld, "nll": -(lp + ld)}
     for group in groups:
+        if all(kept[g] in long_ones for g in group):
+            continue                                 # (never without --window: long_ones is empty)
         own = [cropped_frames(frames[kept[g]], hparams) for g in group]
         top = max(own)
         x = np.zeros((len(group), top * hop, 1), dtype=np.float32)
@@ -72,6 +103,8 @@ def score(args, hparams, model=None):
         log_p, logdet = model.forward(torch.from_numpy(x).cuda(), torch.from_numpy(c).cuda(), lengths=[f * hop for f in own])
         log_p, logdet = log_p.cpu().numpy(), logdet.cpu().numpy()
         for row, (g, f) in enumerate(zip(group, own)):
+            if kept[g] in long_ones:
+                continue                             # its record is the windowed one
             lp, ld = float(log_p[row]), float(logdet[row])
             records[kept[g]] = {"name": meta[kept[g]][0], "samples": f * hop, "log_p": lp, "logdet": ld, "nll": -(lp + ld)}
     out = [records[k] for k in sorted(records)]
@@ -90,6 +123,9 @@ def main(argv=None):
     parser.add_argument("--batch", type=int, default=8, help="utterances per launch (of similar length)")
     parser.add_argument("--max_pad_frac", type=float, default=0.25,
                         help="the largest share of a launch's samples that may be padding (synthesize.plan_batches)")
+    # absent from the namespace unless given: without the flag nothing changes
+    parser.add_argument("--window", type=int, default=argparse.SUPPRESS,
+                        help="score utterances longer than this many samples window by window (FloWaveNet.forward_windowed)")
     args = parser.parse_args(argv)
     score(args, hparams)
 
