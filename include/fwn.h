@@ -798,7 +798,8 @@ int fwn_model_synthesize_windows(const fwn_model_desc* m, int64_t n, int64_t L, 
  * of -Z[row][c] ez(c) over rows [core_off[r] / samples_per_row, + core_len[r] / samples_per_row) -> acc[r][0 .. nslot - 1), the
  * ActNorm term (an may be NULL) -> acc[r][nslot - 1], nslot = fwn_ragged_logdet_slots(n).  The start is clamped to [0, rows] and
  * the count to what is left, on the device; no row outside the range is loaded.  core_off_dev / core_len_dev: DEVICE int32 [n],
- * samples.  fwn_ragged_logdet_rows itself is unchanged.
+ * samples.  One kernel serves both entries: fwn_ragged_logdet_rows(len) is the start-0 case, the same sums in the same order as
+ * fwn_window_logdet_rows(core_off = 0, core_len = len) leaves.
  *
  * fwn_window_sums: window r's partial sums -> part[slot[r]][0 .. 4) fp64 (a negative slot writes nothing): [0] the sum of z^2
  * over elements [core_off / 2, (core_off + core_len) / 2) of both final planes [2][n][L / 2] (one contiguous range per plane;

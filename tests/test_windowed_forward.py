@@ -20,6 +20,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import test_windowed_host as H  # noqa: E402
 import windowed_forward_ref as R  # noqa: E402
+from test_windowed import _i32, _i64, dev  # noqa: E402
 
 from oracle import flowavenet_np as onp  # noqa: E402
 from tf_flowavenet_amd import _lib  # noqa: E402
@@ -36,18 +37,6 @@ ABS_LOGDET = 1e-3
 ABS_Z = 2e-2
 ABS_WAV = 1e-2
 Z_MEAN, Z_P9999, Z_MAX = 2.5e-3, 1.5e-2, 2.5e-2     # tests/test_gpu_parity.py's full-size latent statistics
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def _i64(vals):
-    return torch.tensor(list(vals), dtype=torch.int64).cuda()
-
-
-def _i32(vals):
-    return torch.tensor(list(vals), dtype=torch.int32).cuda()
 
 
 def check_scalars(log_p, logdet, lp0, ld0):
@@ -116,6 +105,55 @@ def test_window_logdet_kernel_alone():
     _logdet_case(lib, 3000, 64, [(1, 2999), (1500, 1499)])
     for ch in (1, 2, 4):                                                       # a base that is not 16-byte aligned
         _logdet_case(lib, 41, ch, [(0, 41), (7, 9), (40, 1), (3, 0)], offset=1)
+
+
+def _both_entries_case(lib, nclip, rows, ch, lens):
+    """``fwn_ragged_logdet_rows(lens)`` and ``fwn_window_logdet_rows(core_off = 0, core_len = lens)`` on the same Z, NaN past each
+    clip's rows (and in the t half of every row): finite accumulators show that nothing outside the range was loaded, equal
+    ones that the two entries add the same terms in the same order."""
+    spr = 2 * ch
+    rng = np.random.default_rng(rows * 19 + ch)
+    z = rng.standard_normal((nclip, rows, 2 * ch)).astype(np.float32)
+    z[:, :, ch:] = np.nan
+    for k, n in enumerate(lens):
+        z[k, min(max(n, 0) // spr, rows):] = np.nan
+    ez = dev(rng.uniform(0.5, 2.0, size=max(1, ch // 32) * 64).astype(np.float32))
+    an = dev(rng.standard_normal((2, 4, ch)).astype(np.float32))
+    zd = dev(np.concatenate([z.reshape(-1), np.full(64, np.nan, dtype=np.float32)]))
+    assert zd.data_ptr() % 16 == 0
+    nslot = lib.fwn_ragged_logdet_slots(nclip)
+    len_d, zero_d = _i32(lens), _i32([0] * nclip)
+    got = []
+    for start in (None, zero_d.data_ptr()):
+        acc = torch.full((nclip, nslot), float("nan"), dtype=torch.float64, device="cuda")
+        if start is None:
+            rc = lib.fwn_ragged_logdet_rows(zd.data_ptr(), nclip, rows, ch, ez.data_ptr(), an.data_ptr(), len_d.data_ptr(), spr,
+                                            acc.data_ptr(), None)
+        else:
+            rc = lib.fwn_window_logdet_rows(zd.data_ptr(), nclip, rows, ch, ez.data_ptr(), an.data_ptr(), start, len_d.data_ptr(), spr,
+                                            acc.data_ptr(), None)
+        assert rc == 0, lib.fwn_last_error()
+        got.append(acc.cpu().numpy())
+    assert np.isfinite(got[0]).all() and np.isfinite(got[1]).all(), (nclip, rows, ch, lens)
+    assert np.array_equal(got[0], got[1]), (nclip, rows, ch, lens)             # the ActNorm slot included
+
+
+def test_ragged_and_window_entries_leave_the_same_sums():
+    """The shapes of ``test_ragged_logdet_kernel_alone`` (tests/test_ragged_forward.py) from a 16-byte-aligned buffer: all four
+    load branches, several chunks per clip.  At Ch = 1 a row is 8 bytes and both row counts are odd, so in a batch every other
+    clip starts 8 bytes off; each of those clips therefore also goes through both entries alone, from the buffer's base."""
+    lib = _lib.load()
+    rows = 37
+    for ch in (1, 2, 4, 16, 128):
+        spr = 2 * ch
+        lens = [0, rows * spr, rows * spr + 1000, spr, (rows - 1) * spr, -5]
+        _both_entries_case(lib, 6, rows, ch, lens)
+        if ch == 1:
+            for n in lens:
+                _both_entries_case(lib, 1, rows, ch, [n])
+    _both_entries_case(lib, 3, 70001, 1, [2, 140002, 70000])                   # many chunks per clip, odd rows (Ch = 1 pairs rows)
+    for n in (2, 140002, 70000):
+        _both_entries_case(lib, 1, 70001, 1, [n])
 
 
 def _sums_case(lib, length, cores, slots, nflows, n_flow, offset=0):

@@ -231,6 +231,85 @@ def test_stream_planner():
         WIN.StreamPlanner(hp, 24)
 
 
+class _StreamModel:
+    """Stands in for FloWaveNet under ``SynthesisStream``: the device call writes each core's absolute sample indices into the
+    PCM buffer and records (absolute start, length, core); frame f of the mel holds f, so a window names the frames it was given."""
+
+    def __init__(self, hp):
+        self._hparams, self._device, self.hop = hp, "cpu", hp.hop_size
+        self.windows = []
+
+    @staticmethod
+    def _clip_id_values(clip_ids, b):
+        return [int(v) for v in clip_ids]
+
+    def _windows_call(self, mel_flat, rows, length, seed, temp, pcm_flat, wav_flat):
+        import torch
+        (clip_id, start, mel_row, core_off, core_len, out_off), = rows
+        assert clip_id == 7 and seed == 75 and temp == 0.5 and out_off == 0 and wav_flat is None
+        assert mel_row >= 0 and mel_row + length // self.hop <= mel_flat.shape[0]
+        frames = mel_flat[mel_row:mel_row + length // self.hop, 0]
+        assert np.array_equal(frames.numpy() * self.hop, np.arange(start, start + length, self.hop))   # the window's own frames
+        assert pcm_flat.numel() == core_len
+        pcm_flat[:] = torch.arange(start + core_off, start + core_off + core_len, dtype=torch.int16)
+        self.windows.append((start, length, core_off, core_len))
+
+
+def test_synthesis_stream_bookkeeping():
+    """The twin of tests/test_windowed_forward_host.py ``test_stream_bookkeeping``: the same clip, window and splits."""
+    import torch
+    from tf_flowavenet_amd.model import SynthesisStream
+    hp = small_hparams()                              # hop 16, unit 16, H 96
+    h, hop, window = WIN.halo_samples(hp), hp.hop_size, 64
+    frames = (2 * h + 5 * window + 16) // hop
+    t = frames * hop
+    c = (torch.arange(frames, dtype=torch.float32)[:, None]).repeat(1, hp.num_mels)
+    plan = WIN.plan_windows(t, window, hp)
+    for split in ([1] * frames, [7] * (frames // 7) + [frames % 7], [frames], [3, 0, 11] + [2] * ((frames - 14) // 2) + [(frames - 14) % 2]):
+        model = _StreamModel(hp)
+        ss = SynthesisStream(model, 75, 7, window, temp=0.5)
+        got, at = [], 0
+        for f in split:
+            got.append(ss.push(c[at:at + f]))
+            at += f
+            assert ss.retained_frames <= (window + 2 * h) // hop + max(split)
+        got.append(ss.finish())
+        assert all(g.dtype == torch.int16 for g in got)
+        assert torch.equal(torch.cat(got), torch.arange(t, dtype=torch.int16))       # every core once, in order, whatever the split
+        assert [(lo, hi - lo, a - lo, b - a) for lo, hi, a, b in plan] == model.windows
+    # frames of another width are refused; the total must be a multiple of the unit
+    ss = SynthesisStream(_StreamModel(hp), 75, 7, window, temp=0.5)
+    with pytest.raises(ValueError):
+        ss.push(c[:2, :3])
+    hp5 = small_hparams(n_block=5)                    # unit 32 = two frames
+    ss = SynthesisStream(_StreamModel(hp5), 75, 7, 64)
+    ss.push(c[:3])
+    with pytest.raises(ValueError):
+        ss.finish()
+
+
+def test_upload_tables():
+    """One buffer, the int64 columns first: every pointer aligned for its type, every column the values put in - negative
+    int32 and uint32 ids from 2^31 on alike."""
+    import ctypes
+    from tf_flowavenet_amd import windowed
+    for n in (1, 5):
+        cols64 = [[(1 << 40) + 3 * i for i in range(n)], [-(1 << 35) - i for i in range(n)], [i for i in range(n)]]
+        cols32 = [[-1 - i for i in range(n)], [(1 << 31) + 5 * i for i in range(n)], [(1 << 32) - 1 - i for i in range(n)],
+                  [-(1 << 31) + i for i in range(n)], [7 * i for i in range(n)]]
+        tab, p64, p32 = windowed.upload_tables(cols64, cols32, "cpu")
+        assert tab.numel() == n * (8 * len(cols64) + 4 * len(cols32)) and len(p64) == len(cols64) and len(p32) == len(cols32)
+        assert p64[0] == tab.data_ptr() and all(p % 8 == 0 for p in p64) and all(p % 4 == 0 for p in p32)
+        spans = sorted([(p, 8 * n) for p in p64] + [(p, 4 * n) for p in p32])
+        assert all(p + size <= q for (p, size), (q, _) in zip(spans, spans[1:]))            # no column overlaps another
+        assert spans[-1][0] + spans[-1][1] == tab.data_ptr() + tab.numel()
+        for p, col in zip(p64, cols64):
+            assert list((ctypes.c_int64 * n).from_address(p)) == col
+        for p, col in zip(p32, cols32):
+            assert list((ctypes.c_uint32 * n).from_address(p)) == [v % (1 << 32) for v in col]
+            assert [v for v in (ctypes.c_int32 * n).from_address(p)] == [(v + (1 << 31)) % (1 << 32) - (1 << 31) for v in col]
+
+
 def test_cli_window_flag(monkeypatch, tmp_path):
     from tf_flowavenet_amd.hparams import hparams
     seen = []

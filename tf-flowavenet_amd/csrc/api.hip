@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <string.h>
 #include <math.h>
+#include <initializer_list>
 
 #include "../../include/fwn.h"
 #include "fwn_internal.h"
@@ -34,6 +35,8 @@ static int check_launch(const char* what) {
 }
 #define REQUIRE(cond, ...) do { if (!(cond)) return fail(FWN_ERR_ARG, __VA_ARGS__); } while (0)
 #define ALIGNED16(p) ((((uintptr_t)(p)) & 15) == 0)
+#define ALIGNED8(p) ((((uintptr_t)(p)) & 7) == 0)
+#define ALIGNED4(p) ((((uintptr_t)(p)) & 3) == 0)
 
 // ---- the hoisted conditioning of one block (inference and training; each has its own hoisting rule) ----
 fwn_cond_plan fwn_plan_cond(bool hoist, int M, int nflow, int L, int cin, int kcpad, const void* stream) {
@@ -216,9 +219,9 @@ int fwn_ragged_logdet_rows(const float* Z, int64_t B, int64_t rows, int Ch, cons
                            int32_t samples_per_row, double* acc, void* stream) {
     REQUIRE(Z && ez && len && acc && B > 0 && B < 65536 && rows > 0 && samples_per_row > 0, "fwn_ragged_logdet_rows: bad argument");
     REQUIRE(Ch >= 1 && (Ch & (Ch - 1)) == 0, "fwn_ragged_logdet_rows: Ch=%d must be a power of two", Ch);
-    REQUIRE((((uintptr_t)Z) & 3) == 0 && (((uintptr_t)acc) & 7) == 0, "fwn_ragged_logdet_rows: misaligned buffer");
+    REQUIRE(ALIGNED4(Z) && ALIGNED8(acc), "fwn_ragged_logdet_rows: misaligned buffer");
     REQUIRE(rows <= ((int64_t)1 << 31) / samples_per_row, "fwn_ragged_logdet_rows: rows * samples_per_row exceeds 2^31");
-    fwn_launch_ragged_logdet(Z, (long)B, (long)rows, Ch, ez, an, len, (int)B, samples_per_row, acc, (hipStream_t)stream);
+    fwn_launch_range_logdet(Z, (long)B, (long)rows, Ch, ez, an, nullptr, len, (int)B, samples_per_row, acc, (hipStream_t)stream);
     return check_launch("fwn_ragged_logdet_rows");
 }
 
@@ -562,14 +565,14 @@ struct FlowChain {
 // A flow of a ragged forward pass (fwn_model_forward_ragged): where its tail keeps Z = (log_s | t) [M][2 Ch] fp32 and where
 // the per-clip sums of -log_s go ([B][fwn_ragged_logdet_nslot(B)] fp64).
 // mom_part: a ragged init pass (fwn_model_forward_init_ragged) - scratch of the masked moments, fwn_ragged_moments_nslot chunks.
-// core_off / core_len: a windowed forward pass (fwn_model_forward_windows) - no lengths; the sums go over each window's core
-// rows [core_off / (2 Ch), + core_len / (2 Ch)) instead (DEVICE int32 [B], samples).
+// off / cnt: the rows the sums go over, [off / (2 Ch), + cnt / (2 Ch)) of each clip (DEVICE int32 [B], samples; off NULL: 0) -
+// (NULL, the lengths) in a ragged pass, each window's (core_off, core_len) in a windowed forward pass, which has no lengths.
 struct FlowRagged {
     float* z;
     double* acc;
     double* mom_part;
-    const int32_t* core_off;
-    const int32_t* core_len;
+    const int32_t* off;
+    const int32_t* cnt;
 };
 // One flow's run.  Zero-initialise, then set by name; what stays zero is absent.
 struct FlowRun {
@@ -666,10 +669,7 @@ static int flow_run_impl(const FlowRun& a) {
     fwn_launch_tail(a.o, (long)M * 256, d->L, d->Wskip, d->bskip, d->Wfinal, d->bfinal, d->Wzero, d->bzero,
                     d->ezero, d->an, a.xa, a.xb, inverse ? nullptr : a.partial, M, d->Ch, d->npt, inverse, hn, hc, (chain || a.rg) ? &tc : nullptr,
                     d->Wts, st);
-    if (a.rg && a.rg->core_off)
-        fwn_launch_window_logdet(a.rg->z, (long)a.B, Ti, d->Ch, d->ezero, d->an, a.rg->core_off, a.rg->core_len, 2 * d->Ch, a.rg->acc, st);
-    else if (a.rg)
-        fwn_launch_ragged_logdet(a.rg->z, (long)a.B, Ti, d->Ch, d->ezero, d->an, a.len, (int)a.B, 2 * d->Ch, a.rg->acc, st);
+    if (a.rg) fwn_launch_range_logdet(a.rg->z, (long)a.B, Ti, d->Ch, d->ezero, d->an, a.rg->off, a.rg->cnt, (int)a.B, 2 * d->Ch, a.rg->acc, st);
     return check_launch("fwn_flow_run");
 }
 
@@ -1312,7 +1312,7 @@ static int model_pass(PassKind kind, const fwn_model_desc* m, int64_t B, int64_t
             unsigned* sync = (!init && b.one_launch) ? (unsigned*)(ws + c.sync + (size_t)(i * nf + j) * c.sync_stride) : nullptr;
             FlowChain ch = flow_chain(m, d, next, M, init != 0, pl.spare, have_h0, b.chained && !sync);
             const FlowRagged rg{(float*)(ws + c.zsave), (double*)(ws + c.acc) + (size_t)(i * nf + j) * B * fwn_ragged_logdet_nslot((long)B),
-                                pt.mompart ? (double*)(ws + c.mompart) : nullptr, wc ? wc->off : nullptr, wc ? wc->len : nullptr};
+                                pt.mompart ? (double*)(ws + c.mompart) : nullptr, wc ? wc->off : nullptr, wc ? wc->len : len};
             FlowRun fr;
             memset(&fr, 0, sizeof(fr));
             fr.d = d; fr.B = B; fr.T = T; fr.xa = pl.at[p]; fr.xb = pl.at[p ^ 1]; fr.ca = ca; fr.P = P;
@@ -1440,8 +1440,6 @@ int fwn_model_synthesize(const fwn_model_desc* m, int64_t B, int64_t T, const fl
 }
 
 // ---- windowed synthesis: one group of n windows of L samples - latent slices, mel rows, the inverse pass, the cores (include/fwn.h) ----
-#define ALIGNED8(p) ((((uintptr_t)(p)) & 7) == 0)
-#define ALIGNED4(p) ((((uintptr_t)(p)) & 3) == 0)
 int fwn_latent_normal_at(float* z, int64_t n, int64_t L, uint64_t seed, const uint32_t* clip_id_dev, const int64_t* start_dev, float temp,
                          const int32_t* len_dev, void* stream) {
     REQUIRE(z && start_dev && n > 0 && n < 65536 && L > 0, "fwn_latent_normal_at: bad argument");
@@ -1478,6 +1476,19 @@ int fwn_window_scatter_pcm16(const float* x, int64_t n, int64_t L, const int32_t
 static size_t windows_mel_bytes(const fwn_model_desc* m, int64_t n, int64_t L) {
     return align_up((size_t)n * (size_t)(L / hop_of(m)) * m->num_mels * 4);
 }
+// what both group entries (`who`) refuse alike: the model and the shape (check_model), more than 32 767 windows, a workspace
+// off its 256 bytes, an 8-byte buffer (the int64 tables, fp64) or a 4-byte one (the 32-bit tables, fp32) off its alignment.
+// A NULL is aligned: whether it may be one is the entry's own check.
+static int check_windows_call(const char* who, const fwn_model_desc* m, int64_t n, int64_t L, const void* workspace,
+                              std::initializer_list<const void*> b8, std::initializer_list<const void*> b4) {
+    int rc = check_model(m, n, L);
+    if (rc) return rc;
+    REQUIRE(n < 32768, "%s: n=%lld windows (at most 32767 per call)", who, (long long)n);
+    REQUIRE((((uintptr_t)workspace) & 255) == 0, "%s: workspace must be 256-byte aligned", who);
+    for (const void* p : b8) REQUIRE(ALIGNED8(p), "%s: the int64 tables and fp64 buffers must be 8-byte aligned", who);
+    for (const void* p : b4) REQUIRE(ALIGNED4(p), "%s: the 32-bit tables and fp32 buffers must be 4-byte aligned", who);
+    return FWN_OK;
+}
 size_t fwn_synthesize_windows_workspace_bytes(const fwn_model_desc* m, int64_t n, int64_t L) {
     if (check_model(m, n, L) != FWN_OK || n >= 32768 || ((m->n_block * m->n_flow) & 1)) return 0;
     return carve(m, n, L, PASS_REVERSE).total + 2 * synth_extra(n, L) + windows_mel_bytes(m, n, L);
@@ -1487,18 +1498,12 @@ int fwn_model_synthesize_windows(const fwn_model_desc* m, int64_t n, int64_t L, 
                                  const int32_t* core_len_dev, const int64_t* out_off_dev, uint64_t seed, float temp, void* workspace,
                                  size_t workspace_bytes, int16_t* pcm_flat, float* wav_flat, void* stream) {
     // everything the inverse pass would refuse is refused here, before the latent fill is enqueued
-    int rc = check_model(m, n, L);
+    int rc = check_windows_call("fwn_model_synthesize_windows", m, n, L, workspace, {mel_row_dev, start_dev, out_off_dev},
+                                {clip_id_dev, core_off_dev, core_len_dev, mel_flat, wav_flat});
     if (rc) return rc;
     REQUIRE(mel_flat && workspace && pcm_flat, "fwn_model_synthesize_windows: null pointer");
     REQUIRE(mel_row_dev && clip_id_dev && start_dev && core_off_dev && core_len_dev && out_off_dev, "fwn_model_synthesize_windows: null table");
-    REQUIRE(ALIGNED8(mel_row_dev) && ALIGNED8(start_dev) && ALIGNED8(out_off_dev),
-            "fwn_model_synthesize_windows: the int64 tables (mel_row_dev, start_dev, out_off_dev) must be 8-byte aligned");
-    REQUIRE(ALIGNED4(clip_id_dev) && ALIGNED4(core_off_dev) && ALIGNED4(core_len_dev),
-            "fwn_model_synthesize_windows: the 32-bit tables (clip_id_dev, core_off_dev, core_len_dev) must be 4-byte aligned");
-    REQUIRE((((uintptr_t)workspace) & 255) == 0, "fwn_model_synthesize_windows: workspace must be 256-byte aligned");
-    REQUIRE(ALIGNED4(mel_flat) && ALIGNED4(wav_flat) && (((uintptr_t)pcm_flat) & 1) == 0,
-            "fwn_model_synthesize_windows: mel_flat and wav_flat must be 4-byte, pcm_flat 2-byte aligned");
-    REQUIRE(n < 32768, "fwn_model_synthesize_windows: n=%lld windows (at most 32767 per call)", (long long)n);
+    REQUIRE((((uintptr_t)pcm_flat) & 1) == 0, "fwn_model_synthesize_windows: pcm_flat must be 2-byte aligned");
     REQUIRE(((m->n_block * m->n_flow) & 1) == 0,
             "fwn_model_synthesize_windows: reverse with odd n_block*n_flow ends in swapped channel order (model.py:199,254); unsupported");
     const size_t base = carve(m, n, L, PASS_REVERSE).total, extra = synth_extra(n, L), need = base + 2 * extra + windows_mel_bytes(m, n, L);
@@ -1526,7 +1531,7 @@ int fwn_window_logdet_rows(const float* Z, int64_t n, int64_t rows, int Ch, cons
     REQUIRE(Ch >= 1 && (Ch & (Ch - 1)) == 0, "fwn_window_logdet_rows: Ch=%d must be a power of two", Ch);
     REQUIRE(ALIGNED4(Z) && ALIGNED8(acc) && ALIGNED4(core_off_dev) && ALIGNED4(core_len_dev), "fwn_window_logdet_rows: misaligned buffer");
     REQUIRE(rows <= ((int64_t)1 << 31) / samples_per_row, "fwn_window_logdet_rows: rows * samples_per_row exceeds 2^31");
-    fwn_launch_window_logdet(Z, (long)n, (long)rows, Ch, ez, an, core_off_dev, core_len_dev, samples_per_row, acc, (hipStream_t)stream);
+    fwn_launch_range_logdet(Z, (long)n, (long)rows, Ch, ez, an, core_off_dev, core_len_dev, (int)n, samples_per_row, acc, (hipStream_t)stream);
     return check_launch("fwn_window_logdet_rows");
 }
 int fwn_window_sums(const float* planes, int64_t n, int64_t L, const int32_t* core_off_dev, const int32_t* core_len_dev, const double* acc,
@@ -1568,18 +1573,12 @@ int fwn_model_forward_windows(const fwn_model_desc* m, int64_t n, int64_t L, con
                               const int32_t* slot_dev, double* acc, const int64_t* z_out_off_dev, float* z_flat, void* workspace,
                               size_t workspace_bytes, void* stream) {
     // everything the pass would refuse is refused here, before the gathers are enqueued
-    int rc = check_model(m, n, L);
+    int rc = check_windows_call("fwn_model_forward_windows", m, n, L, workspace, {x_row_dev, mel_row_dev, z_out_off_dev, acc},
+                                {core_off_dev, core_len_dev, slot_dev, x_flat, mel_flat, z_flat});
     if (rc) return rc;
     REQUIRE(x_flat && mel_flat && workspace && acc, "fwn_model_forward_windows: null pointer");
     REQUIRE(x_row_dev && mel_row_dev && core_off_dev && core_len_dev && slot_dev && (z_out_off_dev || !z_flat),
             "fwn_model_forward_windows: null table");
-    REQUIRE(ALIGNED8(x_row_dev) && ALIGNED8(mel_row_dev) && ALIGNED8(z_out_off_dev) && ALIGNED8(acc),
-            "fwn_model_forward_windows: the int64 tables (x_row_dev, mel_row_dev, z_out_off_dev) and acc must be 8-byte aligned");
-    REQUIRE(ALIGNED4(core_off_dev) && ALIGNED4(core_len_dev) && ALIGNED4(slot_dev),
-            "fwn_model_forward_windows: the int32 tables (core_off_dev, core_len_dev, slot_dev) must be 4-byte aligned");
-    REQUIRE((((uintptr_t)workspace) & 255) == 0, "fwn_model_forward_windows: workspace must be 256-byte aligned");
-    REQUIRE(ALIGNED4(x_flat) && ALIGNED4(mel_flat) && ALIGNED4(z_flat), "fwn_model_forward_windows: x_flat, mel_flat and z_flat must be 4-byte aligned");
-    REQUIRE(n < 32768, "fwn_model_forward_windows: n=%lld windows (at most 32767 per call)", (long long)n);
     REQUIRE(!m->gate_fp8, "fwn_model_forward_windows: windows go with a model without fp8 gates (the pass is the ragged forward's form)");
     const Carve c = carve(m, n, L, PASS_FORWARD_WINDOWS);
     const size_t need = c.total + synth_extra(n, L);

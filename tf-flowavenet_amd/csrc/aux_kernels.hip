@@ -794,139 +794,28 @@ __global__ __launch_bounds__(256) void fill_neg_shift_kernel(float* __restrict__
     }
 }
 
-// ---- ragged forward: one flow's log-det terms per clip -------------------------------------------------
+// ---- ragged and windowed forward: one flow's log-det terms per clip, over a range of its rows ------------
 // Z [nclip][rows][2 Ch] fp32 is what the saving tail keeps of the ZeroConv (fwn_tail_chain.save_z): log_s = Z[row][tau] *
-// ez[(tau / 32) * 64 + tau % 32] for tau < Ch (the pair-tile order of fwn_flow_desc.ezero).  blockIdx.y = clip, blockIdx.x =
-// chunk: the workgroups of a clip stride over its rows [0, len / spr) only - a padded row is never loaded - and each leaves
-// the fp64 sum of -log_s over its share in acc[clip][chunk] (a workgroup without a share leaves 0).  The order of every sum
-// is fixed by the grid: no atomics.  16-byte loads: Ch / 4 per row from Ch = 4 on, one per row at Ch = 2, one per two rows at
-// Ch = 1 (single dwords where the clip's base is not 16-byte aligned).  an (may be NULL): chunk 0 also leaves the flow's
-// ActNorm term sum_tau 3 logs_a + 3 logs_b in acc[clip][nslot - 1].
+// ez[(tau / 32) * 64 + tau % 32] for tau < Ch (the pair-tile order of fwn_flow_desc.ezero).  Clip c's range is rows
+// [off[c] / spr, off[c] / spr + cnt[c % ncnt] / spr) - off NULL: from row 0, the ragged pass's [0, len / spr) - the start
+// clamped to [0, rows], the count to what is left.  blockIdx.y = clip, blockIdx.x = chunk: the workgroups of a clip stride
+// over its range only - no row outside it is loaded - and each leaves the fp64 sum of -log_s over its share in
+// acc[clip][chunk] (a workgroup without a share leaves 0).  The order of every sum is fixed by the grid: no atomics.
+// 16-byte loads where the range's first row is 16-byte aligned: Ch / 4 per row from Ch = 4 on, one per row at Ch = 2.  At
+// Ch = 1 (two rows per 16 bytes, a row is 8 bytes) a range whose first row sits 8 bytes off peels that row as a dword and goes
+// on in 16-byte loads - the peeled form, not single dwords throughout - and one that then ends on an odd row takes its last
+// as a dword.  A whole-model pass never peels without a start table: a clip there has an even number of rows at Ch = 1 (block
+// 0), so every clip's base is 16-byte aligned; only fwn_ragged_logdet_rows with an odd row count per clip reaches the peel
+// from row 0.  Single dwords everywhere else.  an (may be NULL): chunk 0 also leaves the flow's ActNorm term sum_tau 3 logs_a
+// + 3 logs_b in acc[clip][nslot - 1].
 __device__ __forceinline__ float ez_of(const float* __restrict__ ez, int tau) { return ez[(tau >> 5) * 64 + (tau & 31)]; }
-__global__ __launch_bounds__(256) void ragged_logdet_kernel(const float* __restrict__ Z, long rows, int Ch,
-                                                            const float* __restrict__ ez, const float* __restrict__ an,
-                                                            const int* __restrict__ len, int nlen, int spr,
-                                                            double* __restrict__ acc, int nslot) {
+__global__ __launch_bounds__(256) void range_logdet_kernel(const float* __restrict__ Z, long rows, int Ch,
+                                                           const float* __restrict__ ez, const float* __restrict__ an,
+                                                           const int* __restrict__ off, const int* __restrict__ cnt, int ncnt,
+                                                           int spr, double* __restrict__ acc, int nslot) {
     __shared__ double red[256];
     const long c = blockIdx.y;
-    long keep = (long)len[c % nlen] / spr;
-    keep = keep < 0 ? 0 : (keep > rows ? rows : keep);
-    const float* zc = Z + (size_t)c * rows * 2 * Ch;
-    const long stride = (long)gridDim.x * 256, first = (long)blockIdx.x * 256 + threadIdx.x;
-    double s = 0.0;
-    if (Ch >= 4 && ((uintptr_t)zc & 15) == 0) {
-        const int upr = Ch >> 2;                              // 16-byte pieces of log_s per row
-        const long n = keep * upr;
-        for (long i = first; i < n; i += stride) {
-            const long row = i / upr;
-            const int t0 = (int)(i - row * upr) * 4;
-            const float4 v = *(const float4*)(zc + (size_t)row * 2 * Ch + t0);
-            const float* e = ez + (t0 >> 5) * 64 + (t0 & 31);                         // four channels of one pair tile
-            s -= (double)v.x * (double)e[0] + (double)v.y * (double)e[1] + (double)v.z * (double)e[2] + (double)v.w * (double)e[3];
-        }
-    } else if (Ch == 2 && ((uintptr_t)zc & 15) == 0) {
-        const double e0 = ez[0], e1 = ez[1];
-        for (long i = first; i < keep; i += stride) {
-            const float4 v = *(const float4*)(zc + (size_t)i * 4);                    // log_s 0, log_s 1, t 0, t 1
-            s -= (double)v.x * e0 + (double)v.y * e1;
-        }
-    } else if (Ch == 1 && ((uintptr_t)zc & 15) == 0) {
-        const double e0 = ez[0];
-        for (long i = first; i < (keep >> 1); i += stride) {
-            const float4 v = *(const float4*)(zc + (size_t)i * 4);                    // two rows of (log_s, t)
-            s -= (double)v.x * e0 + (double)v.z * e0;
-        }
-        if ((keep & 1) && first == 0) s -= (double)zc[(size_t)(keep - 1) * 2] * e0;
-    } else {
-        const long n = keep * Ch;
-        for (long i = first; i < n; i += stride) {
-            const long row = i / Ch;
-            const int tau = (int)(i - row * Ch);
-            s -= (double)zc[(size_t)row * 2 * Ch + tau] * (double)ez_of(ez, tau);
-        }
-    }
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-        if (threadIdx.x < st) red[threadIdx.x] += red[threadIdx.x + st];
-        __syncthreads();
-    }
-    double* out = acc + (size_t)c * nslot;
-    if (threadIdx.x == 0) out[blockIdx.x] = red[0];
-    if (an && blockIdx.x == 0) {
-        double a = 0.0;
-        for (int tau = threadIdx.x; tau < Ch; tau += 256) a += (double)an[3 * Ch + tau] + (double)an[7 * Ch + tau];
-        __syncthreads();
-        red[threadIdx.x] = a;
-        __syncthreads();
-        for (int st = 128; st > 0; st >>= 1) {
-            if (threadIdx.x < st) red[threadIdx.x] += red[threadIdx.x + st];
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) out[nslot - 1] = red[0];
-    }
-}
-
-// ---- ragged forward: out[0][b] = log_p, out[1][b] = logdet of clip b ------------------------------------
-// One workgroup per clip.  acc [nflows][nclip][nslot] fp64: what ragged_logdet_kernel left for every flow, flow f of block
-// f / n_flow with Ch = 2^(f / n_flow) channels per plane.  A flow's term is mean_C(3 logs) + mean(-log_s) / 2 over the clip's
-// own rows (model.py:80,135): sum_an / (2 Ch) + sum(-log_s) / (2 rows Ch), and 2 rows Ch = len at every block.  The prior is
-// the mean of 0.5 (-log 2 pi - z^2) over [0, len / 2) of both planes (model.py:342-343): nothing past a clip's end is
-// loaded.  Everything is added in fp64 in an order the launch fixes.
-__global__ __launch_bounds__(256) void ragged_finish_kernel(const float* __restrict__ planes, long nclip, long T,
-                                                            const double* __restrict__ acc, int nflows, int n_flow, int nslot,
-                                                            const int* __restrict__ len, float* __restrict__ out) {
-    __shared__ double r1[256], r2[256];
-    const long c = blockIdx.x, hT = T >> 1;
-    long n = len[c];
-    n = n < 0 ? 0 : (n > T ? T : n);
-    const long hn = n >> 1;
-    double s = 0.0, ld = 0.0;
-    for (int q = 0; q < 2; ++q) {
-        const float* z = planes + ((size_t)q * nclip + c) * hT;
-        long i = 0;
-        if (((uintptr_t)z & 15) == 0) {
-            for (long k = threadIdx.x; k < (hn >> 2); k += 256) {
-                const float4 v = *(const float4*)(z + k * 4);
-                s += (double)v.x * v.x + (double)v.y * v.y + (double)v.z * v.z + (double)v.w * v.w;
-            }
-            i = hn & ~3L;
-        }
-        for (long k = i + threadIdx.x; k < hn; k += 256) s += (double)z[k] * z[k];
-    }
-    for (int f = 0; f < nflows; ++f) {
-        const double* a = acc + ((size_t)f * nclip + c) * nslot;
-        double raw = 0.0;
-        for (int k = threadIdx.x; k < nslot - 1; k += 256) raw += a[k];
-        ld += raw / (double)(n > 0 ? n : 1);
-        if (threadIdx.x == 0) ld += a[nslot - 1] / (double)(2 << (f / n_flow));
-    }
-    r1[threadIdx.x] = s;
-    r2[threadIdx.x] = ld;
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-        if (threadIdx.x < st) { r1[threadIdx.x] += r1[threadIdx.x + st]; r2[threadIdx.x] += r2[threadIdx.x + st]; }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        out[c] = (float)(0.5 * (-1.8378770664093453 - r1[0] / (double)(n > 0 ? n : 1)));
-        out[nclip + c] = (float)r2[0];
-    }
-}
-
-// ---- windowed forward: the sums and the latent of a group's cores (include/fwn.h) --------------------------
-// ragged_logdet_kernel with a per-window start: window c's rows [core_off[c] / spr, core_off[c] / spr + core_len[c] / spr) of
-// Z [n][rows][2 Ch] - the start clamped to [0, rows], the count to what is left - and no row outside that range is loaded.
-// The same chunks, the same fp64 sums in the order the grid fixes, the same slots (acc[c][chunk], the ActNorm term in
-// acc[c][nslot - 1]).  16-byte loads as there; at Ch = 1 (two rows per 16 bytes) a range that starts on an odd row takes
-// its first row as a dword, and so does one that ends on one its last.
-__global__ __launch_bounds__(256) void window_logdet_kernel(const float* __restrict__ Z, long rows, int Ch,
-                                                            const float* __restrict__ ez, const float* __restrict__ an,
-                                                            const int* __restrict__ core_off, const int* __restrict__ core_len,
-                                                            int spr, double* __restrict__ acc, int nslot) {
-    __shared__ double red[256];
-    const long c = blockIdx.y;
-    long r0 = (long)core_off[c] / spr, keep = (long)core_len[c] / spr;
+    long r0 = off ? (long)off[c] / spr : 0, keep = (long)cnt[c % ncnt] / spr;
     r0 = r0 < 0 ? 0 : (r0 > rows ? rows : r0);
     keep = keep < 0 ? 0 : (keep > rows - r0 ? rows - r0 : keep);
     const float* zc = Z + ((size_t)c * rows + (size_t)r0) * 2 * Ch;
@@ -939,7 +828,7 @@ __global__ __launch_bounds__(256) void window_logdet_kernel(const float* __restr
             const long row = i / upr;
             const int t0 = (int)(i - row * upr) * 4;
             const float4 v = *(const float4*)(zc + (size_t)row * 2 * Ch + t0);
-            const float* e = ez + (t0 >> 5) * 64 + (t0 & 31);
+            const float* e = ez + (t0 >> 5) * 64 + (t0 & 31);                         // four channels of one pair tile
             s -= (double)v.x * (double)e[0] + (double)v.y * (double)e[1] + (double)v.z * (double)e[2] + (double)v.w * (double)e[3];
         }
     } else if (Ch == 2 && ((uintptr_t)zc & 15) == 0) {
@@ -991,10 +880,58 @@ __global__ __launch_bounds__(256) void window_logdet_kernel(const float* __restr
     }
 }
 
+// ---- ragged forward: out[0][b] = log_p, out[1][b] = logdet of clip b ------------------------------------
+// One workgroup per clip.  acc [nflows][nclip][nslot] fp64: what range_logdet_kernel left for every flow, flow f of block
+// f / n_flow with Ch = 2^(f / n_flow) channels per plane.  A flow's term is mean_C(3 logs) + mean(-log_s) / 2 over the clip's
+// own rows (model.py:80,135): sum_an / (2 Ch) + sum(-log_s) / (2 rows Ch), and 2 rows Ch = len at every block.  The prior is
+// the mean of 0.5 (-log 2 pi - z^2) over [0, len / 2) of both planes (model.py:342-343): nothing past a clip's end is
+// loaded.  Everything is added in fp64 in an order the launch fixes.
+__global__ __launch_bounds__(256) void ragged_finish_kernel(const float* __restrict__ planes, long nclip, long T,
+                                                            const double* __restrict__ acc, int nflows, int n_flow, int nslot,
+                                                            const int* __restrict__ len, float* __restrict__ out) {
+    __shared__ double r1[256], r2[256];
+    const long c = blockIdx.x, hT = T >> 1;
+    long n = len[c];
+    n = n < 0 ? 0 : (n > T ? T : n);
+    const long hn = n >> 1;
+    double s = 0.0, ld = 0.0;
+    for (int q = 0; q < 2; ++q) {
+        const float* z = planes + ((size_t)q * nclip + c) * hT;
+        long i = 0;
+        if (((uintptr_t)z & 15) == 0) {
+            for (long k = threadIdx.x; k < (hn >> 2); k += 256) {
+                const float4 v = *(const float4*)(z + k * 4);
+                s += (double)v.x * v.x + (double)v.y * v.y + (double)v.z * v.z + (double)v.w * v.w;
+            }
+            i = hn & ~3L;
+        }
+        for (long k = i + threadIdx.x; k < hn; k += 256) s += (double)z[k] * z[k];
+    }
+    for (int f = 0; f < nflows; ++f) {
+        const double* a = acc + ((size_t)f * nclip + c) * nslot;
+        double raw = 0.0;
+        for (int k = threadIdx.x; k < nslot - 1; k += 256) raw += a[k];
+        ld += raw / (double)(n > 0 ? n : 1);
+        if (threadIdx.x == 0) ld += a[nslot - 1] / (double)(2 << (f / n_flow));
+    }
+    r1[threadIdx.x] = s;
+    r2[threadIdx.x] = ld;
+    __syncthreads();
+    for (int st = 128; st > 0; st >>= 1) {
+        if (threadIdx.x < st) { r1[threadIdx.x] += r1[threadIdx.x + st]; r2[threadIdx.x] += r2[threadIdx.x + st]; }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        out[c] = (float)(0.5 * (-1.8378770664093453 - r1[0] / (double)(n > 0 ? n : 1)));
+        out[nclip + c] = (float)r2[0];
+    }
+}
+
+// ---- windowed forward: the sums and the latent of a group's cores (include/fwn.h) --------------------------
 // One workgroup per window c of a group: its four partial sums -> out[slot[c]][0 .. 4) fp64 (a negative slot writes nothing):
 //   [0] sum of z^2 over the core's elements [off / 2, (off + len) / 2) of both final planes [2][n][L / 2] (off = core_off[c]
 //       clamped to [0, L], len = core_len[c] to [0, L - off]; nothing outside is loaded),
-//   [1] sum over the flows, in flow order, of their chunk sums of -log_s (acc [nflows][n][nslot], window_logdet_kernel's),
+//   [1] sum over the flows, in flow order, of their chunk sums of -log_s (acc [nflows][n][nslot], range_logdet_kernel's),
 //   [2] sum over the flows of their ActNorm terms, sum_tau(3 logs) / (2 Ch) - the same for every window,
 //   [3] len, the number of samples these sums cover.
 // fp64 throughout, in an order the launch fixes: no atomics.
@@ -1476,25 +1413,19 @@ int fwn_ragged_logdet_nslot(long nclip) {
     const long cap = nclip < 2048 ? 2048 / nclip : 1;
     return (int)(cap > 32 ? 32 : cap) + 1;
 }
-void fwn_launch_ragged_logdet(const float* Z, long nclip, long rows, int Ch, const float* ez, const float* an, const int* len,
-                              int nlen, int samples_per_row, double* acc, hipStream_t st) {
+void fwn_launch_range_logdet(const float* Z, long nclip, long rows, int Ch, const float* ez, const float* an, const int* off,
+                             const int* cnt, int ncnt, int samples_per_row, double* acc, hipStream_t st) {
     const int nslot = fwn_ragged_logdet_nslot(nclip);
-    hipLaunchKernelGGL(ragged_logdet_kernel, dim3((unsigned)(nslot - 1), (unsigned)nclip), dim3(256), 0, st, Z, rows, Ch, ez, an, len,
-                       nlen, samples_per_row, acc, nslot);
+    hipLaunchKernelGGL(range_logdet_kernel, dim3((unsigned)(nslot - 1), (unsigned)nclip), dim3(256), 0, st, Z, rows, Ch, ez, an, off,
+                       cnt, ncnt, samples_per_row, acc, nslot);
 }
 void fwn_launch_ragged_finish(const float* planes, long nclip, long T, const double* acc, int nflows, int n_flow, const int* len,
                               float* out2B, hipStream_t st) {
     hipLaunchKernelGGL(ragged_finish_kernel, dim3((unsigned)nclip), dim3(256), 0, st, planes, nclip, T, acc, nflows, n_flow,
                        fwn_ragged_logdet_nslot(nclip), len, out2B);
 }
-// windowed forward: fwn_launch_ragged_logdet's grid (the same chunks and slots) for the core-restricted sums, one workgroup per
-// window for its partial sums, window_scatter's grid for the latent, one lane per clip for the finish
-void fwn_launch_window_logdet(const float* Z, long n, long rows, int Ch, const float* ez, const float* an, const int* core_off,
-                              const int* core_len, int samples_per_row, double* acc, hipStream_t st) {
-    const int nslot = fwn_ragged_logdet_nslot(n);
-    hipLaunchKernelGGL(window_logdet_kernel, dim3((unsigned)(nslot - 1), (unsigned)n), dim3(256), 0, st, Z, rows, Ch, ez, an, core_off,
-                       core_len, samples_per_row, acc, nslot);
-}
+// windowed forward: one workgroup per window for its partial sums, window_scatter's grid for the latent, one lane per clip for
+// the finish
 void fwn_launch_window_sums(const float* planes, long n, long L, const int* core_off, const int* core_len, const double* acc,
                             int nflows, int n_flow, const int* slot, double* out, hipStream_t st) {
     hipLaunchKernelGGL(window_sums_kernel, dim3((unsigned)n), dim3(256), 0, st, planes, n, L, core_off, core_len, acc, nflows, n_flow,

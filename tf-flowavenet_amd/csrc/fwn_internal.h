@@ -183,22 +183,20 @@ void fwn_launch_corpus_draw(const float* audio, const float* mel, const long lon
 void fwn_launch_fill_neg_shift(float* plane, long nclip, long rows, int Ch, const float* shift, const int* len, int nlen,
                                int samples_per_row, hipStream_t st);
 // One flow's log-det terms per clip from the tail's saved Z [nclip][rows][2 Ch]: acc[clip][0 .. nslot - 1) = fp64 chunk sums of
-// -log_s over the clip's own rows, acc[clip][nslot - 1] = sum_tau of the ActNorm's 3 logs (both planes; an may be NULL);
-// nslot = fwn_ragged_logdet_nslot(nclip).  fwn_launch_ragged_finish turns acc [nflows][nclip][nslot] and the planes into
-// out2B [2][nclip] = per-clip (log_p, logdet).
+// -log_s over rows [off[clip] / samples_per_row, + cnt[clip % ncnt] / samples_per_row) of the clip - off NULL: from row 0,
+// a ragged clip's own rows with cnt its length; a window's core with (core_off, core_len) -, acc[clip][nslot - 1] = sum_tau
+// of the ActNorm's 3 logs (both planes; an may be NULL); nslot = fwn_ragged_logdet_nslot(nclip).  fwn_launch_ragged_finish
+// turns acc [nflows][nclip][nslot] and the planes into out2B [2][nclip] = per-clip (log_p, logdet).
 int fwn_ragged_logdet_nslot(long nclip);
-void fwn_launch_ragged_logdet(const float* Z, long nclip, long rows, int Ch, const float* ez, const float* an, const int* len,
-                              int nlen, int samples_per_row, double* acc, hipStream_t st);
+void fwn_launch_range_logdet(const float* Z, long nclip, long rows, int Ch, const float* ez, const float* an, const int* off,
+                             const int* cnt, int ncnt, int samples_per_row, double* acc, hipStream_t st);
 void fwn_launch_ragged_finish(const float* planes, long nclip, long T, const double* acc, int nflows, int n_flow, const int* len,
                               float* out2B, hipStream_t st);
-// windowed forward (aux_kernels.hip; fwn.h has the contracts).  fwn_launch_window_logdet: fwn_launch_ragged_logdet over rows
-// [core_off[c] / samples_per_row, + core_len[c] / samples_per_row) of window c, the same slots.  fwn_launch_window_sums: window
-// c's partial sums (z^2 over its core of the final planes [2][n][L / 2], -log_s and the ActNorm terms over acc
-// [nflows][n][nslot], the core's length) -> out[slot[c]][0 .. 4) fp64.  fwn_launch_window_latent: the cores of the planes in
+// windowed forward (aux_kernels.hip; fwn.h has the contracts).  fwn_launch_window_sums: window c's partial sums (z^2 over its
+// core of the final planes [2][n][L / 2], -log_s and the ActNorm terms over acc [nflows][n][nslot] - fwn_launch_range_logdet's
+// over the core's rows -, the core's length) -> out[slot[c]][0 .. 4) fp64.  fwn_launch_window_latent: the cores of the planes in
 // time order -> z + out_off[c] (swapped: n_block * n_flow is odd).  fwn_launch_windows_finish: per clip, its windows' sums
 // part[slot0[c] .. slot0[c] + nwin[c])[4] in window order -> out2B [2][nclip].  Every table is read and clamped on the device.
-void fwn_launch_window_logdet(const float* Z, long n, long rows, int Ch, const float* ez, const float* an, const int* core_off,
-                              const int* core_len, int samples_per_row, double* acc, hipStream_t st);
 void fwn_launch_window_sums(const float* planes, long n, long L, const int* core_off, const int* core_len, const double* acc,
                             int nflows, int n_flow, const int* slot, double* out, hipStream_t st);
 void fwn_launch_window_latent(const float* planes, long n, long L, int swapped, const int* core_off, const int* core_len,

@@ -503,7 +503,7 @@ struct TrainCall {
                 const int rc = tail(d, s, xa, xb, m, ch);
                 if (rc != FWN_OK) return rc;
                 if (len) {      // per-clip log-det sums from the Z the tail keeps for the backward (its own whole-batch partials are ignored)
-                    fwn_launch_ragged_logdet(s.z, B, ti, ch, d->ezero, d->an, len, (int)B, 2 * ch, pl.acc + (size_t)(i * NF + j) * B * nslot, st);
+                    fwn_launch_range_logdet(s.z, B, ti, ch, d->ezero, d->an, nullptr, len, (int)B, 2 * ch, pl.acc + (size_t)(i * NF + j) * B * nslot, st);
                     rows.zero_planes(pl.planes, T);
                 }
                 p ^= 1;

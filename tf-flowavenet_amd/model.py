@@ -22,7 +22,8 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib, packing, weights
+from . import _lib, packing, weights, windowed
+from .windowed import ForwardStream, SynthesisStream  # noqa: F401  (the streams' public home is this module)
 
 
 class FloWaveNet:
@@ -112,15 +113,21 @@ class FloWaveNet:
         if g is None and self._hparams.gin_channels > 0:
             raise ValueError("g is None")   # model.py:320-321,353-354
 
-    def _prep(self, x, c, what):
-        import torch
+    def _require_params(self):
         if self._packed is None:
             raise RuntimeError("no parameters loaded: call load_params() / init_synthetic() first")
+
+    def _check_c(self, c):
+        if c.dim() != 3 or c.shape[2] != self._hparams.num_mels:
+            raise ValueError("c must have shape [B, T/hop, %d], got %r" % (self._hparams.num_mels, tuple(c.shape)))
+
+    def _prep(self, x, c, what):
+        import torch
+        self._require_params()
         hp = self._hparams
         if x.dim() != 3 or x.shape[2] != 1:
             raise ValueError("%s must have shape [B, T, 1], got %r" % (what, tuple(x.shape)))
-        if c.dim() != 3 or c.shape[2] != hp.num_mels:
-            raise ValueError("c must have shape [B, T/hop, %d], got %r" % (hp.num_mels, tuple(c.shape)))
+        self._check_c(c)
         b, t = int(x.shape[0]), int(x.shape[1])
         if c.shape[0] != b or int(c.shape[1]) * self.hop != t:
             raise ValueError("c has %d frames for T=%d samples (hop_size=%d)" % (c.shape[1], t, self.hop))
@@ -362,11 +369,9 @@ class FloWaveNet:
         ``synthesize.write_wav``.  Nothing touches the host.  Past a clip's length the PCM, the waveform and z are 0.
         return_wav / return_z add the fp32 waveform [B,T,1] / the latent [B,T,1] to the result, in that order."""
         import torch
-        if self._packed is None:
-            raise RuntimeError("no parameters loaded: call load_params() / init_synthetic() first")
+        self._require_params()
         hp = self._hparams
-        if c.dim() != 3 or c.shape[2] != hp.num_mels:
-            raise ValueError("c must have shape [B, T/hop, %d], got %r" % (hp.num_mels, tuple(c.shape)))
+        self._check_c(c)
         b, t = int(c.shape[0]), int(c.shape[1]) * self.hop
         if b < 1 or t < 1 or t % (1 << hp.n_block):
             raise ValueError("T=%d must be a positive multiple of 2^n_block=%d (model.py:226)" % (t, 1 << hp.n_block))
@@ -405,7 +410,7 @@ class FloWaveNet:
         off = (-ws.data_ptr()) % 256
         return ws.data_ptr() + off, ws.numel() - off
 
-    # ------------------------------------------------------------------ windowed synthesis
+    # ------------------------------------------------------------------ windowed passes (windowed.py drives them)
     def _window_workspace(self, kind, n, length):
         """Scratch of one group of ``n`` windows of ``length`` samples (``kind``: "reverse" - the plain inverse pass's -,
         "synth" - with z, the waveform and the windows' mel rows behind it - or "forward" - the windowed forward pass's, with
@@ -428,6 +433,11 @@ class FloWaveNet:
         off = (-ws.data_ptr()) % 256
         return ws.data_ptr() + off, ws.numel() - off
 
+    # the device calls of a group of windows, methods of the model: what a stand-in model under a stream replaces
+    _windows_call = windowed.synthesize_windows_call
+    _forward_windows_call = windowed.forward_windows_call
+    _forward_windows_finish = windowed.forward_windows_finish
+
     def reverse_windowed(self, z, c, window, batch=8, halo=None, g=None):
         """``reverse(z, c)`` of clips of any length, window by window: z [B,T,1], c [B,T/hop,num_mels] -> x [B,T,1] fp32, T a
         multiple of lcm(hop_size, 2^n_block).  ``windowing.plan_windows(T, window, hparams, halo)`` cuts every clip into cores
@@ -437,47 +447,7 @@ class FloWaveNet:
         network's receptive field), and T is bounded by memory for z, c and x only, not by what one pass can address.
         ``halo`` (a multiple of the unit; 0 = hard cuts) is for experiments.  Host sequencing only: slices, the inverse pass,
         copies."""
-        import torch
-        from . import windowing
-        self._check_g(g)
-        b, t, z32, c32 = self._prep(z, c, "z")
-        plans = [windowing.plan_windows(t, window, self._hparams, halo)] * b
-        x = torch.empty(b, t, 1, dtype=torch.float32, device=self._device)
-        for group in windowing.group_windows(plans, batch, self._hparams):
-            spans = [(clip,) + plans[clip][k] for clip, k in group]
-            length = spans[0][2] - spans[0][1]
-            zg = torch.stack([z32[clip, lo:hi] for clip, lo, hi, _, _ in spans])
-            cg = torch.stack([c32[clip, lo // self.hop:hi // self.hop] for clip, lo, hi, _, _ in spans])
-            xg = torch.empty(len(spans), length, 1, dtype=torch.float32, device=self._device)
-            wsp, wsn = self._window_workspace("reverse", len(spans), length)
-            rc = self._lib.fwn_model_reverse(C.byref(self._packed.model_desc), len(spans), length, zg.data_ptr(), cg.data_ptr(),
-                                             wsp, wsn, xg.data_ptr(), self._stream())
-            _lib.check(rc, "fwn_model_reverse")
-            for row, (clip, lo, _, a, e) in enumerate(spans):
-                x[clip, a:e] = xg[row, a - lo:e - lo]
-        return x
-
-    def _windows_call(self, mel_flat, rows, length, seed, temp, pcm_flat, wav_flat):
-        """One ``fwn_model_synthesize_windows`` group.  rows: per window ``(clip_id, start, mel_row, core_off, core_len, out_off)``
-        - the window is samples [start, start + length) of clip ``clip_id``'s latent stream, its mel rows start at row
-        ``mel_row`` of ``mel_flat``, and ``core_len`` samples from ``core_off`` of its waveform go to element ``out_off`` of
-        ``pcm_flat`` (and ``wav_flat``).  The six tables go up as one buffer: the int64 ones first, so all are aligned."""
-        import torch
-        n = len(rows)
-        t64 = np.asarray([[r[1] for r in rows], [r[2] for r in rows], [r[5] for r in rows]], dtype=np.int64)
-        t32 = np.asarray([[r[0] for r in rows], [r[3] for r in rows], [r[4] for r in rows]], dtype=np.int64).astype(np.uint32)
-        tab = torch.from_numpy(np.concatenate([t64.reshape(-1).view(np.uint8), t32.reshape(-1).view(np.uint8)])).to(self._device)
-        p64, p32 = tab.data_ptr(), tab.data_ptr() + 24 * n
-        assert p64 % 8 == 0
-        wsp, wsn = self._window_workspace("synth", n, length)
-        rc = self._lib.fwn_model_synthesize_windows(C.byref(self._packed.model_desc), n, length, mel_flat.data_ptr(), p64 + 8 * n,
-                                                    p32, p64, p32 + 4 * n, p32 + 8 * n, p64 + 16 * n, int(seed) % (1 << 64),
-                                                    float(temp), wsp, wsn, pcm_flat.data_ptr(),
-                                                    None if wav_flat is None else wav_flat.data_ptr(), self._stream())
-        _lib.check(rc, "fwn_model_synthesize_windows")
-
-    def _temp(self, temp):
-        return float(self._hparams.temp if temp is None else temp)
+        return windowed.reverse_windowed(self, z, c, window, batch, halo, g)
 
     def synthesize_windowed(self, c, seed, clip_ids=None, window=None, batch=8, temp=None, return_wav=False, halo=None):
         """``synthesize`` for clips of any length: c [B,F,num_mels] -> 16-bit PCM, ``torch.int16`` [B, F*hop] on the device, F*hop
@@ -489,88 +459,15 @@ class FloWaveNet:
         neither ``window`` nor ``batch``; the waveform is the whole-clip pass's to rounding (``reverse_windowed``).  No ceiling
         on T other than memory for the mel and the PCM, and 2^34 samples per clip.  The scratch depends on (batch, window)
         alone.  ``return_wav`` adds the fp32 waveform [B,T,1]."""
-        import torch
-        from . import windowing
-        if self._packed is None:
-            raise RuntimeError("no parameters loaded: call load_params() / init_synthetic() first")
-        hp = self._hparams
-        if c.dim() != 3 or c.shape[2] != hp.num_mels:
-            raise ValueError("c must have shape [B, T/hop, %d], got %r" % (hp.num_mels, tuple(c.shape)))
-        b, frames = int(c.shape[0]), int(c.shape[1])
-        t = frames * self.hop
-        if window is None:
-            unit = windowing.unit_samples(hp)
-            window = -(-65536 // unit) * unit
-        if b < 1:
-            raise ValueError("c holds no clip")
-        if t > (1 << 34):
-            raise ValueError("T=%d exceeds the 2^34 samples one clip's latent stream numbers" % t)
-        plans = [windowing.plan_windows(t, window, hp, halo)] * b
-        ids = list(range(b)) if clip_ids is None else self._clip_id_values(clip_ids, b)
-        c32 = c.to(device=torch.device(self._device), dtype=torch.float32).contiguous()
-        pcm = torch.empty(b, t, dtype=torch.int16, device=self._device)
-        wav = torch.empty(b, t, 1, dtype=torch.float32, device=self._device) if return_wav else None
-        for group in windowing.group_windows(plans, batch, self._hparams):
-            rows, length = [], None
-            for clip, k in group:
-                lo, hi, a, e = plans[clip][k]
-                length = hi - lo
-                rows.append((ids[clip], lo, clip * frames + lo // self.hop, a - lo, e - a, clip * t + a))
-            self._windows_call(c32, rows, length, seed, self._temp(temp), pcm, wav)
-        return (pcm, wav) if return_wav else pcm
+        return windowed.synthesize_windowed(self, c, seed, clip_ids, window, batch, temp, return_wav, halo)
 
     def stream(self, seed, clip_id=0, window=None, temp=None, halo=None):
         """Synthesis of one clip whose mel arrives while it is being made: -> a ``SynthesisStream`` with ``push(frames)`` and
         ``finish()``.  Fed the frames of ``c`` in any split, the concatenated output is ``synthesize_windowed(c, seed, [clip_id],
         window, batch=1)`` bit for bit (the same windows, one call each); core k comes out of the push that delivers frame
         ``(b_k + H) / hop``."""
-        if self._packed is None:
-            raise RuntimeError("no parameters loaded: call load_params() / init_synthetic() first")
+        self._require_params()
         return SynthesisStream(self, seed, clip_id, window, temp, halo)
-
-    # ------------------------------------------------------------------ windowed forward
-    def _default_window(self):
-        from . import windowing
-        unit = windowing.unit_samples(self._hparams)
-        return -(-65536 // unit) * unit
-
-    def _check_windowed_forward(self):
-        if self._packed is None:
-            raise RuntimeError("no parameters loaded: call load_params() / init_synthetic() first")
-        if self._gate_fp8:
-            raise ValueError("a gate_fp8 model takes no windows: the windowed forward runs the ragged forward's form of the pass")
-        if self._init:
-            raise ValueError("init=True takes no windows: the data-dependent ActNorm init needs the moments of the whole batch")
-
-    def _forward_windows_call(self, x_flat, mel_flat, rows, length, acc, z_flat):
-        """One ``fwn_model_forward_windows`` group.  rows: per window ``(x_row, mel_row, core_off, core_len, slot, z_off)`` - the
-        window's audio starts at row ``x_row`` of ``x_flat`` (rows of hop samples), its mel at row ``mel_row`` of ``mel_flat``;
-        the sums over ``core_len`` samples from ``core_off`` go to ``acc[slot]``, and that core of the latent, in time order, to
-        element ``z_off`` of ``z_flat`` (None: no latent).  The six tables go up as one buffer, the int64 ones first."""
-        import torch
-        n = len(rows)
-        t64 = np.asarray([[r[0] for r in rows], [r[1] for r in rows], [r[5] for r in rows]], dtype=np.int64)
-        t32 = np.asarray([[r[2] for r in rows], [r[3] for r in rows], [r[4] for r in rows]], dtype=np.int32)
-        tab = torch.from_numpy(np.concatenate([t64.reshape(-1).view(np.uint8), t32.reshape(-1).view(np.uint8)])).to(self._device)
-        p64, p32 = tab.data_ptr(), tab.data_ptr() + 24 * n
-        assert p64 % 8 == 0
-        wsp, wsn = self._window_workspace("forward", n, length)
-        rc = self._lib.fwn_model_forward_windows(C.byref(self._packed.model_desc), n, length, x_flat.data_ptr(), p64,
-                                                 mel_flat.data_ptr(), p64 + 8 * n, p32, p32 + 4 * n, p32 + 8 * n, acc.data_ptr(),
-                                                 p64 + 16 * n, None if z_flat is None else z_flat.data_ptr(), wsp, wsn,
-                                                 self._stream())
-        _lib.check(rc, "fwn_model_forward_windows")
-
-    def _forward_windows_finish(self, acc, slot0, nwin):
-        """``fwn_forward_windows_finish``: clip c's windows are slots ``slot0[c] .. slot0[c] + nwin[c]`` of ``acc`` -> fp32 [2, B]."""
-        import torch
-        b = len(slot0)
-        tab = torch.from_numpy(np.asarray([slot0, nwin], dtype=np.int32)).to(self._device)
-        out = torch.empty(2, b, dtype=torch.float32, device=self._device)
-        rc = self._lib.fwn_forward_windows_finish(acc.data_ptr(), tab.data_ptr(), tab.data_ptr() + 4 * b, b, out.data_ptr(),
-                                                  self._stream())
-        _lib.check(rc, "fwn_forward_windows_finish")
-        return out
 
     def forward_windowed(self, x, c, window=None, batch=8, return_z=False, halo=None, g=None):
         """``forward(x, c)`` of clips of any length, window by window: x [B,T,1], c [B,T/hop,num_mels] -> ``(log_p [B], logdet
@@ -584,35 +481,13 @@ class FloWaveNet:
         ``return_z`` adds z [B,T,1] fp32 in TIME order - the latent ``reverse`` / ``reverse_windowed(z, c, window)`` take and
         invert.  No ceiling on T other than memory for x, c and z; the scratch depends on (batch, window) alone.  ``halo`` (0
         = hard cuts) is for experiments.  ``init=True`` and ``gate_fp8`` models raise ``ValueError``."""
-        import torch
-        from . import windowing
-        self._check_g(g)
-        self._check_windowed_forward()
-        b, t, x32, c32 = self._prep(x, c, "x")
-        if t > (1 << 34):
-            raise ValueError("T=%d exceeds 2^34 samples per clip" % t)
-        if window is None:
-            window = self._default_window()
-        plan = windowing.plan_windows(t, window, self._hparams, halo)
-        plans, nwin, frames = [plan] * b, len(plan), t // self.hop
-        acc = torch.zeros(b * nwin, 4, dtype=torch.float64, device=self._device)
-        z = torch.empty(b, t, 1, dtype=torch.float32, device=self._device) if return_z else None
-        for group in windowing.group_windows(plans, batch, self._hparams):
-            rows, length = [], None
-            for clip, k in group:
-                lo, hi, a, e = plans[clip][k]
-                length = hi - lo
-                rows.append((clip * frames + lo // self.hop, clip * frames + lo // self.hop, a - lo, e - a, clip * nwin + k,
-                             clip * t + a))
-            self._forward_windows_call(x32, c32, rows, length, acc, z)
-        out = self._forward_windows_finish(acc, [clip * nwin for clip in range(b)], [nwin] * b)
-        return (out[0], out[1], z) if return_z else (out[0], out[1])
+        return windowed.forward_windowed(self, x, c, window, batch, return_z, halo, g)
 
     def forward_stream(self, window=None, halo=None, return_z=True):
         """The likelihood and the latent of one clip that is still arriving: -> a ``ForwardStream`` with ``push(x_samples,
         c_frames)`` and ``finish()``.  Fed the clip in any split, the concatenated z cores and the scalars are
         ``forward_windowed(x, c, window, batch=1, return_z=True)`` bit for bit (the same windows, one call each)."""
-        self._check_windowed_forward()
+        windowed.check_forward(self)
         return ForwardStream(self, window, halo, return_z)
 
     def upsample(self, c):
@@ -633,167 +508,6 @@ class FloWaveNet:
         return cur
 
     __call__ = forward
-
-
-class SynthesisStream:
-    """``FloWaveNet.stream``: 16-bit PCM of one clip while its mel is still arriving.  ``push(frames)`` takes [f, num_mels] (a
-    tensor or an array, any f >= 0) and returns the PCM of the cores that became computable with them, one ``torch.int16``
-    tensor on the device, possibly empty; ``finish()`` returns the rest (``ValueError`` if the frame total is no multiple of
-    lcm(hop_size, 2^n_block) / hop_size).  One ``fwn_model_synthesize_windows`` call per window; the object keeps only the
-    mel frames a later window still needs - at most (window + 2 H) / hop plus one push (``windowing.StreamPlanner``)."""
-
-    def __init__(self, model, seed, clip_id=0, window=None, temp=None, halo=None):
-        from . import windowing
-        hp = model._hparams
-        if window is None:
-            unit = windowing.unit_samples(hp)
-            window = -(-65536 // unit) * unit
-        self._model = model
-        self._plan = windowing.StreamPlanner(hp, window, halo)
-        self._seed = int(seed)
-        self._clip = FloWaveNet._clip_id_values([clip_id], 1)[0]
-        self._temp = model._temp(temp)
-        self._buf = None             # device [capacity, num_mels]: frames _base .. _base + _n of the clip
-        self._base = 0
-        self._n = 0
-
-    @property
-    def retained_frames(self):
-        return self._n
-
-    def _append(self, frames):
-        import torch
-        m = self._model
-        f = torch.as_tensor(frames).to(device=torch.device(m._device), dtype=torch.float32)
-        if f.dim() != 2 or f.shape[1] != m._hparams.num_mels:
-            raise ValueError("frames must have shape [f, %d], got %r" % (m._hparams.num_mels, tuple(f.shape)))
-        need = self._n + int(f.shape[0])
-        if self._buf is None or need > self._buf.shape[0]:
-            grown = torch.empty(max(need, 2 * (0 if self._buf is None else self._buf.shape[0])), m._hparams.num_mels,
-                                dtype=torch.float32, device=m._device)
-            if self._n:
-                grown[:self._n] = self._buf[:self._n]
-            self._buf = grown
-        self._buf[self._n:need] = f
-        self._n = need
-        return int(f.shape[0])
-
-    def _run(self, windows):
-        import torch
-        m = self._model
-        out = []
-        for lo, hi, a, e in windows:
-            pcm = torch.empty(e - a, dtype=torch.int16, device=m._device)
-            m._windows_call(self._buf, [(self._clip, lo, lo // m.hop - self._base, a - lo, e - a, 0)], hi - lo, self._seed, self._temp,
-                            pcm, None)
-            out.append(pcm)
-        drop = self._plan.first_frame - self._base      # frames no later window reads
-        if drop > 0:
-            drop = min(drop, self._n)
-            self._buf[:self._n - drop] = self._buf[drop:self._n].clone()
-            self._base += drop
-            self._n -= drop
-        if not out:
-            return torch.empty(0, dtype=torch.int16, device=m._device)
-        return out[0] if len(out) == 1 else torch.cat(out)
-
-    def push(self, frames):
-        return self._run(self._plan.push(self._append(frames)))
-
-    def finish(self):
-        return self._run(self._plan.finish())
-
-
-class ForwardStream:
-    """``FloWaveNet.forward_stream``: log_p, logdet and the time-ordered latent of one clip while it is still arriving - the twin
-    of ``SynthesisStream`` over the same ``windowing.StreamPlanner``.  ``push(x_samples, c_frames)`` takes f * hop samples (any
-    shape holding that many) and their f mel frames [f, num_mels] (tensors or arrays, any f >= 0) and returns the z of the cores
-    that became computable, one fp32 tensor on the device, possibly empty (always empty without ``return_z``); ``finish()``
-    returns ``(z_rest, log_p, logdet)``, the scalars fp32 0-dim tensors (``ValueError`` if the frame total is no multiple of
-    lcm(hop_size, 2^n_block) / hop_size, or nothing was pushed).  One ``fwn_model_forward_windows`` call per window; window k's
-    sums wait in slot k of a device table until ``finish`` adds them in window order.  The object keeps only the audio and mel
-    a later window still needs - at most (window + 2 H) / hop frames plus one push."""
-
-    def __init__(self, model, window=None, halo=None, return_z=True):
-        from . import windowing
-        self._model = model
-        self._plan = windowing.StreamPlanner(model._hparams, model._default_window() if window is None else window, halo)
-        self._return_z = bool(return_z)
-        self._x = None               # device [capacity, hop]: the audio of frames _base .. _base + _n of the clip
-        self._c = None               # device [capacity, num_mels]: those frames
-        self._base = 0
-        self._n = 0
-        self._acc = None             # device [capacity, 4] fp64: window k's partial sums in row k
-        self._k = 0                  # windows run
-
-    @property
-    def retained_frames(self):
-        return self._n
-
-    @staticmethod
-    def _grown(buf, used, need, like):
-        """``buf`` with room for ``need`` rows (doubling), its first ``used`` rows kept; ``like``: a tensor of the row's shape and dtype."""
-        import torch
-        if buf is not None and need <= buf.shape[0]:
-            return buf
-        grown = torch.empty((max(need, 2 * (0 if buf is None else buf.shape[0])),) + tuple(like.shape[1:]), dtype=like.dtype,
-                            device=like.device)
-        if used:
-            grown[:used] = buf[:used]
-        return grown
-
-    def _append(self, x_samples, c_frames):
-        import torch
-        m = self._model
-        dev = torch.device(m._device)
-        f = torch.as_tensor(c_frames).to(device=dev, dtype=torch.float32)
-        if f.dim() != 2 or f.shape[1] != m._hparams.num_mels:
-            raise ValueError("c_frames must have shape [f, %d], got %r" % (m._hparams.num_mels, tuple(f.shape)))
-        xs = torch.as_tensor(x_samples).to(device=dev, dtype=torch.float32).reshape(-1)
-        if xs.numel() != int(f.shape[0]) * m.hop:
-            raise ValueError("%d frames go with %d samples (hop_size=%d), got %d" % (f.shape[0], f.shape[0] * m.hop, m.hop, xs.numel()))
-        xs = xs.reshape(-1, m.hop)
-        need = self._n + int(f.shape[0])
-        self._x = self._grown(self._x, self._n, need, xs)
-        self._c = self._grown(self._c, self._n, need, f)
-        self._x[self._n:need] = xs
-        self._c[self._n:need] = f
-        self._n = need
-        return int(f.shape[0])
-
-    def _run(self, windows):
-        import torch
-        m = self._model
-        out = []
-        for lo, hi, a, e in windows:
-            z = torch.empty(e - a, dtype=torch.float32, device=m._device) if self._return_z else None
-            if self._acc is None or self._k == self._acc.shape[0]:
-                self._acc = self._grown(self._acc, self._k, self._k + 1, torch.empty(1, 4, dtype=torch.float64, device=m._device))
-            row = lo // m.hop - self._base
-            m._forward_windows_call(self._x, self._c, [(row, row, a - lo, e - a, self._k, 0)], hi - lo, self._acc, z)
-            self._k += 1
-            if z is not None:
-                out.append(z)
-        drop = self._plan.first_frame - self._base      # frames no later window reads
-        if drop > 0:
-            drop = min(drop, self._n)
-            for buf in (self._x, self._c):
-                buf[:self._n - drop] = buf[drop:self._n].clone()
-            self._base += drop
-            self._n -= drop
-        if not out:
-            return torch.empty(0, dtype=torch.float32, device=m._device)
-        return out[0] if len(out) == 1 else torch.cat(out)
-
-    def push(self, x_samples, c_frames):
-        return self._run(self._plan.push(self._append(x_samples, c_frames)))
-
-    def finish(self):
-        z = self._run(self._plan.finish())
-        if not self._k:
-            raise ValueError("finish: nothing was pushed")
-        out = self._model._forward_windows_finish(self._acc, [0], [self._k])
-        return z, out[0, 0], out[1, 0]
 
 
 def check_lengths(lengths, b, t, hop, n_block):

@@ -263,11 +263,10 @@ def _synthesize_device(args, hparams, model, names, mels, done=()):
 
 def window_samples(window, hparams):
     """``--window SAMPLES`` rounded up to a multiple of lcm(hop_size, 2^n_block), the unit every window edge sits on."""
-    from .windowing import unit_samples
-    unit = unit_samples(hparams)
+    from .windowing import round_up_to_unit
     if int(window) < 1:
         raise ValueError("--window must be a positive number of samples, got %r" % (window,))
-    return -(-int(window) // unit) * unit
+    return round_up_to_unit(window, hparams)
 
 
 def _synthesize_windowed(args, hparams, model, names, mels, window):

@@ -24,16 +24,28 @@ def unit_samples(hparams):
     return math.lcm(int(hparams.hop_size), 1 << int(hparams.n_block))
 
 
+def round_up_to_unit(samples, hparams):
+    """``samples`` rounded up to a multiple of ``unit_samples``."""
+    unit = unit_samples(hparams)
+    return -(-int(samples) // unit) * unit
+
+
+def default_window(hparams):
+    """The window of every windowed entry that is given none: 65 536 samples, rounded up to the unit."""
+    return round_up_to_unit(65536, hparams)
+
+
 def halo_samples(hparams):
     """The halo H in samples (module docstring): 15 872 for the stock model, 2 112 for ``hparams8000``."""
     reach = 1 + sum(3 ** layer for layer in range(int(hparams.n_layer)))
     h = int(hparams.n_flow) * reach * ((2 << int(hparams.n_block)) - 2) + 2 * int(hparams.hop_size)
-    unit = unit_samples(hparams)
-    return -(-h // unit) * unit
+    return round_up_to_unit(h, hparams)
 
 
 def _check_window(window, halo, hparams):
     unit = unit_samples(hparams)
+    if window is None:
+        window = default_window(hparams)
     if int(window) != window or window < unit or window % unit:
         raise ValueError("window=%r must be a positive multiple of lcm(hop_size, 2^n_block) = %d" % (window, unit))
     if halo is None:
@@ -47,8 +59,9 @@ def plan_windows(t, window, hparams, halo=None):
     """The windows of a clip of ``t`` samples: a list of ``(lo, hi, a, b)`` in samples.  The cores ``[a, b)`` tile ``[0, t)`` in
     order in steps of ``window`` (the last one may be shorter); window k is ``[lo, hi) = [max(0, a - H), min(t, b + H))`` - the
     inverse pass runs on that, and ``[a - lo, b - lo)`` of its output is kept.  ``window`` is a positive multiple of
-    ``unit_samples``, ``t`` a multiple of it; ``halo`` (a multiple of it too) overrides ``halo_samples`` - 0 is the cut without
-    context, the negative control of the tests.  A clip with ``t <= window`` is one window and needs no halo."""
+    ``unit_samples`` (None, here and in ``StreamPlanner``: ``default_window``), ``t`` a multiple of it; ``halo`` (a multiple
+    of it too) overrides ``halo_samples`` - 0 is the cut without context, the negative control of the tests.  A clip with
+    ``t <= window`` is one window and needs no halo."""
     window, h, unit = _check_window(window, halo, hparams)
     if int(t) != t or t < unit or t % unit:
         raise ValueError("t=%r must be a positive multiple of lcm(hop_size, 2^n_block) = %d" % (t, unit))
