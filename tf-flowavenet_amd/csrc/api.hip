@@ -1395,7 +1395,7 @@ int fwn_latent_normal(float* z, int64_t B, int64_t T, uint64_t seed, const uint3
     REQUIRE(z && B > 0 && B < 65536 && T > 0, "fwn_latent_normal: bad argument");
     REQUIRE((((uintptr_t)z) & 3) == 0, "fwn_latent_normal: z must be 4-byte aligned");
     REQUIRE(T <= ((int64_t)1 << 34), "fwn_latent_normal: T=%lld exceeds the 2^32 quads one clip's counter word numbers", (long long)T);
-    fwn_launch_latent_normal(z, (long)B, (long)T, (unsigned long long)seed, clip_id_dev, temp, len_dev, (hipStream_t)stream);
+    fwn_launch_latent_normal_at(z, (long)B, (long)T, (unsigned long long)seed, clip_id_dev, nullptr, temp, len_dev, (hipStream_t)stream);
     return check_launch("fwn_latent_normal");
 }
 int fwn_pcm16(const float* x, int16_t* pcm, int64_t B, int64_t T, const int32_t* len_dev, void* stream) {
@@ -1430,7 +1430,7 @@ int fwn_model_synthesize(const fwn_model_desc* m, int64_t B, int64_t T, const fl
         return fail(FWN_ERR_WORKSPACE, "fwn_model_synthesize: workspace %zu < required %zu bytes", workspace_bytes, base + 2 * extra);
     float* z = z_out ? z_out : (float*)((char*)workspace + base);
     float* wav = wav_out ? wav_out : (float*)((char*)workspace + base + extra);
-    fwn_launch_latent_normal(z, (long)B, (long)T, (unsigned long long)seed, clip_id_dev, temp, len_dev, (hipStream_t)stream);
+    fwn_launch_latent_normal_at(z, (long)B, (long)T, (unsigned long long)seed, clip_id_dev, nullptr, temp, len_dev, (hipStream_t)stream);
     rc = check_launch("fwn_model_synthesize (latent)");
     if (rc) return rc;
     rc = model_pass(kind, m, B, T, z, mel, len_dev, workspace, base, nullptr, nullptr, nullptr, nullptr, wav, stream);

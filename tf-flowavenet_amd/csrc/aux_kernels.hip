@@ -464,16 +464,32 @@ __global__ __launch_bounds__(256) void merge_kernel(const float* __restrict__ pl
     }
 }
 
-// ---- ragged batches: zero the rows past each clip's own length --------------------------------
-// buf [nclip][rows][row_bytes]; clip c keeps rows [0, len[c % nlen] / spr) and has the rest set to zero.  blockIdx.y = clip,
-// the workgroups of a clip stride over its padded bytes only: a clip of full length costs each of them one load of len.  The
-// length is clamped to the buffer here, so no value of it stores outside.  Whole 16-byte pieces between the first and the
-// last 16-byte boundary of the padded range, single dwords (at most three each side) around them.
-__global__ __launch_bounds__(256) void mask_rows_kernel(char* __restrict__ buf, long rows, long row_bytes,
-                                                        const int* __restrict__ len, int nlen, int spr) {
+// ---- per-clip row kernels: the pieces the ragged, synthesis, corpus and windowed kernels below share --------
+// Grid: blockIdx.y = clip (row, slot, window), and the workgroups of blockIdx.x stride over that row alone - four 16-byte
+// stores per thread if the whole row were written, at most about 2048 workgroups over all rows.
+static inline long row_cap(long nrows) { return nrows < 2048 ? 2048 / nrows : 1; }
+static inline dim3 row_grid(long bytes_per_row, long nrows) {
+    const long want = (bytes_per_row + 16383) / 16384, cap = row_cap(nrows);
+    return dim3((unsigned)(want < 1 ? 1 : (want > cap ? cap : want)), (unsigned)nrows);
+}
+// Every length and every core comes from a table in device memory and is clamped where it is read, so no value of it loads
+// or stores outside the buffer: a length to [0, T]; a core's offset to [0, L] and its count to what is left of L.
+__device__ __forceinline__ long clamp_len(long len, long T) { return len < 0 ? 0 : (len > T ? T : len); }
+__device__ __forceinline__ void clamp_core(long& off, long& n, long L) {
+    off = clamp_len(off, L);
+    n = clamp_len(n, L - off);
+}
+
+// ---- ragged batches: the rows past each clip's own length, filled ------------------------------------
+// buf [nclip][rows][row_bytes]; clip c keeps rows [0, len[c % nlen] / spr) and has every dword of the rest set to
+// val(its byte offset from the clip's base).  The workgroups of a clip stride over its padded bytes only: a clip of full
+// length costs each of them one load of len.  Whole 16-byte pieces between the first and the last 16-byte boundary of the
+// padded range, single dwords (at most three each side) around them.
+template <class Val>
+__device__ __forceinline__ void fill_padded_rows(char* buf, long rows, size_t row_bytes, const int* __restrict__ len, int nlen,
+                                                 int spr, Val val) {
     const long c = blockIdx.y;
-    long keep = (long)len[c % nlen] / spr;
-    keep = keep < 0 ? 0 : (keep > rows ? rows : keep);
+    const long keep = clamp_len((long)len[c % nlen] / spr, rows);
     if (keep == rows) return;
     const uintptr_t clip = (uintptr_t)buf + (size_t)c * rows * row_bytes;
     const uintptr_t p0 = clip + (size_t)keep * row_bytes, p1 = clip + (size_t)rows * row_bytes;
@@ -481,26 +497,41 @@ __global__ __launch_bounds__(256) void mask_rows_kernel(char* __restrict__ buf, 
     if (a0 > p1) a0 = p1;
     uintptr_t a1 = p1 & ~(uintptr_t)15;
     if (a1 < a0) a1 = a0;
-    const uint4 z4 = make_uint4(0u, 0u, 0u, 0u);
+    auto at = [&](uintptr_t q) { return val(q - clip); };
     for (uintptr_t q = a0 + ((size_t)blockIdx.x * 256 + threadIdx.x) * 16; q < a1; q += (size_t)gridDim.x * 256 * 16)
-        *(uint4*)q = z4;
+        *(float4*)q = make_float4(at(q), at(q + 4), at(q + 8), at(q + 12));
     if (blockIdx.x == 0) {
         const uintptr_t h = p0 + (size_t)threadIdx.x * 4, t = a1 + (size_t)(threadIdx.x - 4) * 4;
-        if (threadIdx.x < 4 && h < a0) *(unsigned*)h = 0u;
-        if (threadIdx.x >= 4 && threadIdx.x < 8 && t < p1) *(unsigned*)t = 0u;
+        if (threadIdx.x < 4 && h < a0) *(float*)h = at(h);
+        if (threadIdx.x >= 4 && threadIdx.x < 8 && t < p1) *(float*)t = at(t);
     }
+}
+// zero: what a clip on its own would find past its end
+__global__ __launch_bounds__(256) void mask_rows_kernel(char* __restrict__ buf, long rows, long row_bytes,
+                                                        const int* __restrict__ len, int nlen, int spr) {
+    fill_padded_rows(buf, rows, (size_t)row_bytes, len, nlen, spr, [](size_t) { return 0.0f; });
+}
+// Ragged forward: the padded rows of a flow's x_a plane [nclip][rows][Ch] fp32 (Ch a power of two) hold -shift[tau].  The front
+// conv applies ActNorm on the fly, (v + shift[tau]) * scale[tau]: a zero in a padded row would reach its +-1 taps as shift *
+// scale, where a clip on its own is zero-padded AFTER ActNorm.  (-s + s) is exactly +0, so every product is an exact zero.
+__global__ __launch_bounds__(256) void fill_neg_shift_kernel(float* __restrict__ buf, long rows, int Ch,
+                                                             const float* __restrict__ shift, const int* __restrict__ len,
+                                                             int nlen, int spr) {
+    fill_padded_rows((char*)buf, rows, (size_t)Ch * 4, len, nlen, spr,
+                     [=](size_t off) { return -shift[(off >> 2) & (size_t)(Ch - 1)]; });      // rows start at the clip's base
 }
 
 // ---- synthesis: the latent z drawn on the device ------------------------------------------------------------
-// z [B][T] fp32 = temp * N(0,1) from Philox4x32-10 (include/fwn.h fwn_latent_normal has the stream's definition; the fp64
-// restatement the tests compare against is tests/philox_ref.py).  Sample i of a clip comes from counter (i / 4, 0, clip_id, 0)
-// alone, so it does not depend on B, on the clip's row, on T or on where the buffer starts.  blockIdx.y = clip and the
-// workgroups of a clip stride over its quads (mask_rows_kernel's grid); one lane runs one Philox call and stores its four
-// samples as one 16-byte piece where that piece is whole and 16-byte aligned, as single dwords otherwise (the last quad of
-// a T that is no multiple of 4; every quad of a row that does not start on 16 bytes).  Samples at i >= len[b] (clamped to
-// [0, T] here, so no value of it stores outside) are +0.  logf / sqrtf / sincospif are the library's accurate forms (the build
-// has no fast-math): |z - fp64| stays within a few ulp of |z| <= 5.77 temp; 2 u2 is exact, so the sine and cosine see no
-// argument rounding.
+// z [n][L] fp32 = temp * N(0,1) from Philox4x32-10 (include/fwn.h fwn_latent_normal has the stream's definition; the fp64
+// restatement the tests compare against is tests/philox_ref.py).  Row r holds samples start[r] .. start[r] + L of clip
+// clip_id[r]'s stream (start NULL: from sample 0, fwn_latent_normal's whole clips; a negative start is read as 0).  Sample i of
+// a clip comes from counter (i / 4, 0, clip_id, 0), lane i % 4, alone, so it does not depend on n, on the clip's row, on L, on
+// where the buffer starts or on how the stream is cut into windows.  The lanes of a row stride over the QUADS OF THE STREAM that
+// overlap it (the first and the last may be partial when start or start + L is no multiple of 4); one lane runs one Philox
+// call and stores its four samples as one 16-byte piece where that piece is wholly inside the row and 16-byte aligned, as
+// single dwords otherwise.  Samples at j >= len[r] (clamped to [0, L]) are +0.  logf / sqrtf / sincospif are the library's
+// accurate forms (the build has no fast-math): |z - fp64| stays within a few ulp of |z| <= 5.77 temp; 2 u2 is exact, so the
+// sine and cosine see no argument rounding.
 __device__ __forceinline__ uint4 philox4x32_10(uint4 c, unsigned k0, unsigned k1) {
 #pragma unroll
     for (int r = 0; r < 10; ++r) {
@@ -521,152 +552,14 @@ __device__ __forceinline__ void box_muller(unsigned r, unsigned r2, float temp, 
     a = rad * c * temp;
     b = rad * s * temp;
 }
-__global__ __launch_bounds__(256) void latent_normal_kernel(float* __restrict__ z, long T, unsigned k0, unsigned k1,
-                                                            const unsigned* __restrict__ clip_id, float temp,
-                                                            const int* __restrict__ len) {
-    const long b = blockIdx.y;
-    long keep = len ? (long)len[b] : T;
-    keep = keep < 0 ? 0 : (keep > T ? T : keep);
-    const unsigned clip = clip_id ? clip_id[b] : (unsigned)b;
-    float* row = z + (size_t)b * T;
-    const long nq = (T + 3) >> 2;
-    for (long q = (long)blockIdx.x * 256 + threadIdx.x; q < nq; q += (long)gridDim.x * 256) {
-        const long i0 = q * 4;
-        float v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-        if (i0 < keep) {                                          // a quad wholly past the clip's end draws nothing
-            const uint4 r = philox4x32_10(make_uint4((unsigned)q, 0u, clip, 0u), k0, k1);
-            box_muller(r.x, r.y, temp, v[0], v[1]);
-            box_muller(r.z, r.w, temp, v[2], v[3]);
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                if (i0 + e >= keep) v[e] = 0.0f;
-        }
-        float* p = row + i0;
-        if (i0 + 4 <= T && (((uintptr_t)p) & 15) == 0) {
-            *(float4*)p = make_float4(v[0], v[1], v[2], v[3]);
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                if (i0 + e < T) p[e] = v[e];
-        }
-    }
-}
-
-// ---- training: a batch drawn from the device-resident corpus ---------------------------------------------------
-// include/fwn.h fwn_corpus_draw has the layout and the stream's definition (tests/corpus_ref.py restates it).  blockIdx.y =
-// slot b.  Every workgroup of a slot derives the slot's pick itself - one Philox call and two table reads, uniform over the
-// workgroup - from the counter as it stands: nothing in this launch writes it (corpus_advance_kernel does, behind it in
-// stream order).  The workgroups of a slot then stride over the row of x and the row of c: [0, keep) copied from the corpus,
-// [keep, total) +0.  A row goes in 16-byte pieces where source, destination, keep and total are all 16-byte multiples - so a
-// piece is either wholly inside the clip or wholly past it - and in dwords otherwise.  The first workgroup of a slot writes
-// len and picks.  The table is the caller's: a negative frame count is read as 0, and no start leaves [0, n - F).
-__device__ __forceinline__ void corpus_copy_row(const float* src, float* dst, long keep, long total, long first, long stride) {
-    if ((((uintptr_t)src | (uintptr_t)dst) & 15) == 0 && ((keep | total) & 3) == 0) {
-        for (long q = first; q < (total >> 2); q += stride) {
-            const long i = q * 4;
-            *(float4*)(dst + i) = i < keep ? *(const float4*)(src + i) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        }
-    } else {
-        for (long i = first; i < total; i += stride) dst[i] = i < keep ? src[i] : 0.0f;
-    }
-}
-__global__ __launch_bounds__(256) void corpus_draw_kernel(const float* __restrict__ audio, const float* __restrict__ mel,
-                                                          const long long* __restrict__ frame_off, unsigned long long n_utt, int hop,
-                                                          int num_mels, int unit_frames, long F, unsigned k0, unsigned k1,
-                                                          unsigned stream_id, const unsigned long long* counter,
-                                                          float* __restrict__ x, float* __restrict__ c, int* __restrict__ len,
-                                                          int* __restrict__ picks) {
-    const unsigned b = blockIdx.y;
-    const unsigned long long d = *counter;
-    const uint4 r = philox4x32_10(make_uint4((unsigned)(d & 0xffffffffull), (unsigned)(d >> 32), b, stream_id), k0, k1);
-    const long long u = (long long)(((unsigned long long)r.x * n_utt) >> 32);            // n_utt < 2^32: no overflow
-    const long long f0 = frame_off[u];
-    long long n = frame_off[u + 1] - f0;
-    if (n < 0) n = 0;
-    long long start = 0, frames;
-    if (n > F) {
-        start = (long long)__umul64hi((unsigned long long)r.y << 32, (unsigned long long)(n - F));      // (r1 (n - F)) >> 32
-        frames = F;
-    } else {
-        frames = n / unit_frames * unit_frames;
-    }
-    const long long row0 = f0 + start;
-    const long first = (long)blockIdx.x * 256 + threadIdx.x, stride = (long)gridDim.x * 256;
-    corpus_copy_row(audio + row0 * hop, x + (long long)b * F * hop, (long)(frames * hop), F * hop, first, stride);
-    corpus_copy_row(mel + row0 * num_mels, c + (long long)b * F * num_mels, (long)(frames * num_mels), F * num_mels, first, stride);
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        len[b] = (int)(frames * hop);
-        if (picks) {
-            picks[2 * b] = (int)u;
-            picks[2 * b + 1] = (int)start;
-        }
-    }
-}
-// one lane, behind the gather in stream order: the draw counter moves on (a plain load and a plain vector store)
-__global__ void corpus_advance_kernel(unsigned long long* counter) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) *counter = *counter + 1ull;
-}
-
-// ---- synthesis: fp32 waveform -> 16-bit PCM ------------------------------------------------------------------
-// x [B][T] fp32 -> pcm [B][T] int16 = rint((double)clamp(x, -1, 1) * 32767.0), NaN -> 0: synthesize.write_wav's float64 NumPy
-// arithmetic bit for bit (the fp64 product of an fp32 value and 32767 is exact, so the one rounding is rint's half-to-even;
-// the fp32 product would round twice at near-ties).  Samples at i >= len[b] (clamped as above) are 0.  blockIdx.y = clip.
-// Between the first and the last 16-byte boundary of the clip's pcm row, one lane turns eight samples (two 16-byte loads)
-// into one 16-byte store - where x is 16-byte aligned at that first boundary too; the up to seven samples on either side go
-// one by one, and so does the whole row where x and pcm disagree about their 16-byte phase.
-__device__ __forceinline__ short pcm16_of(float v) {
-    v = (v != v) ? 0.0f : fminf(fmaxf(v, -1.0f), 1.0f);
-    return (short)(int)rint((double)v * 32767.0);
-}
-__global__ __launch_bounds__(256) void pcm16_kernel(const float* __restrict__ x, short* __restrict__ pcm, long T,
-                                                    const int* __restrict__ len) {
-    const long b = blockIdx.y;
-    long keep = len ? (long)len[b] : T;
-    keep = keep < 0 ? 0 : (keep > T ? T : keep);
-    const float* xr = x + (size_t)b * T;
-    short* pr = pcm + (size_t)b * T;
-    // [a0, a1): the samples of the row whose pcm bytes form whole aligned 16-byte pieces
-    long a0 = (long)(((16 - (((uintptr_t)pr) & 15)) & 15) >> 1);
-    if (a0 > T) a0 = T;
-    long a1 = a0 + ((T - a0) & ~7L);
-    if ((((uintptr_t)(xr + a0)) & 15) != 0) a1 = a0 = 0;         // phases disagree: everything goes through the tail loop
-    const long first = (long)blockIdx.x * 256 + threadIdx.x, stride = (long)gridDim.x * 256;
-    for (long g = first; g < ((a1 - a0) >> 3); g += stride) {
-        const long i0 = a0 + g * 8;
-        union { short s[8]; uint4 u; } o;
-        if (i0 >= keep) {
-            o.u = make_uint4(0u, 0u, 0u, 0u);                     // past the clip's end: nothing is loaded
-        } else {
-            const float4 lo = *(const float4*)(xr + i0), hi = *(const float4*)(xr + i0 + 4);
-            const float v[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-#pragma unroll
-            for (int e = 0; e < 8; ++e) o.s[e] = (i0 + e < keep) ? pcm16_of(v[e]) : (short)0;
-        }
-        *(uint4*)(pr + i0) = o.u;
-    }
-    const long nside = a0 + (T - a1);                             // head [0, a0) and tail [a1, T)
-    for (long j = first; j < nside; j += stride) {
-        const long i = j < a0 ? j : a1 + (j - a0);
-        pr[i] = i < keep ? pcm16_of(xr[i]) : (short)0;
-    }
-}
-
-// ---- windowed synthesis: the latent of a window, the mel rows of a window, the cores of a group (include/fwn.h) ----------
-// z [n][L] fp32: row r holds samples start[r] .. start[r] + L of clip clip_id[r]'s stream - latent_normal_kernel with a
-// per-row start.  Sample i = start + j still comes from counter (i / 4, 0, clip, 0), lane i % 4, through the same
-// philox4x32_10 and box_muller, so a row is bit for bit the slice of what latent_normal_kernel writes for that clip.  The
-// lanes of a row stride over the QUADS OF THE STREAM that overlap the window (the first and the last may be partial when
-// start or start + L is no multiple of 4); a quad wholly inside the row goes as one 16-byte store where its address is
-// 16-byte aligned, as dwords otherwise.  j >= len[r] (clamped to [0, L]) is +0.  A negative start is read as 0.
 __global__ __launch_bounds__(256) void latent_normal_at_kernel(float* __restrict__ z, long L, unsigned k0, unsigned k1,
                                                                const unsigned* __restrict__ clip_id,
                                                                const long long* __restrict__ start, float temp,
                                                                const int* __restrict__ len) {
     const long r = blockIdx.y;
-    long keep = len ? (long)len[r] : L;
-    keep = keep < 0 ? 0 : (keep > L ? L : keep);
+    const long keep = len ? clamp_len(len[r], L) : L;
     const unsigned clip = clip_id ? clip_id[r] : (unsigned)r;
-    long long s0 = start[r];
+    long long s0 = start ? start[r] : 0;
     if (s0 < 0) s0 = 0;
     float* row = z + (size_t)r * L;
     const long long q0 = s0 >> 2, nq = ((s0 + L + 3) >> 2) - q0;
@@ -693,63 +586,138 @@ __global__ __launch_bounds__(256) void latent_normal_at_kernel(float* __restrict
     }
 }
 
+// ---- training: a batch drawn from the device-resident corpus ---------------------------------------------------
+// include/fwn.h fwn_corpus_draw has the layout and the stream's definition (tests/corpus_ref.py restates it).  blockIdx.y =
+// slot b.  Every workgroup of a slot derives the slot's pick itself - one Philox call and two table reads, uniform over the
+// workgroup - from the counter as it stands: nothing in this launch writes it (corpus_advance_kernel does, behind it in
+// stream order).  The workgroups of a slot then stride over the row of x and the row of c (copy_row).  The first workgroup of
+// a slot writes len and picks.  The table is the caller's: a negative frame count is read as 0, and no start leaves [0, n - F).
+//
+// copy_row: dst[0, keep) = src[0, keep), dst[keep, total) = +0, nothing of src from keep on loaded.  16-byte pieces where
+// source, destination, keep and total are all 16-byte multiples - so a piece is either wholly copied or wholly zero - and
+// dwords otherwise.  CUT = false: the caller's keep is total, and the tests against it are compiled out.
+template <bool CUT>
+__device__ __forceinline__ void copy_row(const float* src, float* dst, long keep, long total, long first, long stride) {
+    if ((((uintptr_t)src | (uintptr_t)dst) & 15) == 0 && ((keep | total) & 3) == 0) {
+        for (long q = first; q < (total >> 2); q += stride) {
+            const long i = q * 4;
+            *(float4*)(dst + i) = (!CUT || i < keep) ? *(const float4*)(src + i) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        }
+    } else {
+        for (long i = first; i < total; i += stride) dst[i] = (!CUT || i < keep) ? src[i] : 0.0f;
+    }
+}
+__global__ __launch_bounds__(256) void corpus_draw_kernel(const float* __restrict__ audio, const float* __restrict__ mel,
+                                                          const long long* __restrict__ frame_off, unsigned long long n_utt, int hop,
+                                                          int num_mels, int unit_frames, long F, unsigned k0, unsigned k1,
+                                                          unsigned stream_id, const unsigned long long* counter,
+                                                          float* __restrict__ x, float* __restrict__ c, int* __restrict__ len,
+                                                          int* __restrict__ picks) {
+    const unsigned b = blockIdx.y;
+    const unsigned long long d = *counter;
+    const uint4 r = philox4x32_10(make_uint4((unsigned)(d & 0xffffffffull), (unsigned)(d >> 32), b, stream_id), k0, k1);
+    const long long u = (long long)(((unsigned long long)r.x * n_utt) >> 32);            // n_utt < 2^32: no overflow
+    const long long f0 = frame_off[u];
+    long long n = frame_off[u + 1] - f0;
+    if (n < 0) n = 0;
+    long long start = 0, frames;
+    if (n > F) {
+        start = (long long)__umul64hi((unsigned long long)r.y << 32, (unsigned long long)(n - F));      // (r1 (n - F)) >> 32
+        frames = F;
+    } else {
+        frames = n / unit_frames * unit_frames;
+    }
+    const long long row0 = f0 + start;
+    const long first = (long)blockIdx.x * 256 + threadIdx.x, stride = (long)gridDim.x * 256;
+    copy_row<true>(audio + row0 * hop, x + (long long)b * F * hop, (long)(frames * hop), F * hop, first, stride);
+    copy_row<true>(mel + row0 * num_mels, c + (long long)b * F * num_mels, (long)(frames * num_mels), F * num_mels, first, stride);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        len[b] = (int)(frames * hop);
+        if (picks) {
+            picks[2 * b] = (int)u;
+            picks[2 * b + 1] = (int)start;
+        }
+    }
+}
+// one lane, behind the gather in stream order: the draw counter moves on (a plain load and a plain vector store)
+__global__ void corpus_advance_kernel(unsigned long long* counter) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) *counter = *counter + 1ull;
+}
+
+// ---- synthesis: fp32 waveform -> 16-bit PCM ------------------------------------------------------------------
+// x [B][T] fp32 -> pcm [B][T] int16 = rint((double)clamp(x, -1, 1) * 32767.0), NaN -> 0: synthesize.write_wav's float64 NumPy
+// arithmetic bit for bit (the fp64 product of an fp32 value and 32767 is exact, so the one rounding is rint's half-to-even;
+// the fp32 product would round twice at near-ties).  Samples at i >= len[b] (clamped) are 0.
+__device__ __forceinline__ short pcm16_of(float v) {
+    v = (v != v) ? 0.0f : fminf(fmaxf(v, -1.0f), 1.0f);
+    return (short)(int)rint((double)v * 32767.0);
+}
+// One row: pr[0, n) = pcm16_of(xr[i]) for i < keep, 0 from keep on - and nothing of xr from keep on is loaded.  Between the
+// first and the last 16-byte boundary of pr, one lane turns eight samples (two 16-byte loads) into one 16-byte store - where
+// xr is 16-byte aligned at that first boundary too; the up to seven samples on either side go one by one, and so does the
+// whole row where xr and pr disagree about their 16-byte phase.  CUT = false: the caller's keep is n, and the tests against it
+// are compiled out (left in, the launch over a group's 8 cores of 262 144 samples took 5.3 us against 3.5 - 4.0).
+template <bool CUT>
+__device__ __forceinline__ void pcm16_row(const float* __restrict__ xr, short* __restrict__ pr, long n, long keep, long first,
+                                          long stride) {
+    // [a0, a1): the samples of the row whose pcm bytes form whole aligned 16-byte pieces
+    long a0 = (long)(((16 - (((uintptr_t)pr) & 15)) & 15) >> 1);
+    if (a0 > n) a0 = n;
+    long a1 = a0 + ((n - a0) & ~7L);
+    if ((((uintptr_t)(xr + a0)) & 15) != 0) a1 = a0 = 0;         // phases disagree: everything goes through the side loop
+    for (long g = first; g < ((a1 - a0) >> 3); g += stride) {
+        const long i0 = a0 + g * 8;
+        union { short s[8]; uint4 u; } o;
+        if (CUT && i0 >= keep) {
+            o.u = make_uint4(0u, 0u, 0u, 0u);                     // past the clip's end: nothing is loaded
+        } else {
+            const float4 lo = *(const float4*)(xr + i0), hi = *(const float4*)(xr + i0 + 4);
+            const float v[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+#pragma unroll
+            for (int e = 0; e < 8; ++e) o.s[e] = (!CUT || i0 + e < keep) ? pcm16_of(v[e]) : (short)0;
+        }
+        *(uint4*)(pr + i0) = o.u;
+    }
+    const long nside = a0 + (n - a1);                             // head [0, a0) and tail [a1, n)
+    for (long j = first; j < nside; j += stride) {
+        const long i = j < a0 ? j : a1 + (j - a0);
+        pr[i] = (!CUT || i < keep) ? pcm16_of(xr[i]) : (short)0;
+    }
+}
+__global__ __launch_bounds__(256) void pcm16_kernel(const float* __restrict__ x, short* __restrict__ pcm, long T,
+                                                    const int* __restrict__ len) {
+    const long b = blockIdx.y;
+    pcm16_row<true>(x + (size_t)b * T, pcm + (size_t)b * T, T, len ? clamp_len(len[b], T) : T, (long)blockIdx.x * 256 + threadIdx.x,
+                    (long)gridDim.x * 256);
+}
+
+// ---- windowed synthesis: the mel rows of a window, the cores of a group (include/fwn.h) ----------
 // dst [n][count] fp32: row r = the count floats of src from float offset src_row[r] * row_floats (64-bit: the source is a flat
-// buffer of whole clips, or of many).  16-byte pieces where source and destination rows are both 16-byte aligned and count
-// is a multiple of 4, dwords otherwise (corpus_copy_row's rule).  A negative offset is read as 0.
+// buffer of whole clips, or of many), through copy_row.  A negative offset is read as 0.
 __global__ __launch_bounds__(256) void window_gather_kernel(const float* __restrict__ src, const long long* __restrict__ src_row,
                                                             long row_floats, float* __restrict__ dst, long count) {
     const long r = blockIdx.y;
     long long s0 = src_row[r];
     if (s0 < 0) s0 = 0;
-    const float* s = src + (size_t)s0 * (size_t)row_floats;
-    float* d = dst + (size_t)r * count;
-    const long first = (long)blockIdx.x * 256 + threadIdx.x, stride = (long)gridDim.x * 256;
-    if ((((uintptr_t)s | (uintptr_t)d) & 15) == 0 && (count & 3) == 0) {
-        for (long q = first; q < (count >> 2); q += stride) *(float4*)(d + q * 4) = *(const float4*)(s + q * 4);
-    } else {
-        for (long i = first; i < count; i += stride) d[i] = s[i];
-    }
+    copy_row<false>(src + (size_t)s0 * (size_t)row_floats, dst + (size_t)r * count, count, count,
+                    (long)blockIdx.x * 256 + threadIdx.x, (long)gridDim.x * 256);
 }
 
-// The cores of a group: for row r of x [n][L] fp32, the core_len[r] samples from core_off[r] go to pcm + out_off[r] as 16-bit
-// PCM (pcm16_of: fwn_pcm16's arithmetic) and / or to wav + out_off[r] as they are.  The core is clamped into the row here -
-// core_off to [0, L], core_len to [0, L - core_off] - so no table value reads outside x; out_off is the caller's (64-bit).
-// Nothing outside [out_off, out_off + core_len) is written.  PCM: pcm16_kernel's scheme on the core - between the first and
-// the last 16-byte boundary of the destination one lane turns eight samples into one 16-byte store where x is 16-byte
-// aligned there too, single samples on either side and everywhere where the phases disagree.  Waveform: 16-byte pieces
-// between the destination's boundaries where the source agrees, dwords otherwise.
+// The cores of a group: for row r of x [n][L] fp32, the core_len[r] samples from core_off[r] (clamped into the row) go to
+// pcm + out_off[r] as 16-bit PCM (pcm16_row on the core) and / or to wav + out_off[r] as they are; out_off is the caller's
+// (64-bit).  Nothing outside [out_off, out_off + core_len) is written.  The waveform is not copy_row's rule: its destination
+// starts anywhere, so it goes in 16-byte pieces between the DESTINATION's boundaries where the source agrees, dwords otherwise.
 __global__ __launch_bounds__(256) void window_scatter_kernel(const float* __restrict__ x, long L, const int* __restrict__ core_off,
                                                              const int* __restrict__ core_len,
                                                              const long long* __restrict__ out_off, short* __restrict__ pcm,
                                                              float* __restrict__ wav) {
     const long r = blockIdx.y;
     long off = core_off[r], n = core_len[r];
-    off = off < 0 ? 0 : (off > L ? L : off);
-    n = n < 0 ? 0 : (n > L - off ? L - off : n);
+    clamp_core(off, n, L);
     const float* xr = x + (size_t)r * L + off;
     const long long o0 = out_off[r];
     const long first = (long)blockIdx.x * 256 + threadIdx.x, stride = (long)gridDim.x * 256;
-    if (pcm) {
-        short* pr = pcm + o0;
-        long a0 = (long)(((16 - (((uintptr_t)pr) & 15)) & 15) >> 1);
-        if (a0 > n) a0 = n;
-        long a1 = a0 + ((n - a0) & ~7L);
-        if ((((uintptr_t)(xr + a0)) & 15) != 0) a1 = a0 = 0;     // phases disagree: everything goes through the side loop
-        for (long g = first; g < ((a1 - a0) >> 3); g += stride) {
-            const long i0 = a0 + g * 8;
-            union { short s[8]; uint4 u; } o;
-            const float4 lo = *(const float4*)(xr + i0), hi = *(const float4*)(xr + i0 + 4);
-            const float v[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-#pragma unroll
-            for (int e = 0; e < 8; ++e) o.s[e] = pcm16_of(v[e]);
-            *(uint4*)(pr + i0) = o.u;
-        }
-        const long nside = a0 + (n - a1);                         // head [0, a0) and tail [a1, n)
-        for (long j = first; j < nside; j += stride) {
-            const long i = j < a0 ? j : a1 + (j - a0);
-            pr[i] = pcm16_of(xr[i]);
-        }
-    }
+    if (pcm) pcm16_row<false>(xr, pcm + o0, n, n, first, stride);
     if (wav) {
         float* wr = wav + o0;
         long a0 = (long)(((16 - (((uintptr_t)wr) & 15)) & 15) >> 2);
@@ -762,35 +730,6 @@ __global__ __launch_bounds__(256) void window_scatter_kernel(const float* __rest
             const long i = j < a0 ? j : a1 + (j - a0);
             wr[i] = xr[i];
         }
-    }
-}
-
-// ---- ragged forward: the rows past each clip's end of a flow's x_a plane hold -shift --------------------
-// The front conv applies ActNorm on the fly, (v + shift[tau]) * scale[tau]: a zero in a padded row would reach its +-1 taps
-// as shift * scale, where a clip on its own is zero-padded AFTER ActNorm.  (-s + s) is exactly +0, so with -shift[tau] in
-// those rows every product is an exact zero.  buf [nclip][rows][Ch] fp32 (Ch a power of two), shift [Ch]; the clamping, the
-// grid and the 16-byte stores with dword heads and tails are mask_rows_kernel's.
-__global__ __launch_bounds__(256) void fill_neg_shift_kernel(float* __restrict__ buf, long rows, int Ch,
-                                                             const float* __restrict__ shift, const int* __restrict__ len,
-                                                             int nlen, int spr) {
-    const long c = blockIdx.y;
-    long keep = (long)len[c % nlen] / spr;
-    keep = keep < 0 ? 0 : (keep > rows ? rows : keep);
-    if (keep == rows) return;
-    const size_t row_bytes = (size_t)Ch * 4;
-    const uintptr_t clip = (uintptr_t)buf + (size_t)c * rows * row_bytes;
-    const uintptr_t p0 = clip + (size_t)keep * row_bytes, p1 = clip + (size_t)rows * row_bytes;
-    uintptr_t a0 = (p0 + 15) & ~(uintptr_t)15;
-    if (a0 > p1) a0 = p1;
-    uintptr_t a1 = p1 & ~(uintptr_t)15;
-    if (a1 < a0) a1 = a0;
-    auto val = [&](uintptr_t q) { return -shift[((q - clip) >> 2) & (size_t)(Ch - 1)]; };     // rows start at the clip's base
-    for (uintptr_t q = a0 + ((size_t)blockIdx.x * 256 + threadIdx.x) * 16; q < a1; q += (size_t)gridDim.x * 256 * 16)
-        *(float4*)q = make_float4(val(q), val(q + 4), val(q + 8), val(q + 12));
-    if (blockIdx.x == 0) {
-        const uintptr_t h = p0 + (size_t)threadIdx.x * 4, t = a1 + (size_t)(threadIdx.x - 4) * 4;
-        if (threadIdx.x < 4 && h < a0) *(float*)h = val(h);
-        if (threadIdx.x >= 4 && threadIdx.x < 8 && t < p1) *(float*)t = val(t);
     }
 }
 
@@ -816,8 +755,7 @@ __global__ __launch_bounds__(256) void range_logdet_kernel(const float* __restri
     __shared__ double red[256];
     const long c = blockIdx.y;
     long r0 = off ? (long)off[c] / spr : 0, keep = (long)cnt[c % ncnt] / spr;
-    r0 = r0 < 0 ? 0 : (r0 > rows ? rows : r0);
-    keep = keep < 0 ? 0 : (keep > rows - r0 ? rows - r0 : keep);
+    clamp_core(r0, keep, rows);
     const float* zc = Z + ((size_t)c * rows + (size_t)r0) * 2 * Ch;
     const long stride = (long)gridDim.x * 256, first = (long)blockIdx.x * 256 + threadIdx.x;
     double s = 0.0;
@@ -891,9 +829,7 @@ __global__ __launch_bounds__(256) void ragged_finish_kernel(const float* __restr
                                                             const int* __restrict__ len, float* __restrict__ out) {
     __shared__ double r1[256], r2[256];
     const long c = blockIdx.x, hT = T >> 1;
-    long n = len[c];
-    n = n < 0 ? 0 : (n > T ? T : n);
-    const long hn = n >> 1;
+    const long n = clamp_len(len[c], T), hn = n >> 1;
     double s = 0.0, ld = 0.0;
     for (int q = 0; q < 2; ++q) {
         const float* z = planes + ((size_t)q * nclip + c) * hT;
@@ -942,8 +878,7 @@ __global__ __launch_bounds__(256) void window_sums_kernel(const float* __restric
     __shared__ double r1[256], r2[256];
     const long c = blockIdx.x, hL = L >> 1;
     long off = core_off[c], len = core_len[c];
-    off = off < 0 ? 0 : (off > L ? L : off);
-    len = len < 0 ? 0 : (len > L - off ? L - off : len);
+    clamp_core(off, len, L);
     const long e0 = off >> 1, e1 = (off + len) >> 1;
     double s = 0.0, ld = 0.0, an = 0.0;
     for (int q = 0; q < 2; ++q) {
@@ -990,8 +925,7 @@ __global__ __launch_bounds__(256) void window_latent_kernel(const float* __restr
                                                             const long long* __restrict__ out_off, float* __restrict__ z) {
     const long c = blockIdx.y, hL = L >> 1;
     long off = core_off[c], len = core_len[c];
-    off = off < 0 ? 0 : (off > L ? L : off);
-    len = len < 0 ? 0 : (len > L - off ? L - off : len);
+    clamp_core(off, len, L);
     const float* even = planes + ((size_t)(swapped ? 1 : 0) * n + c) * hL;             // where the even samples are
     const float* odd = planes + ((size_t)(swapped ? 0 : 1) * n + c) * hL;
     float* zr = z + out_off[c];
@@ -1121,10 +1055,7 @@ __global__ __launch_bounds__(256) void ddi_moments_ragged_kernel(const float* __
     const int tid = threadIdx.x, role = blockIdx.y;
     const float* src = role ? xb : xa;
     double* out = part + ((size_t)blockIdx.x * 4 + 2 * role) * Ch;
-    auto keep_of = [&](long c) {
-        const long k = (long)len[c] / spr;
-        return k < 0 ? 0 : (k > rows ? rows : k);
-    };
+    auto keep_of = [&](long c) { return clamp_len((long)len[c] / spr, rows); };
     if (Ch <= 256) {
         const int tau = tid & (Ch - 1), sub = tid / Ch, R = 256 / Ch;
         double s = 0.0, s2 = 0.0;
@@ -1172,10 +1103,7 @@ __global__ void ddi_moments_ragged_finish_kernel(const double* __restrict__ part
         mom[i] = s;
     } else if (i == 4 * Ch) {
         long n = 0;
-        for (long c = 0; c < nclip; ++c) {
-            const long k = (long)len[c] / spr;
-            n += k < 0 ? 0 : (k > rows ? rows : k);
-        }
+        for (long c = 0; c < nclip; ++c) n += clamp_len((long)len[c] / spr, rows);
         mom[i] = (double)n;
     }
 }
@@ -1349,68 +1277,43 @@ void fwn_launch_merge(const float* planes, long B, long T, float* x, hipStream_t
 }
 void fwn_launch_mask_rows(void* base, long nclip, long rows, long row_bytes, const int* len, int nlen, int samples_per_row,
                           hipStream_t st) {
-    // four 16-byte stores per thread if the whole clip were padding; at most ~2048 workgroups over all clips
-    const long want = (rows * row_bytes + 16383) / 16384, cap = nclip < 2048 ? 2048 / nclip : 1;
-    const long gx = want < 1 ? 1 : (want > cap ? cap : want);
-    hipLaunchKernelGGL(mask_rows_kernel, dim3((unsigned)gx, (unsigned)nclip), dim3(256), 0, st, (char*)base, rows, row_bytes, len,
-                       nlen, samples_per_row);
-}
-void fwn_launch_latent_normal(float* z, long B, long T, unsigned long long seed, const unsigned* clip_id, float temp, const int* len,
-                              hipStream_t st) {
-    // write-bound: four 16-byte stores per thread, at most ~2048 workgroups over all clips (fwn_launch_mask_rows)
-    const long want = (T * 4 + 16383) / 16384, cap = B < 2048 ? 2048 / B : 1;
-    const long gx = want < 1 ? 1 : (want > cap ? cap : want);
-    hipLaunchKernelGGL(latent_normal_kernel, dim3((unsigned)gx, (unsigned)B), dim3(256), 0, st, z, T, (unsigned)(seed & 0xffffffffull),
-                       (unsigned)(seed >> 32), clip_id, temp, len);
+    hipLaunchKernelGGL(mask_rows_kernel, row_grid(rows * row_bytes, nclip), dim3(256), 0, st, (char*)base, rows, row_bytes, len, nlen,
+                       samples_per_row);
 }
 void fwn_launch_pcm16(const float* x, short* pcm, long B, long T, const int* len, hipStream_t st) {
-    const long want = (T * 2 + 16383) / 16384, cap = B < 2048 ? 2048 / B : 1;              // four 16-byte stores per thread
-    const long gx = want < 1 ? 1 : (want > cap ? cap : want);
-    hipLaunchKernelGGL(pcm16_kernel, dim3((unsigned)gx, (unsigned)B), dim3(256), 0, st, x, pcm, T, len);
+    hipLaunchKernelGGL(pcm16_kernel, row_grid(T * 2, B), dim3(256), 0, st, x, pcm, T, len);
 }
-// windowed synthesis: the grids of the three launches above them (four 16-byte stores per thread, at most ~2048 workgroups)
 void fwn_launch_latent_normal_at(float* z, long n, long L, unsigned long long seed, const unsigned* clip_id, const long long* start,
                                  float temp, const int* len, hipStream_t st) {
-    const long want = (L * 4 + 16383) / 16384, cap = n < 2048 ? 2048 / n : 1;
-    const long gx = want < 1 ? 1 : (want > cap ? cap : want);
-    hipLaunchKernelGGL(latent_normal_at_kernel, dim3((unsigned)gx, (unsigned)n), dim3(256), 0, st, z, L, (unsigned)(seed & 0xffffffffull),
+    hipLaunchKernelGGL(latent_normal_at_kernel, row_grid(L * 4, n), dim3(256), 0, st, z, L, (unsigned)(seed & 0xffffffffull),
                        (unsigned)(seed >> 32), clip_id, start, temp, len);
 }
 void fwn_launch_window_gather(const float* src, const long long* src_row, long row_floats, float* dst, long n, long count,
                               hipStream_t st) {
-    const long want = (count * 4 + 16383) / 16384, cap = n < 2048 ? 2048 / n : 1;
-    const long gx = want < 1 ? 1 : (want > cap ? cap : want);
-    hipLaunchKernelGGL(window_gather_kernel, dim3((unsigned)gx, (unsigned)n), dim3(256), 0, st, src, src_row, row_floats, dst, count);
+    hipLaunchKernelGGL(window_gather_kernel, row_grid(count * 4, n), dim3(256), 0, st, src, src_row, row_floats, dst, count);
 }
 void fwn_launch_window_scatter(const float* x, long n, long L, const int* core_off, const int* core_len, const long long* out_off,
                                short* pcm, float* wav, hipStream_t st) {
-    const long want = (L * (wav ? 4 : 2) + 16383) / 16384, cap = n < 2048 ? 2048 / n : 1;
-    const long gx = want < 1 ? 1 : (want > cap ? cap : want);
-    hipLaunchKernelGGL(window_scatter_kernel, dim3((unsigned)gx, (unsigned)n), dim3(256), 0, st, x, L, core_off, core_len, out_off, pcm,
+    hipLaunchKernelGGL(window_scatter_kernel, row_grid(L * (wav ? 4 : 2), n), dim3(256), 0, st, x, L, core_off, core_len, out_off, pcm,
                        wav);
 }
 void fwn_launch_corpus_draw(const float* audio, const float* mel, const long long* frame_off, long n_utt, int hop, int num_mels,
                             int unit_frames, long B, long F, unsigned long long seed, unsigned stream_id, unsigned long long* counter,
                             float* x, float* c, int* len, int* picks, hipStream_t st) {
-    // the longer of the two rows at four 16-byte stores per thread, at most ~2048 workgroups over all slots (fwn_launch_mask_rows)
-    const long widest = F * (hop > num_mels ? hop : num_mels);
-    const long want = (widest * 4 + 16383) / 16384, cap = B < 2048 ? 2048 / B : 1;
-    const long gx = want < 1 ? 1 : (want > cap ? cap : want);
-    hipLaunchKernelGGL(corpus_draw_kernel, dim3((unsigned)gx, (unsigned)B), dim3(256), 0, st, audio, mel, frame_off,
+    // sized for the longer of the two rows
+    hipLaunchKernelGGL(corpus_draw_kernel, row_grid(F * (hop > num_mels ? hop : num_mels) * 4, B), dim3(256), 0, st, audio, mel, frame_off,
                        (unsigned long long)n_utt, hop, num_mels, unit_frames, F, (unsigned)(seed & 0xffffffffull), (unsigned)(seed >> 32),
                        stream_id, counter, x, c, len, picks);
     hipLaunchKernelGGL(corpus_advance_kernel, dim3(1), dim3(64), 0, st, counter);
 }
 void fwn_launch_fill_neg_shift(float* plane, long nclip, long rows, int Ch, const float* shift, const int* len, int nlen,
                                int samples_per_row, hipStream_t st) {
-    const long want = (rows * Ch * 4 + 16383) / 16384, cap = nclip < 2048 ? 2048 / nclip : 1;       // as fwn_launch_mask_rows
-    const long gx = want < 1 ? 1 : (want > cap ? cap : want);
-    hipLaunchKernelGGL(fill_neg_shift_kernel, dim3((unsigned)gx, (unsigned)nclip), dim3(256), 0, st, plane, rows, Ch, shift, len, nlen,
+    hipLaunchKernelGGL(fill_neg_shift_kernel, row_grid(rows * Ch * 4, nclip), dim3(256), 0, st, plane, rows, Ch, shift, len, nlen,
                        samples_per_row);
 }
-// slots per clip and flow: up to 32 chunk sums (about 2048 workgroups over all clips at most) and the ActNorm term
+// slots per clip and flow: up to 32 chunk sums (row_grid's cap over all clips) and the ActNorm term
 int fwn_ragged_logdet_nslot(long nclip) {
-    const long cap = nclip < 2048 ? 2048 / nclip : 1;
+    const long cap = row_cap(nclip);
     return (int)(cap > 32 ? 32 : cap) + 1;
 }
 void fwn_launch_range_logdet(const float* Z, long nclip, long rows, int Ch, const float* ez, const float* an, const int* off,
@@ -1424,7 +1327,7 @@ void fwn_launch_ragged_finish(const float* planes, long nclip, long T, const dou
     hipLaunchKernelGGL(ragged_finish_kernel, dim3((unsigned)nclip), dim3(256), 0, st, planes, nclip, T, acc, nflows, n_flow,
                        fwn_ragged_logdet_nslot(nclip), len, out2B);
 }
-// windowed forward: one workgroup per window for its partial sums, window_scatter's grid for the latent, one lane per clip for
+// windowed forward: one workgroup per window for its partial sums, row_grid for the latent, one lane per clip for
 // the finish
 void fwn_launch_window_sums(const float* planes, long n, long L, const int* core_off, const int* core_len, const double* acc,
                             int nflows, int n_flow, const int* slot, double* out, hipStream_t st) {
@@ -1433,10 +1336,7 @@ void fwn_launch_window_sums(const float* planes, long n, long L, const int* core
 }
 void fwn_launch_window_latent(const float* planes, long n, long L, int swapped, const int* core_off, const int* core_len,
                               const long long* out_off, float* z, hipStream_t st) {
-    const long want = (L * 4 + 16383) / 16384, cap = n < 2048 ? 2048 / n : 1;
-    const long gx = want < 1 ? 1 : (want > cap ? cap : want);
-    hipLaunchKernelGGL(window_latent_kernel, dim3((unsigned)gx, (unsigned)n), dim3(256), 0, st, planes, n, L, swapped, core_off, core_len,
-                       out_off, z);
+    hipLaunchKernelGGL(window_latent_kernel, row_grid(L * 4, n), dim3(256), 0, st, planes, n, L, swapped, core_off, core_len, out_off, z);
 }
 void fwn_launch_windows_finish(const double* part, const int* slot0, const int* nwin, long nclip, float* out2B, hipStream_t st) {
     hipLaunchKernelGGL(windows_finish_kernel, dim3((unsigned)((nclip + 63) / 64)), dim3(64), 0, st, part, slot0, nwin, nclip, out2B);

@@ -158,15 +158,14 @@ void fwn_launch_merge(const float* planes, long B, long T, float* x, hipStream_t
 // rows past a clip's own length); len is read on the device and clamped to the buffer.  base and row_bytes: multiples of 4.
 void fwn_launch_mask_rows(void* base, long nclip, long rows, long row_bytes, const int* len, int nlen, int samples_per_row,
                           hipStream_t st);
-// synthesis (aux_kernels.hip): z [B][T] = temp * N(0,1), Philox4x32-10 keyed by (seed, clip_id[b]) (NULL: clip b is b), and
-// fp32 [B][T] -> int16 PCM; len (may be NULL) is read on the device and clamped to [0, T]: +0 / 0 from there on.
-void fwn_launch_latent_normal(float* z, long B, long T, unsigned long long seed, const unsigned* clip_id, float temp, const int* len,
-                              hipStream_t st);
+// synthesis (aux_kernels.hip): fp32 [B][T] -> int16 PCM; len (may be NULL) is read on the device and clamped to [0, T]: 0 from
+// there on.
 void fwn_launch_pcm16(const float* x, short* pcm, long B, long T, const int* len, hipStream_t st);
-// windowed synthesis (aux_kernels.hip; fwn.h has the contracts): row r of z [n][L] = samples start[r] .. start[r] + L of clip
-// clip_id[r]'s latent stream; row r of dst [n][count] = count floats of src from src_row[r] * row_floats; the core
-// [core_off[r], core_off[r] + core_len[r]) of row r of x [n][L] -> pcm + out_off[r] (int16) and / or wav + out_off[r] (fp32).
-// Every table is read on the device.
+// synthesis, whole clips and windows (aux_kernels.hip; fwn.h has the contracts): row r of z [n][L] = temp * N(0,1), samples
+// start[r] .. start[r] + L (start NULL: from 0) of the Philox4x32-10 stream keyed by (seed, clip_id[r]) (NULL: clip r is r),
+// +0 from len[r] on (may be NULL; clamped to [0, L]); row r of dst [n][count] = count floats of src from src_row[r] *
+// row_floats; the core [core_off[r], core_off[r] + core_len[r]) of row r of x [n][L] -> pcm + out_off[r] (int16) and / or
+// wav + out_off[r] (fp32).  Every table is read on the device.
 void fwn_launch_latent_normal_at(float* z, long n, long L, unsigned long long seed, const unsigned* clip_id, const long long* start,
                                  float temp, const int* len, hipStream_t st);
 void fwn_launch_window_gather(const float* src, const long long* src_row, long row_floats, float* dst, long n, long count,

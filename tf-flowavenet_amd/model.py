@@ -144,21 +144,27 @@ class FloWaveNet:
         (``reverse(..., lengths=)``) keeps a workspace of its own: it also holds the masked copy of the mel.  So does a
         ragged forward (``ragged="forward"``): one flow's ZeroConv output and the per-clip log-det sums on top of that; and a
         ragged init (``ragged="init"``): the chunk sums of the masked moments on top of those."""
+        name = {"forward": "fwn_ragged_forward_workspace_bytes", "init": "fwn_ragged_init_workspace_bytes"}.get(
+            ragged, "fwn_ragged_workspace_bytes") if ragged else "fwn_workspace_bytes"
+        return self._cached_workspace(self._ws, self._ws_key(b, t, ragged), name, (b, t), lambda: self._keep_shape(b, t))
+
+    def _cached_workspace(self, cache, key, name, args, evict):
+        """``cache[key]`` as (256-byte aligned pointer, bytes from there).  A missing entry is allocated: ``lib.<name>(model,
+        *args)`` bytes (0 is the library's refusal of the shape) and 256 to align in, after ``evict()`` has made room in the cache."""
         import torch
-        key = self._ws_key(b, t, ragged)
-        ws = self._ws.get(key)
+        ws = cache.get(key)
         if ws is None:
-            name = {"forward": "fwn_ragged_forward_workspace_bytes", "init": "fwn_ragged_init_workspace_bytes"}.get(
-                ragged, "fwn_ragged_workspace_bytes") if ragged else "fwn_workspace_bytes"
-            n = getattr(self._lib, name)(C.byref(self._packed.model_desc), b, t)
+            n = getattr(self._lib, name)(C.byref(self._packed.model_desc), *args)
             if n == 0:
                 _lib.check(-1, name)
-            for k in [k for k in self._ws if k[:2] != (b, t)]:
-                del self._ws[k]   # keep only the current shape's workspaces
-            ws = torch.empty(n + 256, dtype=torch.uint8, device=self._device)
-            self._ws[key] = ws
+            evict()
+            ws = cache[key] = torch.empty(n + 256, dtype=torch.uint8, device=self._device)
         off = (-ws.data_ptr()) % 256
         return ws.data_ptr() + off, ws.numel() - off
+
+    def _keep_shape(self, b, t):
+        for k in [k for k in self._ws if k[:2] != (b, t)]:
+            del self._ws[k]   # keep only the current shape's workspaces
 
     def _ws_key(self, b, t, ragged=False):
         return (b, t, self._stream()) + ((("ragged", ragged) if ragged in ("forward", "init") else ("ragged",)) if ragged else ())
@@ -210,11 +216,9 @@ class FloWaveNet:
 
     def _forward_ragged(self, b, t, x32, c32, return_z, lengths):
         import torch
-        if self._gate_fp8:
-            raise ValueError("a gate_fp8 model takes no lengths: the e4m3 copies of h are not masked")
         if self._init:
             raise ValueError("init=True takes no lengths: the data-dependent ActNorm init of a ragged batch is forward_init(x, c, lengths)")
-        lens = torch.tensor(self._check_lengths(lengths, b, t), dtype=torch.int32).to(self._device)
+        lens = self._device_lengths(lengths, b, t)
         wsp, wsn = self._workspace(b, t, ragged="forward")
         out = torch.empty(2, b, dtype=torch.float32, device=self._device)
         zp = torch.empty(2, b, t // 2, dtype=torch.float32, device=self._device) if return_z else None
@@ -235,9 +239,7 @@ class FloWaveNet:
         import torch
         self._check_g(g)
         b, t, x32, c32 = self._prep(x, c, "x")
-        if self._gate_fp8:
-            raise ValueError("a gate_fp8 model takes no lengths: the e4m3 copies of h are not masked")
-        lens = torch.tensor(self._check_lengths(lengths, b, t), dtype=torch.int32).to(self._device)
+        lens = self._device_lengths(lengths, b, t)
         wsp, wsn = self._workspace(b, t, ragged="init")
         out = torch.empty(2, b, dtype=torch.float32, device=self._device)
         zp = torch.empty(2, b, t // 2, dtype=torch.float32, device=self._device) if return_z else None
@@ -294,6 +296,13 @@ class FloWaveNet:
         """``lengths`` of a ragged ``reverse`` / ``forward`` -> list of B ints, validated on the host before anything is launched."""
         return check_lengths(lengths, b, t, self.hop, self._hparams.n_block)
 
+    def _device_lengths(self, lengths, b, t, fp8_ok=False):
+        """``lengths`` -> the int32 device tensor a ragged pass reads; a ``gate_fp8`` model has no such pass."""
+        import torch
+        if self._gate_fp8 and not fp8_ok:
+            raise ValueError("a gate_fp8 model takes no lengths: the e4m3 copies of h are not masked")
+        return torch.tensor(self._check_lengths(lengths, b, t), dtype=torch.int32).to(self._device)
+
     def reverse(self, z, c, g=None, dtype=None, lengths=None):
         """z [B,T,1], c [B,T/hop,num_mels] -> x [B,T,1] (model.py:350-396).  fp32 unless ``dtype`` is given: a torch dtype, or
         "hparams" for the reference's return type, ``hparams.dtype`` (float16 / bfloat16 / float32; model.py:356-357,396).
@@ -308,10 +317,7 @@ class FloWaveNet:
         if dtype == "hparams":
             dtype = {"float16": torch.float16, "bfloat16": torch.bfloat16, "float32": torch.float32}[str(self._hparams.dtype).replace("tf.", "")]
         b, t, z32, c32 = self._prep(z, c, "z")
-        if lengths is not None:
-            if self._gate_fp8:
-                raise ValueError("a gate_fp8 model takes no lengths: the e4m3 copies of h are not masked")
-            lens = torch.tensor(self._check_lengths(lengths, b, t), dtype=torch.int32).to(self._device)
+        lens = None if lengths is None else self._device_lengths(lengths, b, t)
         wsp, wsn = self._workspace(b, t, ragged=lengths is not None)
         x = torch.empty(b, t, 1, dtype=torch.float32, device=self._device)
         if lengths is None:
@@ -354,7 +360,7 @@ class FloWaveNet:
         if b < 1 or t < 1:
             raise ValueError("b and t must be positive, got %d, %d" % (b, t))
         ids = self._clip_ids(clip_ids, b)
-        lens = None if lengths is None else torch.tensor(self._check_lengths(lengths, b, t), dtype=torch.int32).to(self._device)
+        lens = None if lengths is None else self._device_lengths(lengths, b, t, fp8_ok=True)
         z = torch.empty(b, t, 1, dtype=torch.float32, device=self._device)
         rc = self._lib.fwn_latent_normal(z.data_ptr(), b, t, int(seed) % (1 << 64), None if ids is None else ids.data_ptr(),
                                          float(self._hparams.temp if temp is None else temp),
@@ -377,11 +383,7 @@ class FloWaveNet:
             raise ValueError("T=%d must be a positive multiple of 2^n_block=%d (model.py:226)" % (t, 1 << hp.n_block))
         c32 = c.to(device=torch.device(self._device), dtype=torch.float32).contiguous()
         ids = self._clip_ids(clip_ids, b)
-        lens = None
-        if lengths is not None:
-            if self._gate_fp8:
-                raise ValueError("a gate_fp8 model takes no lengths: the e4m3 copies of h are not masked")
-            lens = torch.tensor(self._check_lengths(lengths, b, t), dtype=torch.int32).to(self._device)
+        lens = None if lengths is None else self._device_lengths(lengths, b, t)
         wsp, wsn = self._synth_workspace(b, t, lens is not None)
         pcm = torch.empty(b, t, dtype=torch.int16, device=self._device)
         wav = torch.empty(b, t, 1, dtype=torch.float32, device=self._device) if return_wav else None
@@ -396,19 +398,8 @@ class FloWaveNet:
 
     def _synth_workspace(self, b, t, ragged):
         """``_workspace`` for ``synthesize``: the inverse pass's scratch with z and the fp32 waveform behind it."""
-        import torch
-        key = (b, t, self._stream(), "synth", bool(ragged))
-        ws = self._ws.get(key)
-        if ws is None:
-            n = self._lib.fwn_synthesize_workspace_bytes(C.byref(self._packed.model_desc), b, t, 1 if ragged else 0)
-            if n == 0:
-                _lib.check(-1, "fwn_synthesize_workspace_bytes")
-            for k in [k for k in self._ws if k[:2] != (b, t)]:
-                del self._ws[k]   # keep only the current shape's workspaces
-            ws = torch.empty(n + 256, dtype=torch.uint8, device=self._device)
-            self._ws[key] = ws
-        off = (-ws.data_ptr()) % 256
-        return ws.data_ptr() + off, ws.numel() - off
+        return self._cached_workspace(self._ws, (b, t, self._stream(), "synth", bool(ragged)), "fwn_synthesize_workspace_bytes",
+                                      (b, t, 1 if ragged else 0), lambda: self._keep_shape(b, t))
 
     # ------------------------------------------------------------------ windowed passes (windowed.py drives them)
     def _window_workspace(self, kind, n, length):
@@ -417,21 +408,16 @@ class FloWaveNet:
         every tail's ZeroConv output, the per-window sums and the windows' audio and mel rows).  A cache of its own, keyed by shape and stream: a
         long clip alternates between a few shapes (first, middle, end windows) and ``_workspace`` keeps one shape only.  The
         eight most recently used are kept; a size depends on (n, length) alone, never on a clip's length."""
-        import torch
         key = (kind, n, length, self._stream())
-        ws = self._wws.pop(key, None)
-        if ws is None:
-            name = {"synth": "fwn_synthesize_windows_workspace_bytes", "forward": "fwn_forward_windows_workspace_bytes"}.get(
-                kind, "fwn_workspace_bytes")
-            nbytes = getattr(self._lib, name)(C.byref(self._packed.model_desc), n, length)
-            if nbytes == 0:
-                _lib.check(-1, name)
+        if key in self._wws:
+            self._wws[key] = self._wws.pop(key)      # re-inserted last: the dict's order is the order of use
+        name = {"synth": "fwn_synthesize_windows_workspace_bytes", "forward": "fwn_forward_windows_workspace_bytes"}.get(
+            kind, "fwn_workspace_bytes")
+
+        def evict():
             while len(self._wws) >= 8:
                 del self._wws[next(iter(self._wws))]
-            ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=self._device)
-        self._wws[key] = ws                  # (re-)inserted last: the dict's order is the order of use
-        off = (-ws.data_ptr()) % 256
-        return ws.data_ptr() + off, ws.numel() - off
+        return self._cached_workspace(self._wws, key, name, (n, length), evict)
 
     # the device calls of a group of windows, methods of the model: what a stand-in model under a stream replaces
     _windows_call = windowed.synthesize_windows_call
