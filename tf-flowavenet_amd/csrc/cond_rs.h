@@ -18,20 +18,7 @@
 // The product is NOT transposed (rows on accumulator rows, channels on lanes): a store instruction writes 128 contiguous bytes
 // of two P rows.
 #pragma once
-#include "gate_rs.h"        // rs_wload, rs_vmwait, rs_static_for
-
-// one 16-byte LDS-DMA per lane issued from inline asm (tail_rs.h's trs_dma16: issued through the builtin, hipcc drains vmcnt
-// in front of the next LDS access): M0 = the LDS address, saved and restored inside the statement
-__device__ __forceinline__ void crs_dma16(u32x4 srd, uint32_t voff, uint32_t lds_addr) {
-    uint32_t keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 4\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(srd), "s"(lds_addr) : "memory");
-}
-__device__ __forceinline__ u32x4 crs_srd(const void* p, uint32_t bytes) {
-    const unsigned long long b = (unsigned long long)(uintptr_t)p;
-    return u32x4{(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)b), (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(b >> 32)) & 0xffffu,
-                 (uint32_t)__builtin_amdgcn_readfirstlane((int)bytes), 0x00020000u};
-}
+#include "reg_stream.h"     // the shared primitives (rs_srd, rs_dma16, rs_wload, the counted waits, VmWalk) and their rules
 
 struct CondRsArgs {
     const bf16* ca;         // [M][cin]
@@ -55,24 +42,24 @@ struct CrsCount {
     static constexpr int prologue = AHEAD * PPW + 2 * (R - 1);      // operations of the prologue: what is younger than anything issued in front of it
     // ops issued after the second load of W(g) when k-step g waits for it (kind 0) / after the second piece of item i at its barrier (kind 1)
     static constexpr int after(int kind, int key) {
-        int count = -1;
-#define CRS_OP(k_, a_) do { if (count >= 0) ++count; if (kind == (k_) && key == (a_)) count = 0; } while (0)
-        for (int i = 0; i < AHEAD; ++i) { for (int j = 0; j < PPW - 1; ++j) CRS_OP(2, -1); CRS_OP(1, i); }
-        for (int g = 0; g < R - 1; ++g) { CRS_OP(2, -1); CRS_OP(0, g); }
-        for (int i = 0; i < 64; ++i)
+        VmWalk w;
+        auto pieces = [&](int i) { for (int j = 0; j < PPW; ++j) w.op(kind == 1 && key == i && j == PPW - 1); };
+        auto loads = [&](int g) { w.op(); w.op(kind == 0 && key == g); };
+        for (int i = 0; i < AHEAD; ++i) pieces(i);
+        for (int g = 0; g < R - 1; ++g) loads(g);
+        for (int i = 0; i < 64 && !w.done; ++i)
             for (int l = 0; l < 4; ++l) {
                 const int g = 4 * i + l;
-                if (l == 0 && kind == 1 && key == i) return count;
-                if (kind == 0 && key == g) return count;
-                if (l == 0) { for (int j = 0; j < PPW - 1; ++j) CRS_OP(2, -1); CRS_OP(1, i + AHEAD); }
-                CRS_OP(2, -1); CRS_OP(0, g + R - 1);
+                w.query(l == 0 && kind == 1 && key == i);
+                w.query(kind == 0 && key == g);
+                if (l == 0) pieces(i + AHEAD);
+                loads(g + R - 1);
             }
-#undef CRS_OP
-        return -1;
+        return w.result;
     }
-    // the count the kernel uses at position pos (0 .. 7) of a pair of items: one statement per position whatever the pair (a
-    // branch on "first pair" around an asm wait that names ring registers is the persistent gate's race: gate_rs.h), so the
-    // smaller of the first pair's and the steady state's value
+    // the count the kernel uses at position pos (0 .. 7) of a pair of items: one statement per position whatever the pair (no
+    // branch around a wait that names ring registers: reg_stream.h, rs_wwait), so the smaller of the first pair's and the steady
+    // state's value
     static constexpr int wait_kstep(int pos) {
         int n = after(0, pos);
         for (int pr = 1; pr < 6; ++pr) { const int m = after(0, 8 * pr + pos); if (m < n) n = m; }
@@ -87,19 +74,6 @@ struct CrsCount {
         return true;
     }
 };
-
-template <int N>
-__device__ __forceinline__ void crs_wwait2(bf16x8& a, bf16x8& b) {
-    static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit counter");
-    asm volatile("s_waitcnt vmcnt(%2)" : "+v"(a), "+v"(b) : "n"(N) : "memory");
-}
-template <int I, int R>
-__device__ __forceinline__ void crs_touch_all(bf16x8 (&wq)[R][2]) {
-    if constexpr (I < R) {
-        asm volatile("" : "+v"(wq[I][0]), "+v"(wq[I][1]));
-        crs_touch_all<I + 1, R>(wq);
-    }
-}
 
 template <int MT, int R = 8>
 __global__ __launch_bounds__(512) void cond_rs_kernel(CondRsArgs p) {
@@ -124,21 +98,18 @@ __global__ __launch_bounds__(512) void cond_rs_kernel(CondRsArgs p) {
     const int npairs = (q1 - q0 + 1) >> 1;               // items past q1 are phantoms: zero pieces, out-of-range (zero) weights
 
     // ---- DMA pieces: piece j of this wave = slot rows 8 (wave + 8 j) .. + 7 of item i (chunk q0 + i) in slot i % 4
-    const u32x4 srd_a = crs_srd(ca, (uint32_t)((size_t)M * cin * 2));
+    const u32x4 srd_a = rs_srd(ca, (uint32_t)((size_t)M * cin * 2));
     auto issue_piece = [&](int i, int j) {
         const int pi = wave + 8 * j;
         const int jrow = 8 * pi + (lane >> 3);
         const int c = (lane & 7) ^ ((jrow >> 1) & 7);
         const int col = (q0 + i) * 64 + c * 8;
         const bool ok = (jrow < BM) & (m0 + jrow < M) & (col < cin) & (q0 + i < q1);
-        crs_dma16(srd_a, ok ? (uint32_t)((m0 + jrow) * cin + col) * 2u : FWN_OOB, lds0 + (uint32_t)((i & 3) * SLOT + pi * 1024));
+        rs_dma16(srd_a, ok ? (uint32_t)((m0 + jrow) * cin + col) * 2u : FWN_OOB, lds0 + (uint32_t)((i & 3) * SLOT + pi * 1024));
     };
     // ---- this wave's weight stream from k-step 4 q0 on: k-step g (relative) -> ring stage g % 8, two fragments
     const int nks = p.kcpad / 16;
-    const unsigned long long wbase = (unsigned long long)(uintptr_t)p.Ws + ((unsigned long long)(z * 8 + wave) * nks + (unsigned long long)q0 * 4) * 2048ull;
-    const u32x4 wsrd = {(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)wbase),
-                        (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(wbase >> 32)) & 0xffffu,
-                        (uint32_t)__builtin_amdgcn_readfirstlane((q1 - q0) * 4 * 2048), 0x00020000u};
+    const u32x4 wsrd = rs_srd(p.Ws, (uint32_t)((q1 - q0) * 4 * 2048), ((unsigned long long)(z * 8 + wave) * nks + (unsigned long long)q0 * 4) * 2048ull);
     const uint32_t wl = (uint32_t)lane * 16u;
     bf16x8 wq[R][2];
     // k-step (8 pr + G): its byte offset = pr * 16384 + G * 2048: a 4-KiB window in the scalar offset, the rest an immediate
@@ -182,7 +153,7 @@ __global__ __launch_bounds__(512) void cond_rs_kernel(CondRsArgs p) {
                 if (i == 0) rs_vmwait<C::wait_item0>(); else rs_vmwait<C::wait_item>();
                 FWN_RING_BARRIER();
             }
-            crs_wwait2<C::wait_kstep(pos)>(wq[pos][0], wq[pos][1]);
+            rs_wwait<C::wait_kstep(pos)>(wq[pos][0], wq[pos][1]);
             if constexpr (l == 0) {
 #pragma unroll
                 for (int mi = 0; mi < MT; ++mi) hf[mi] = *(const bf16x8*)(la + mi * 4096 + xv);
@@ -206,7 +177,7 @@ __global__ __launch_bounds__(512) void cond_rs_kernel(CondRsArgs p) {
     // are anyone else's
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
-    crs_touch_all<0, R>(wq);
+    rs_touch_all(wq);
 
     // ---- epilogue: register r of tile (mi, cg) = row m0 + 32 mi + acc_row_c(r) + 4 lh, column 64 wave + 32 cg + lr
     float* out = (sp == 0 ? p.P : p.part + (size_t)(sp - 1) * p.part_stride) + (size_t)z * M * 512;
@@ -242,15 +213,6 @@ struct GateHsArgs {
     bf16* o;                // [M][256]
     int M, Ti, dil;
 };
-__device__ __forceinline__ void crs_fload(float& dst, u32x4 srd, uint32_t voff) {
-    asm volatile("s_nop 4\n\tbuffer_load_dword %0, %1, %2, 0 offen" : "=v"(dst) : "v"(voff), "s"(srd) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void crs_fwait2(float& a, float& b) {
-    static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit counter");
-    asm volatile("s_waitcnt vmcnt(%2)" : "+v"(a), "+v"(b) : "n"(N) : "memory");
-}
-
 template <int MT, int NW, int R = 8>
 __global__ __launch_bounds__(64 * NW, 8 / NW) void gate_hs_kernel(GateHsArgs p) {      // two waves per SIMD either way: two 4-wave workgroups share a CU
     constexpr int PPW = NW == 8 ? 2 : MT;                // pieces per wave and item: 8 NW PPW slot rows >= 32 MT
@@ -274,13 +236,13 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void gate_hs_kernel(GateHsArgs p) 
     const int M = p.M, Ti = p.Ti, dil = p.dil, m0 = rt * BM;
 
     // ---- bias: the first two vector-memory operations of the wave
-    const u32x4 sb = crs_srd(p.bias, 512u * 4u);
+    const u32x4 sb = rs_srd(p.bias, 512u * 4u);
     float b0, b1;
-    crs_fload(b0, sb, (uint32_t)(wv * 64 + lr) * 4u);
-    crs_fload(b1, sb, (uint32_t)(wv * 64 + 32 + lr) * 4u);
+    rs_dload(b0, sb, (uint32_t)(wv * 64 + lr) * 4u);
+    rs_dload(b1, sb, (uint32_t)(wv * 64 + 32 + lr) * 4u);
 
     // ---- DMA pieces: piece j of this wave = slot rows 8 (wave + NW j) .. + 7 of item i in slot i % 4
-    const u32x4 srd_a = crs_srd(p.h, (uint32_t)((size_t)M * FWN_HID * 2));
+    const u32x4 srd_a = rs_srd(p.h, (uint32_t)((size_t)M * FWN_HID * 2));
     int tq[PPW];                                          // time index within its clip of this lane's row of piece j
 #pragma unroll
     for (int j = 0; j < PPW; ++j) tq[j] = (m0 + 8 * (wave + NW * j) + (lane >> 3)) % Ti;
@@ -290,15 +252,12 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void gate_hs_kernel(GateHsArgs p) 
         const int c = (lane & 7) ^ ((jrow >> 1) & 7);
         const int shift = ((i >> 2) - 1) * dil;
         const bool ok = (i < NITEM) & (jrow < BM) & (m0 + jrow < M) & ((unsigned)(tq[j] + shift) < (unsigned)Ti);
-        crs_dma16(srd_a, ok ? (uint32_t)((m0 + jrow + shift) * FWN_HID + (i & 3) * 64 + c * 8) * 2u : FWN_OOB,
+        rs_dma16(srd_a, ok ? (uint32_t)((m0 + jrow + shift) * FWN_HID + (i & 3) * 64 + c * 8) * 2u : FWN_OOB,
                   lds0 + (uint32_t)((i & 3) * SLOT + pi * 1024));
     };
     // ---- this wave's weight stream: k-step g -> ring stage g % 8, two fragments; past k-step 47 out of range (zeros)
     constexpr int NKS = NITEM * 4;
-    const unsigned long long wbase = (unsigned long long)(uintptr_t)p.Ws + (unsigned long long)wv * NKS * 2048ull;
-    const u32x4 wsrd = {(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)wbase),
-                        (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(wbase >> 32)) & 0xffffu,
-                        (uint32_t)(NKS * 2048), 0x00020000u};
+    const u32x4 wsrd = rs_srd(p.Ws, (uint32_t)(NKS * 2048), (unsigned long long)wv * NKS * 2048ull);
     const uint32_t wl = (uint32_t)lane * 16u;
     bf16x8 wq[R][2];
     auto issue_w = [&](auto G, auto F, int pairbase) {
@@ -316,7 +275,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void gate_hs_kernel(GateHsArgs p) 
         issue_w(G, std::integral_constant<int, 0>{}, 0);
         issue_w(G, std::integral_constant<int, 1>{}, 0);
     });
-    crs_fwait2<C::prologue>(b0, b1);                      // everything younger than the bias loads is the prologue
+    rs_wwait<C::prologue>(b0, b1);                      // everything younger than the bias loads is the prologue
 
     f32x16 acc[MT][2];
 #pragma unroll
@@ -341,7 +300,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void gate_hs_kernel(GateHsArgs p) 
                 if (i == 0) rs_vmwait<C::wait_item0>(); else rs_vmwait<C::wait_item>();
                 FWN_RING_BARRIER();
             }
-            crs_wwait2<C::wait_kstep(pos)>(wq[pos][0], wq[pos][1]);
+            rs_wwait<C::wait_kstep(pos)>(wq[pos][0], wq[pos][1]);
             if constexpr (l == 0) {
 #pragma unroll
                 for (int mi = 0; mi < MT; ++mi) hf[mi] = *(const bf16x8*)(la + mi * 4096 + xv);
@@ -364,7 +323,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void gate_hs_kernel(GateHsArgs p) 
     // are anyone else's; the P loads below are the compiler's own, with nothing of ours in flight
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
-    crs_touch_all<0, R>(wq);
+    rs_touch_all(wq);
 
     // ---- epilogue (GateProb::epilogue_impl's hoisted-P arm, the same expression on the same pairs): register r of tile
     // (mi, cg) = row m0 + 32 mi + acc_row_c(r) + 4 lh, packed column 64 wv + 32 cg + lr = filter | gate of channel 32 wv + lr

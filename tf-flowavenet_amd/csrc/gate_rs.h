@@ -26,8 +26,7 @@
 // zero rows, the zero row of the clip mask among them) are issued behind barrier i - 2 (which proves the laggers have
 // left item i - 4) and every wave waits for its own pieces of item i before it arrives at barrier i.
 #pragma once
-#include "gemm_ring.h"
-#include <type_traits>
+#include "reg_stream.h"     // the shared primitives (rs_srd, rs_wload, the counted waits, rs_touch_all, rs_static_for, VmWalk) and their rules
 
 // MT: 32-row time tiles per wave (8: 256-row workgroup tiles; 4: 128-row tiles for row counts at which 256-row tiles would
 // leave CUs empty; 2: 64-row tiles, round 6 - block 3 of the 8-clip pass, 8 064 rows x cin 640, where the 128 x 128 tap-sharing
@@ -62,33 +61,6 @@ struct GateRsArgs {
 #define RS_STAMP_RT(i) do { } while (0)
 #endif
 
-// one 16-byte load per lane, hidden from hipcc's wait bookkeeping; the caller counts vmcnt.
-// * A BUFFER load (MUBUF), like the LDS-DMA pieces and the epilogue stores: a counted s_waitcnt vmcnt(N) is only a wait
-//   for a particular operation if the operations retire in issue order, and that holds among MUBUF operations.  The first
-//   persistent form of this kernel loaded the weights with global_load_dwordx4 (the FLAT family, segment global): with
-//   out-of-range pieces (which complete at once) and stores between the loads, ~40 % of the overlapped steps came back
-//   wrong while every wait had at least its static count of younger operations in program order (FWN_RS_CHECK build):
-//   younger MUBUF operations were retiring ahead of older global loads.  (The guide's "flat_*: out of order".)
-// * s_nop 4: the descriptor and the offset are scalar arithmetic on kernel arguments, but under SGPR pressure hipcc parks
-//   scalars in VGPR lanes and brings them back with v_readlane_b32 right in front of the statement - a VALU write of an
-//   SGPR that a VMEM instruction reads needs 5 wait states, and hipcc pads nothing inside an asm (guide section 5.7 item 2):
-//   without the pad the NKC = 10 instantiation loaded through garbage bases (memory access faults at random addresses).
-template <int OFF>
-__device__ __forceinline__ void rs_wload(bf16x8& dst, u32x4 srd, uint32_t soff, uint32_t voff) {
-    static_assert(OFF >= 0 && OFF < 4096, "12-bit unsigned immediate");
-    asm volatile("s_nop 4\n\tbuffer_load_dwordx4 %0, %1, %2, %3 offen offset:%4" : "=v"(dst) : "v"(voff), "s"(srd), "s"(soff), "i"(OFF) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void rs_wwait(bf16x8& a) {
-    static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit counter");
-    asm volatile("s_waitcnt vmcnt(%1)" : "+v"(a) : "n"(N) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void rs_vmwait() {
-    static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit counter");
-    asm volatile("s_waitcnt vmcnt(%0)" : : "n"(N) : "memory");
-}
-
 // tanh(f) sigmoid(g) from the exponents u = -2 log2(e) f, v = -log2(e) g the accumulators hold (common.h gated_unit2):
 // a = 2^u, b = 2^v -> (1 - a) / ((1 + a)(1 + b)).  Scalar fp32 on purpose: this epilogue is paid for at one or two waves
 // per SIMD, where every v_pk_*_f32 costs the issue time of about four plain VALU instructions (guide, price of fillers),
@@ -100,25 +72,6 @@ __device__ __forceinline__ float rs_gated1(float u, float v) {
     const float r = __builtin_amdgcn_rcpf((1.0f + a) * (1.0f + b));
     return (1.0f - a) * r;
 }
-
-// every ring stage made opaque at this point (behind a wait: no use of a stage is scheduled above it)
-template <int I, int R>
-__device__ __forceinline__ void rs_touch_all(bf16x8 (&wq)[R]) {
-    if constexpr (I < R) {
-        asm volatile("" : "+v"(wq[I]));
-        rs_touch_all<I + 1, R>(wq);
-    }
-}
-
-template <int I, int N, class F>
-__device__ __forceinline__ void rs_static_for_impl(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        rs_static_for_impl<I + 1, N>(f);
-    }
-}
-template <int N, class F>
-__device__ __forceinline__ void rs_static_for(F&& f) { rs_static_for_impl<0, N>(f); }
 
 // Packed row (packing.py gate order: row cg*64 + kind*32 + c of channel cg*32 + c) of accumulator row rho of channel
 // group grp (16 channels): a lane's registers 8 pp + j (filter) and 8 pp + 4 + j (gate) belong to the same channel
@@ -173,50 +126,44 @@ struct RsCount {
     // target: tk 0 = weights W(ta, tb) / 1 = last piece of global item ta; query: qk 0 = the wait in front of k-step (qa, qb) /
     // 1 = the arrival at global barrier qa
     static constexpr int walk(int tk, int ta, int tb, int qk, int qa, int qb) {
-        int count = -1, result = -1;
-        bool done = false;
-#define RS_W(tile, k) do { if (count >= 0) ++count; if (tk == 0 && ta == (tile) && tb == (k)) count = 0; } while (0)
-#define RS_P(J) do { for (int j_ = 0; j_ < PP; ++j_) { if (count >= 0) ++count; if (tk == 1 && ta == (J) && j_ == PP - 1) count = 0; } } while (0)
-#define RS_P1(J, j_) do { if (count >= 0) ++count; if (tk == 1 && ta == (J) && (j_) == PP - 1) count = 0; } while (0)
-#define RS_QB(b) do { if (!done && qk == 1 && qa == (b)) { result = count; done = true; } } while (0)
-#define RS_QK(tile, g) do { if (!done && qk == 0 && qa == (tile) && qb == (g)) { result = count; done = true; } } while (0)
-        RS_P(0);
+        VmWalk w;
+        auto load = [&](int tile, int k) { w.op(tk == 0 && ta == tile && tb == k); };
+        auto piece = [&](int J, int j) { w.op(tk == 1 && ta == J && j == PP - 1); };
+        auto pieces = [&](int J) { for (int j = 0; j < PP; ++j) piece(J, j); };
+        auto ring = [&] { for (int k = 0; k < R - 1; ++k) load(0, k); };
+        auto at_barrier = [&](int b) { w.query(qk == 1 && qa == b); };
+        pieces(0);
         if (!LAG) {
-            for (int k = 0; k < R - 1; ++k) RS_W(0, k);
-            RS_QB(0);
+            ring();
+            at_barrier(0);
         } else {
-            RS_QB(0);
-            RS_P(1);
-            RS_P(2);
-            for (int k = 0; k < R - 1; ++k) RS_W(0, k);
+            at_barrier(0);
+            pieces(1);
+            pieces(2);
+            ring();
         }
         for (int tile = 0; tile < 3; ++tile) {
             for (int i = 0; i < NI; ++i) {
                 const int J = tile * NI + i;
-                if (LAG) RS_QB(J + 1);
-                else if (i > 0) RS_QB(J);
+                if (LAG) at_barrier(J + 1);
+                else if (i > 0) at_barrier(J);
                 for (int l = 0; l < P::item_ks(i); ++l) {
                     const int g = P::item_first(i) + l;
-                    RS_QK(tile, g);
+                    w.query(qk == 0 && qa == tile && qb == g);
                     for (int slot = 0; slot < MT; ++slot) {
-                        if (!LAG && tile == 0 && g == 0 && slot < PP) RS_P1(1, slot);
-                        if (l == 0 && slot < PP && (PERSIST || i + AHEAD < NI)) RS_P1(J + AHEAD, slot);
+                        if (!LAG && tile == 0 && g == 0 && slot < PP) piece(1, slot);
+                        if (l == 0 && slot < PP && (PERSIST || i + AHEAD < NI)) piece(J + AHEAD, slot);
                         if (slot == 1) {
-                            if (g + R - 1 < NK) RS_W(tile, g + R - 1);
-                            else if (PERSIST && (g - 1) % R <= R - 2) RS_W(tile + 1, (g - 1) % R);
+                            if (g + R - 1 < NK) load(tile, g + R - 1);
+                            else if (PERSIST && (g - 1) % R <= R - 2) load(tile + 1, (g - 1) % R);
                         }
                     }
                 }
             }
-            if (PERSIST && (NK - 1) % R <= R - 2) RS_W(tile + 1, (NK - 1) % R);
-            if (!LAG) RS_QB((tile + 1) * NI);
+            if (PERSIST && (NK - 1) % R <= R - 2) load(tile + 1, (NK - 1) % R);
+            if (!LAG) at_barrier((tile + 1) * NI);
         }
-#undef RS_W
-#undef RS_P
-#undef RS_P1
-#undef RS_QB
-#undef RS_QK
-        return result;
+        return w.result;
     }
     // tile: 0 = the workgroup's first tile, 1 = any later one
     static constexpr int wait_kstep(int tile, int g) { return walk(0, tile, g, 0, tile, g); }
@@ -276,10 +223,7 @@ __device__ __forceinline__ void gate_rs_wave(const GateRsArgs& p, unsigned char*
     };
 
     // ---- weight stream of this wave (the same for every tile): k-step g -> ring stage g % R
-    const unsigned long long wbase = (unsigned long long)(uintptr_t)p.Wg + (unsigned long long)grp * NK * 1024;
-    const u32x4 wsrd = {(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)wbase),
-                        (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(wbase >> 32)) & 0xffffu,      // stride 0
-                        (uint32_t)(NK * 1024), 0x00020000u};
+    const u32x4 wsrd = rs_srd(p.Wg, (uint32_t)(NK * 1024), (unsigned long long)grp * NK * 1024);
     const uint32_t wl = (uint32_t)lane * 16u;
     bf16x8 wq[R];
     auto issue_w = [&](auto G) {                      // 4 KiB windows: the window in the scalar offset, the rest an immediate
@@ -403,11 +347,8 @@ __device__ __forceinline__ void gate_rs_wave(const GateRsArgs& p, unsigned char*
 #if defined(FWN_RS_SAFE) && (FWN_RS_SAFE & 1)        // developer build: drain in front of every k-step
                 rs_wwait<0>(wq[g % R]);
 #else
-                // ONE statement whatever the tile: under `if (first) wait<n0> else wait<n1>` hipcc merges the two arms' "+v"
-                // operand in a new register and fills it with a v_mov IN FRONT of the s_waitcnt of one arm - a copy of a ring
-                // stage whose load is still in flight (found in the ISA by tools/check_async_loads.py; it was the persistent
-                // form's race: stale weights in the k-steps whose counts differ between the first and the later tiles,
-                // whenever the load had not landed by then).  The smaller count is safe for both (it waits for more).
+                // ONE statement whatever the tile, with the smaller count (no branch around a wait that names ring registers:
+                // reg_stream.h, rs_wwait - the persistent form's race)
                 rs_wwait<(n0 < n1 ? n0 : n1)>(wq[g % R]);
 #endif
             }
@@ -505,7 +446,7 @@ __device__ __forceinline__ void gate_rs_wave(const GateRsArgs& p, unsigned char*
     // registers) and its out-of-range pieces must have landed before the registers / the LDS are anyone else's
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
-    rs_touch_all<0, R>(wq);           // every ring stage named behind the wait (any R)
+    rs_touch_all(wq);         // every ring stage named behind the wait (any R)
 }
 
 // NKC: conditioning k-steps of 16 (cin / 16 rounded up); MT: 32-row time tiles per wave; R: ring stages of weight fragments

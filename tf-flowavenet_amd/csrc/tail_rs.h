@@ -24,7 +24,7 @@
 // LDS: region A = o ring, then the Wz image; region B = S, then U; 8 KB of per-flow constants; MT = 4: 140 KB (one workgroup
 // per CU), MT = 2: 74 KB (two), MT = 1: 57 KB.
 #pragma once
-#include "gate_rs.h"
+#include "reg_stream.h"     // the shared primitives (rs_srd, rs_dma16, rs_wload, rs_dload, the counted waits, VmWalk) and their rules
 #include "tail_chain.h"
 
 #ifndef FWN_TRS_SAFE
@@ -64,39 +64,32 @@ struct TrsCount {
     // target: tk 0 = W(ta) / 1 = the last own piece of item ta; query: qk 0 = the wait in front of k-step qa / 1 = the wait in
     // front of item barrier qa
     static constexpr int walk(int tk, int ta, int qk, int qa) {
-        int count = -1, result = -1;
-        bool done = false;
-#define T_OP() do { if (count >= 0) ++count; } while (0)
-#define T_W(k) do { T_OP(); if (tk == 0 && ta == (k)) count = 0; } while (0)
-#define T_P1(i, j) do { T_OP(); if (tk == 1 && ta == (i) && (j) == PP - 1) count = 0; } while (0)
-#define T_QK(g) do { if (!done && qk == 0 && qa == (g)) { result = count; done = true; } } while (0)
-#define T_QB(i) do { if (!done && qk == 1 && qa == (i)) { result = count; done = true; } } while (0)
-        T_OP();
+        VmWalk w;
+        auto load = [&](int k) { w.op(tk == 0 && ta == k); };
+        auto piece = [&](int i, int j) { w.op(tk == 1 && ta == i && j == PP - 1); };
+        auto kstep = [&](int g, bool pieces) {          // under k-step g: one operation at most behind each MFMA slot
+            for (int slot = 0; slot < MT; ++slot) {
+                if (pieces && slot < PP && (g >> 2) + LA < NI) piece((g >> 2) + LA, slot);
+                if (slot == WSLOT && g + R - 1 < NKW) load(g + R - 1);
+            }
+        };
+        w.op();
         for (int k = 0; k < R - 1; ++k) {
             if (k % 2 == 0 && k / 2 < LA)
-                for (int j = 0; j < PP; ++j) T_P1(k / 2, j);
-            T_W(k);
+                for (int j = 0; j < PP; ++j) piece(k / 2, j);
+            load(k);
         }
         for (int g = 0; g < 32; ++g) {
-            T_QK(g);
-            if ((g & 3) == 0) T_QB(g >> 2);
-            for (int slot = 0; slot < MT; ++slot) {
-                if ((g & 3) == 0 && slot < PP && (g >> 2) + LA < NI) T_P1((g >> 2) + LA, slot);
-                if (slot == WSLOT && g + R - 1 < NKW) T_W(g + R - 1);
-            }
+            w.query(qk == 0 && qa == g);
+            if ((g & 3) == 0) w.query(qk == 1 && qa == (g >> 2));
+            kstep(g, (g & 3) == 0);
         }
-        for (int s = 0; s < NSV + NZ + NX; ++s) T_OP();
+        for (int s = 0; s < NSV + NZ + NX; ++s) w.op();
         for (int g = 32; g < 48; ++g) {
-            T_QK(g);
-            for (int slot = 0; slot < MT; ++slot)
-                if (slot == WSLOT && g + R - 1 < NKW) T_W(g + R - 1);
+            w.query(qk == 0 && qa == g);
+            kstep(g, false);
         }
-#undef T_OP
-#undef T_W
-#undef T_P1
-#undef T_QK
-#undef T_QB
-        return result;
+        return w.result;
     }
     static constexpr int wait_kstep(int g) { return walk(0, g, 0, g); }
     static constexpr int wait_barrier(int i) { return walk(1, i, 1, i); }
@@ -128,37 +121,8 @@ __device__ __forceinline__ void trs_store_row32(const uint2 (&pk)[4], srd_t dst,
     }
 }
 
-// LDS-DMA piece (64 lanes x 16 bytes -> LDS at the wave-uniform byte address lds_addr + lane * 16) issued from inline asm.
-// Through the builtin (buf_load16_lds) hipcc knows that LDS writes are in flight and puts an s_waitcnt vmcnt(0) in front of the
-// next ds_read / ds_write it emits (it cannot tell that the access is to another slot): in this kernel that drained the whole
-// prologue - two more o slices and R - 1 weight fragments - in front of the first k-step, and the Wz image in front of phase
-// 2 (stamps: 3.6 k cycles at barrier 0).  Issued from asm the pieces are invisible to that pass; every wait for them is one of
-// TrsCount's.  M0 (the LDS address) is compiler-reserved: saved and restored inside the statement (guide section 5.7).
-__device__ __forceinline__ void trs_dma16(u32x4 srd, uint32_t voff, uint32_t lds_addr) {
-    uint32_t keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 4\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(srd), "s"(lds_addr) : "memory");
-}
-// raw buffer descriptor (stride 0, range check on the byte offset) in SGPRs an asm statement can name
-__device__ __forceinline__ u32x4 trs_srd(const void* p, uint32_t bytes) {
-    const unsigned long long b = (unsigned long long)(uintptr_t)p;
-    return u32x4{(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)b), (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(b >> 32)) & 0xffffu,
-                 (uint32_t)__builtin_amdgcn_readfirstlane((int)bytes), 0x00020000u};
-}
-
-// one dword per lane, hidden from hipcc's wait bookkeeping like rs_wload (the caller counts vmcnt)
-__device__ __forceinline__ void trs_xload(float& dst, u32x4 srd, uint32_t voff) {
-    asm volatile("s_nop 4\n\tbuffer_load_dword %0, %1, %2, 0 offen" : "=v"(dst) : "v"(voff), "s"(srd) : "memory");
-}
-
-// every ring stage made opaque at this point (behind a wait: no consumer of a stage is scheduled above it)
-template <int I, int R>
-__device__ __forceinline__ void trs_touch(bf16x8 (&wq)[R]) {
-    if constexpr (I < R) {
-        asm volatile("" : "+v"(wq[I]));
-        trs_touch<I + 1, R>(wq);
-    }
-}
+// (every LDS-DMA piece, weight load and plane load below is issued from inline asm - rs_dma16, rs_wload, rs_dload of
+// reg_stream.h, where the reasons are - and waited for with one of TrsCount's counts)
 
 // MT: 32-row time tiles per workgroup (tile = 32 MT rows); FRONT: the chained front conv (Ch <= 8); SAVE: keep S, U, Z for
 // the training backward; R: ring stages of weight fragments per wave.  L = 2 layers, one ZeroConv pair tile (Ch <= 32).
@@ -200,12 +164,12 @@ __global__ __launch_bounds__(512, (MT <= 2 ? 4 : 2)) void tail_rs_kernel(TailArg
         else if (wave == 4) { src = a.an; bytes = (uint32_t)Ch * 32u; }
         else if (wave == 5 && front) { src = a.bfn; bytes = 1024u; }
         else if (wave == 6 && front && a.an_next) { src = a.an_next; bytes = (uint32_t)Ch * 32u; }
-        trs_dma16(trs_srd(src, bytes), (uint32_t)lane * 16u, lds0 + (uint32_t)(A_BYTES + B_BYTES + 1024 * wave));
+        rs_dma16(rs_srd(src, bytes), (uint32_t)lane * 16u, lds0 + (uint32_t)(A_BYTES + B_BYTES + 1024 * wave));
     }
 
     // ---- o slices: item i = (layer i / 4, columns 64 (i % 4) ..), image [rows][64] in slot i % 4; piece j of this wave =
     // image rows 8 (wave + 8 j) .. + 7 (rows past the tile or the matrix: out of range = zeros)
-    const u32x4 srd_o = trs_srd(a.o, (uint32_t)(((size_t)(a.L - 1) * a.o_stride + (size_t)M * FWN_HID) * 2));
+    const u32x4 srd_o = rs_srd(a.o, (uint32_t)(((size_t)(a.L - 1) * a.o_stride + (size_t)M * FWN_HID) * 2));
     auto issue_piece = [&](int item, int j) {
         const int pi = wave + 8 * j;
         const int jrow = 8 * pi + (lane >> 3);
@@ -213,17 +177,12 @@ __global__ __launch_bounds__(512, (MT <= 2 ? 4 : 2)) void tail_rs_kernel(TailArg
         const int gr = g0 + jrow;
         const bool ok = (jrow < BM) & ((unsigned)gr < (unsigned)M);
         const uint32_t off = (uint32_t)((item >> 2) * a.o_stride + (long)gr * FWN_HID + (item & 3) * 64 + c * 8) * 2u;
-        trs_dma16(srd_o, ok ? off : FWN_OOB, lds0 + (uint32_t)((item & 3) * SLOT + (wave + 8 * j) * 1024));
+        rs_dma16(srd_o, ok ? off : FWN_OOB, lds0 + (uint32_t)((item & 3) * SLOT + (wave + 8 * j) * 1024));
     };
 
     // ---- this wave's weight stream: k-step g -> ring stage g % R; g >= 48: the next flow's front weights [256][kfn]
-    const unsigned long long wbase = (unsigned long long)(uintptr_t)Wts + (unsigned long long)wave * (48 * 1024);
-    const u32x4 wsrd = {(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)wbase),
-                        (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(wbase >> 32)) & 0xffffu, (uint32_t)(48 * 1024), 0x00020000u};
-    const unsigned long long nbase = (unsigned long long)(uintptr_t)(front ? (const void*)a.Wfn : (const void*)Wts);
-    const u32x4 nsrd = {(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)nbase),
-                        (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(nbase >> 32)) & 0xffffu,
-                        front ? (uint32_t)(256 * a.kfn * 2) : 0u, 0x00020000u};
+    const u32x4 wsrd = rs_srd(Wts, (uint32_t)(48 * 1024), (unsigned long long)wave * (48 * 1024));
+    const u32x4 nsrd = rs_srd(front ? (const void*)a.Wfn : (const void*)Wts, front ? (uint32_t)(256 * a.kfn * 2) : 0u);
     const uint32_t wl = (uint32_t)lane * 16u;
     bf16x8 wq[R];
     auto issue_w = [&](auto G) {
@@ -331,12 +290,12 @@ __global__ __launch_bounds__(512, (MT <= 2 ? 4 : 2)) void tail_rs_kernel(TailArg
     TRS_STAMP(4);
     // ---- the ZeroConv weights [64][256] as 4 sub-tiles [64][64] of 8 KB into region A (tail_chain.h's image): 4 pieces per wave
     {
-        const u32x4 srd_z = trs_srd(a.Wz, 64u * 256u * 2u);
+        const u32x4 srd_z = rs_srd(a.Wz, 64u * 256u * 2u);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int pi = wave + 8 * j, q = pi >> 3;
             const int r = (pi & 7) * 8 + (lane >> 3);
-            trs_dma16(srd_z, (uint32_t)(r * FWN_HID + q * 64 + ((lane & 7) ^ ((r >> 1) & 7)) * 8) * 2u, lds0 + (uint32_t)(pi * 1024));
+            rs_dma16(srd_z, (uint32_t)(r * FWN_HID + q * 64 + ((lane & 7) ^ ((r >> 1) & 7)) * 8) * 2u, lds0 + (uint32_t)(pi * 1024));
         }
     }
     // ---- the coupling's in_b values of the tile waves' rows (accumulator registers 0 - 3: channels 4 lh .. + 3, all there are for
@@ -344,6 +303,8 @@ __global__ __launch_bounds__(512, (MT <= 2 ? 4 : 2)) void tail_rs_kernel(TailArg
     // at the end of every workgroup.  Every wave issues the four loads (the others out of range): one wait schedule.
     float xpre[4];
     {
+        // (rs_srd's descriptor written out, the byte count without its readfirstlane: with it hipcc places one scalar
+        // instruction of every instantiation elsewhere - the same code otherwise, but not the code that was measured)
         const unsigned long long xbase = (unsigned long long)(uintptr_t)a.xb;
         const u32x4 xsrd = {(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)xbase),
                             (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(xbase >> 32)) & 0xffffu,
@@ -353,7 +314,7 @@ __global__ __launch_bounds__(512, (MT <= 2 ? 4 : 2)) void tail_rs_kernel(TailArg
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int tau = r + 4 * lh;
-            trs_xload(xpre[r], xsrd, (rv && tau < Ch) ? (uint32_t)(row * Ch + tau) * 4u : FWN_OOB);
+            rs_dload(xpre[r], xsrd, (rv && tau < Ch) ? (uint32_t)(row * Ch + tau) * 4u : FWN_OOB);
         }
     }
 
@@ -381,7 +342,7 @@ __global__ __launch_bounds__(512, (MT <= 2 ? 4 : 2)) void tail_rs_kernel(TailArg
     // everything this wave has requested has landed: the Wz pieces, the front weights (they stay in their ring stages)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
-    trs_touch<0, R>(wq);
+    rs_touch_all(wq);
     asm volatile("" : "+v"(xpre[0]), "+v"(xpre[1]), "+v"(xpre[2]), "+v"(xpre[3]));
     TRS_STAMP(6);
     FWN_RING_BARRIER();              // every wave has read its last S fragments

@@ -54,7 +54,8 @@ int main(int argc, char** argv) {
         Ws[f] = dalloc_bf16(256ull * 512, 0.05f); Wf[f] = dalloc_bf16(256ull * 256, 0.06f); Wz[f] = dalloc_bf16(64ull * 256, 0.02f);
         Wfn[f] = dalloc_bf16(256ull * kfn, 0.3f);
         CK(hipMalloc(&Wts[f], 8ull * 48 * 1024));
-        hipLaunchKernelGGL(tail_stream_pack_kernel, dim3(96), dim3(256), 0, 0, (const bf16*)Ws[f], (const bf16*)Wf[f], (bf16*)Wts[f]);
+        hipLaunchKernelGGL(tail_stream_pack_kernel, dim3(96), dim3(256), 0, 0, (const bf16*)Ws[f], (const bf16*)Wf[f], (bf16*)Wts[f],
+                           (const TailStreamJob*)nullptr);
     }
     float* bs = dalloc_f32(256, 0.1f); float* bfin = dalloc_f32(256, 0.1f); float* bz = dalloc_f32(64, 0.01f); float* ez = dalloc_f32(64, 0.0f, 1.0f);
     float* an = dalloc_f32(8 * Ch, 0.1f, 1.0f); float* bfn = dalloc_f32(256, 0.1f); float* ann = dalloc_f32(8 * Ch, 0.1f, 1.0f);

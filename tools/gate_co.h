@@ -50,28 +50,24 @@ struct CoCount {
     using P = CoPlan<NKC>;
     static constexpr int PP = 5, NI = P::NI, NK = P::NK, AHEAD = 3, WSLOT = 6;
     static constexpr int walk(int tk, int ta, int qk, int qa) {     // target: 0 = W(ta) / 1 = last piece of item ta; query: 0 = wait of k-step qa / 1 = barrier qa
-        int count = -1, result = -1;
-        bool done = false;
-#define CO_W(k) do { if (count >= 0) ++count; if (tk == 0 && ta == (k)) count = 0; } while (0)
-#define CO_P(J) do { for (int j_ = 0; j_ < PP; ++j_) { if (count >= 0) ++count; if (tk == 1 && ta == (J) && j_ == PP - 1) count = 0; } } while (0)
-#define CO_P1(J, j_) do { if (count >= 0) ++count; if (tk == 1 && ta == (J) && (j_) == PP - 1) count = 0; } while (0)
-        for (int i = 0; i < AHEAD && i < NI; ++i) CO_P(i);
-        for (int k = 0; k < R - 1; ++k) CO_W(k);
+        VmWalk w;
+        auto load = [&](int k) { w.op(tk == 0 && ta == k); };
+        auto piece = [&](int J, int j) { w.op(tk == 1 && ta == J && j == PP - 1); };
+        for (int i = 0; i < AHEAD && i < NI; ++i)
+            for (int j = 0; j < PP; ++j) piece(i, j);
+        for (int k = 0; k < R - 1; ++k) load(k);
         for (int i = 0; i < NI; ++i) {
-            if (!done && qk == 1 && qa == i) { result = count; done = true; }
+            w.query(qk == 1 && qa == i);
             for (int l = 0; l < P::item_ks(i); ++l) {
                 const int g = P::item_first(i) + l;
-                if (!done && qk == 0 && qa == g) { result = count; done = true; }
+                w.query(qk == 0 && qa == g);
                 for (int slot = 0; slot < 8; ++slot) {
-                    if (l == 0 && slot < PP && i + AHEAD < NI) CO_P1(i + AHEAD, slot);
-                    if (slot == WSLOT && g + R - 1 < NK) CO_W(g + R - 1);
+                    if (l == 0 && slot < PP && i + AHEAD < NI) piece(i + AHEAD, slot);
+                    if (slot == WSLOT && g + R - 1 < NK) load(g + R - 1);
                 }
             }
         }
-#undef CO_W
-#undef CO_P
-#undef CO_P1
-        return result;
+        return w.result;
     }
     static constexpr int wait_kstep(int g) { return walk(0, g, 0, g); }
     static constexpr int wait_barrier(int i) { return walk(1, i, 1, i); }
@@ -136,10 +132,7 @@ __global__ __launch_bounds__(256, 2) void gate_co_kernel(GateRsArgs p) {
     };
 
     // ---- weight stream of this wave: k-step g (this plan's order) -> ring stage g % R, read at its RsPlan position
-    const unsigned long long wbase = (unsigned long long)(uintptr_t)p.Wg + (unsigned long long)grp * NK * 1024;
-    const u32x4 wsrd = {(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)wbase),
-                        (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(wbase >> 32)) & 0xffffu,      // stride 0
-                        (uint32_t)(NK * 1024), 0x00020000u};
+    const u32x4 wsrd = rs_srd(p.Wg, (uint32_t)(NK * 1024), (unsigned long long)grp * NK * 1024);
     const uint32_t wl = (uint32_t)lane * 16u;
     bf16x8 wq[R];
     auto issue_w = [&](auto G) {
