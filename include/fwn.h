@@ -871,6 +871,41 @@ int fwn_corpus_draw(const float* audio, const float* mel, const int64_t* frame_o
                     int unit_frames, int64_t B, int64_t F, uint64_t seed, uint32_t stream_id, uint64_t* counter_dev, float* x,
                     float* c, int32_t* len, int32_t* picks, void* stream);
 
+/* ---- sample-rate conversion (additive; FWN_VERSION unchanged): one band-limited rational resampler, so that wavs of any rate go
+ * in (preprocessing.load_wav) and any rate comes out (synthesize --out_rate).  DESIGN.md "Sample-rate conversion" has the
+ * definition; tests/resample_ref.py restates it in fp64.
+ *
+ * For in_rate -> out_rate: up = out_rate / gcd, down = in_rate / gcd, q = max(up, down), Hh = zeros * q.  A clip of N samples
+ * has n_out(N) = ceil(N up / down) outputs
+ *     y[m] = sum_n x[n] h[m down - n up],  |m down - n up| <= Hh,  x = 0 outside [0, N)
+ *     h[j] = (up rolloff / q) sinc(rolloff j / q) I0(beta sqrt(1 - (j / Hh)^2)) / I0(beta),  sinc(t) = sin(pi t) / (pi t)
+ * evaluated from the phase table T [up][K], K = 2 Hh div up + 1, T[r][k] = h[r + k up - Hh] (0 past the support): with n0 =
+ * (m down + Hh) div up and r = (m down + Hh) mod up, y[m] = sum_k x[n0 - k] T[r][k].
+ *
+ * fwn_resample_taps: K, or FWN_ERR_ARG.  fwn_resample_design: T into table_host [up][K] - HOST memory, host code, no device
+ * call: fp64 throughout (I0 by its power series), each entry rounded to fp32 once.  Both refuse (FWN_ERR_ARG, with a message) up
+ * or down outside 1..2^20, gcd(up, down) != 1 and zeros outside 1..64; the design also rolloff outside (0, 1], beta < 0 (or
+ * above 100, or NaN) and a null table.
+ *
+ * fwn_resample: one launch for B clips.  x: row b at x + b * x_stride elements, float32 (x_pcm16 = 0) or int16 PCM read as
+ * v / 32768, exact (x_pcm16 = 1); element j of a row is CLIP sample in_start + j, j < n_in - the provided span.  Clip b has
+ * N_b = len_dev[b] samples (DEVICE int64 [B], read on the device and clamped to [0, len_host]) or len_host when len_dev is
+ * NULL.  y: row b at y + b * y_stride floats; y[b][i] = output m0 + i for i < n_out, and exact +0 where m0 + i >= n_out(N_b).
+ * Nothing else is written.  No sample at or past N_b, and none outside the provided span, is loaded (a NaN there is harmless).
+ * An output's bits depend only on the clip's samples in its support, on N_b and on m: not on B, the row, in_start, m0 or the
+ * workgroup tile - each output is four fmaf chains over k mod 4 in ascending k, added (a0 + a1) + (a2 + a3) - so a clip cut
+ * into chunks, or batched with others, gets the bits it gets alone.  All arithmetic on m down and N up is 64-bit: N up to
+ * 2^40.  Refusals (FWN_ERR_ARG, before any launch): those of fwn_resample_taps; a null or misaligned x, y, table_dev (or
+ * misaligned len_dev); x_pcm16 not 0 / 1; B outside 1..65535; negative in_start, n_in, m0 or len_host, n_out < 1; a stride
+ * shorter than its row; a ratio whose tile of 256 outputs reads more than 16384 input samples (64 KiB of LDS); and any
+ * requested output m < n_out(len_host) whose support within [0, len_host) is not inside [in_start, in_start + n_in).
+ * Speed: tools/bench_resample.py. */
+int fwn_resample_taps(int up, int down, int zeros);
+int fwn_resample_design(int up, int down, int zeros, double beta, double rolloff, float* table_host);
+int fwn_resample(const void* x, int x_pcm16, int64_t B, int64_t x_stride, int64_t in_start, int64_t n_in, const int64_t* len_dev,
+                 int64_t len_host, const float* table_dev, int up, int down, int zeros, float* y, int64_t y_stride, int64_t m0,
+                 int64_t n_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -268,6 +268,9 @@ SIGNATURES = {
     "fwn_forward_windows_workspace_bytes": (C.c_size_t, [C.POINTER(ModelDesc), i64, i64]),
     "fwn_model_forward_windows": (C.c_int, [C.POINTER(ModelDesc), i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]),
     "fwn_corpus_draw": (C.c_int, [vp, vp, vp, i64, C.c_int, C.c_int, C.c_int, i64, i64, C.c_uint64, C.c_uint32, vp, vp, vp, vp, vp, vp]),
+    "fwn_resample_taps": (C.c_int, [C.c_int, C.c_int, C.c_int]),
+    "fwn_resample_design": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, vp]),
+    "fwn_resample": (C.c_int, [vp, C.c_int, i64, i64, i64, i64, vp, i64, vp, C.c_int, C.c_int, C.c_int, vp, i64, i64, i64, vp]),
 }
 
 _lib = None

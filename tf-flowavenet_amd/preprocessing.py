@@ -7,10 +7,16 @@ multiple of ``hop_size``), ``mels/dataset-mel-%05d.npy`` (float32 ``[N, num_mels
 The spectrogram (``librosa.feature.melspectrogram`` in the reference, ``:58-64``) runs in
 ``libfwn.so`` (``fwn_mel_spectrogram``); there is no CPU fallback.
 
-Differences (deliberate): wavs are read with the stdlib ``wave`` module (16-bit PCM at
-``hparams.sample_rate``; librosa's resampling loader is not a dependency), the TFRecord writer
-(``tfrecord.py``) is out of scope, and clips are processed on one device stream instead of a
-process pool.
+Differences (deliberate): wavs are read with the stdlib ``wave`` module (``load_wav``: 8, 16, 24 and
+32-bit PCM of any rate and channel count) and a wav whose rate is not ``hparams.sample_rate`` is
+resampled on the device (``resample.Resampler`` - where the reference's ``librosa.load(...,
+sr=hparams.sample_rate)`` resamples, ``:50``; librosa is not a dependency and its filter is not
+reproduced: the definition is DESIGN.md "Sample-rate conversion"), so corpora of any rate and of
+mixed rates go in; a corpus already at ``hparams.sample_rate`` gives the files it always gave.
+``read_wav`` is the strict reader (16-bit at the model's rate, an error otherwise).  Non-PCM wav
+encodings and compressed formats, and peak normalisation / padding on the device, are out of scope;
+the TFRecord writer (``tfrecord.py``) is too, and clips are processed on one device stream instead
+of a process pool.
 """
 from __future__ import annotations
 
@@ -114,10 +120,53 @@ def read_wav(path, sample_rate):
     return pcm
 
 
+def _pcm_to_float(raw, width, path="wav"):
+    """The bytes of little-endian PCM frames -> float32 in [-1, 1): 8-bit is unsigned ((v - 128) / 128), 16, 24 and 32-bit are
+    signed (v / 2^(bits - 1)).  8, 16 and 24-bit values are exact in float32; 32-bit ones are divided in float64 and rounded once
+    (the largest few then round to 1.0)."""
+    if width == 1:
+        return (np.frombuffer(raw, dtype=np.uint8).astype(np.float32) - 128.0) / 128.0
+    if width == 2:
+        return np.frombuffer(raw, dtype="<i2").astype(np.float32) / 32768.0
+    if width == 3:
+        b = np.frombuffer(raw, dtype=np.uint8).reshape(-1, 3).astype(np.int32)
+        v = b[:, 0] | (b[:, 1] << 8) | (b[:, 2] << 16)
+        return (v - ((v & 0x800000) << 1)).astype(np.float32) / 8388608.0
+    if width == 4:
+        return (np.frombuffer(raw, dtype="<i4").astype(np.float64) / 2147483648.0).astype(np.float32)
+    raise ValueError("%s: %d-byte samples are not supported (8, 16, 24 and 32-bit PCM are)" % (path, width))
+
+
+def load_wav(path, sample_rate, resamplers=None):
+    """PCM wav of any rate -> float32 mono at ``sample_rate`` (the reference's ``librosa.load(path, sr=sample_rate)``).
+
+    8, 16, 24 and 32-bit PCM through the stdlib ``wave`` module; the channel mean as ``read_wav`` takes it; a file whose rate
+    differs is resampled on the device (``resample.Resampler``).  ``resamplers``: a dict the caller keeps, source rate ->
+    ``Resampler``, so that a corpus designs and uploads one table per source rate.  A 16-bit file at ``sample_rate`` gives
+    ``read_wav``'s array bit for bit, with no device call."""
+    with wave.open(path, "rb") as w:
+        rate, channels = w.getframerate(), w.getnchannels()
+        pcm = _pcm_to_float(w.readframes(w.getnframes()), w.getsampwidth(), path)
+    if channels > 1:
+        pcm = pcm.reshape(-1, channels).mean(axis=1)
+    if rate == int(sample_rate):
+        return pcm
+    from .resample import Resampler
+    if resamplers is None:
+        resamplers = {}
+    if rate not in resamplers:
+        resamplers[rate] = Resampler(rate, sample_rate)
+    if len(pcm) == 0:
+        return pcm
+    import torch
+    return resamplers[rate](torch.from_numpy(np.ascontiguousarray(pcm))).cpu().numpy()
+
+
 def build_from_path(in_dir, out_dir, hparams, num_workers=1):
     """``in_dir/<book>/metadata.csv`` + ``wavs/<id>.wav`` (single speaker, preprocessing.py:30-45)."""
     del num_workers     # one device stream does the work of the reference's process pool
     mel_fn = MelSpectrogram(hparams)
+    resamplers = {}                                  # one Resampler (one phase table on the device) per source rate
     books = sorted(os.path.join(in_dir, f) for f in os.listdir(in_dir) if os.path.isdir(os.path.join(in_dir, f)))
     metadata, index = [], 1
     for book in books:
@@ -126,7 +175,7 @@ def build_from_path(in_dir, out_dir, hparams, num_workers=1):
         for line in lines:
             parts = line.strip().split("|")
             text = parts[2] if len(parts) > 2 else ""
-            wav = read_wav(os.path.join(book, "wavs", "%s.wav" % parts[0]), hparams.sample_rate)
+            wav = load_wav(os.path.join(book, "wavs", "%s.wav" % parts[0]), hparams.sample_rate, resamplers)
             audio, mel = _process_utterance(wav, hparams, mel_fn)
             audio_filename = "dataset-audio-%05d.npy" % index
             mel_filename = "dataset-mel-%05d.npy" % index

@@ -15,7 +15,10 @@ audio does not depend on the batch it lands in.  ``--device_rng`` (opt-in) keeps
 a stream of this package's own - with or without ``--ragged``, only the mel goes up and only 16-bit PCM comes down.
 ``--window SAMPLES`` (opt-in) synthesizes every clip longer than that window by window (``windowing.plan_windows``: each window
 with the network's receptive field of real context on both sides, so the seams are exact) - no clip is too long for one call
-any more - and writes its wav core by core; the other clips take the paths above.
+any more - and writes its wav core by core; the other clips take the paths above.  ``--out_rate HZ`` (opt-in) resamples the
+float audio on the device before it is written (``resample.Resampler``: a clip's true samples, ``frames * hop`` of them, not its
+padding -> ``ceil(frames * hop * HZ / sample_rate)`` samples, ``write_wav``'s arithmetic, ``HZ`` in the header) on the default
+path, with ``--ragged`` and with ``--window``; with ``--device_rng`` - which holds 16-bit PCM, not float audio - it is an error.
 """
 from __future__ import annotations
 
@@ -120,9 +123,39 @@ def write_wav_pcm(path, pcm, sample_rate):
         w.writeframes(np.ascontiguousarray(pcm, dtype="<i2").tobytes())
 
 
+class _Output:
+    """Where the float paths write their wavs.  Without ``--out_rate``: ``write_wav`` of the clip's true samples at
+    ``hparams.sample_rate``, as ever.  With it: the true samples (``lengths``; not a clip's padding) are resampled on the
+    device (``resample.Resampler``), ``n_out(length)`` samples per clip come down, and ``write_wav`` writes them with ``HZ`` in
+    the header."""
+
+    def __init__(self, args, hparams):
+        self.dir, self.rate, self.resampler = args.output_dir, int(hparams.sample_rate), None
+        out_rate = getattr(args, "out_rate", None)
+        if out_rate is not None:
+            if int(out_rate) < 1:
+                raise ValueError("--out_rate must be a positive rate in Hz, got %r" % (out_rate,))
+            from .resample import Resampler
+            self.rate, self.resampler = int(out_rate), Resampler(hparams.sample_rate, out_rate)
+
+    def path(self, name):
+        return os.path.join(self.dir, name[:-4] + ".wav")
+
+    def write(self, names, wav, lengths):
+        """``wav``: device float32 [B, T]; clip b is ``names[b]`` with ``lengths[b]`` true samples."""
+        if self.resampler is not None:
+            wav = self.resampler(wav, lengths=lengths)
+            lengths = [self.resampler.out_length(n) for n in lengths]
+        wav = wav.cpu().numpy()
+        for n, w, length in zip(names, wav, lengths):
+            write_wav(self.path(n), w[:length], self.rate)
+
+
 def synthesize(args, hparams, model=None):
     import torch
     from .model import FloWaveNet
+    if getattr(args, "out_rate", None) is not None and getattr(args, "device_rng", False):
+        raise ValueError("--out_rate applies to the float paths: it cannot be combined with --device_rng")
     if model is None:
         model = FloWaveNet(hparams).load_params(load_checkpoint(args.saved_dir))
     os.makedirs(args.output_dir, exist_ok=True)
@@ -140,6 +173,7 @@ def synthesize(args, hparams, model=None):
         if n not in done:
             by_len.setdefault(mels[n].shape[0], []).append(n)
     gen = torch.Generator(device="cpu").manual_seed(int(args.seed))
+    out = _Output(args, hparams)
     hop = hparams.hop_size
     align = max(1, (1 << hparams.n_block) // np.gcd(1 << hparams.n_block, hop))
     for frames, group in sorted(by_len.items()):
@@ -153,9 +187,8 @@ def synthesize(args, hparams, model=None):
             chunk = group[i:i + per_call]
             c = np.stack([np.pad(mels[n], ((0, pad), (0, 0)), mode="edge") for n in chunk])
             z = torch.randn(len(chunk), t, 1, generator=gen) * hparams.temp     # synthesize.py:14
-            wav = model.reverse(z.cuda(), torch.from_numpy(c).cuda()).squeeze(-1).cpu().numpy()
-            for n, w in zip(chunk, wav):
-                write_wav(os.path.join(args.output_dir, n[:-4] + ".wav"), w[:frames * hop], hparams.sample_rate)
+            wav = model.reverse(z.cuda(), torch.from_numpy(c).cuda()).squeeze(-1)
+            out.write(chunk, wav, [frames * hop] * len(chunk))
     return names
 
 
@@ -167,6 +200,7 @@ def _synthesize_ragged(args, hparams, model, names, mels, done=()):
     hop = hparams.hop_size
     frames = [mels[n].shape[0] for n in names]
     keep = [k for k, n in enumerate(names) if n not in done]
+    out = _Output(args, hparams)
     for group in plan_batches([frames[k] for k in keep], int(args.batch), float(getattr(args, "max_pad_frac", 0.25)), hparams):
         group = [keep[j] for j in group]
         own = [_aligned_frames(frames[k], hparams) for k in group]        # frames of each clip after its own edge padding
@@ -177,9 +211,8 @@ def _synthesize_ragged(args, hparams, model, names, mels, done=()):
             c[row, :f] = np.pad(mels[names[k]], ((0, f - frames[k]), (0, 0)), mode="edge")
             gen = torch.Generator(device="cpu").manual_seed(int(args.seed) + k)
             z[row, :f * hop] = torch.randn(f * hop, 1, generator=gen) * hparams.temp
-        wav = model.reverse(z.cuda(), torch.from_numpy(c).cuda(), lengths=[f * hop for f in own]).squeeze(-1).cpu().numpy()
-        for row, k in enumerate(group):
-            write_wav(os.path.join(args.output_dir, names[k][:-4] + ".wav"), wav[row, :frames[k] * hop], hparams.sample_rate)
+        wav = model.reverse(z.cuda(), torch.from_numpy(c).cuda(), lengths=[f * hop for f in own]).squeeze(-1)
+        out.write([names[k] for k in group], wav, [frames[k] * hop for k in group])
     return names
 
 
@@ -280,7 +313,8 @@ def _synthesize_windowed(args, hparams, model, names, mels, window):
     from .windowing import plan_windows
     hop = hparams.hop_size
     device_rng = bool(getattr(args, "device_rng", False))
-    done = set()
+    out = _Output(args, hparams)                     # --out_rate (never with --device_rng): the whole clip is resampled on
+    done = set()                                     # the device, and comes down in pieces of the window's size
     for k, name in enumerate(names):
         frames = int(mels[name].shape[0])
         own = _aligned_frames(frames, hparams)
@@ -293,12 +327,16 @@ def _synthesize_windowed(args, hparams, model, names, mels, window):
             gen = torch.Generator(device="cpu").manual_seed(int(args.seed) + k)
             z = torch.randn(1, own * hop, 1, generator=gen) * hparams.temp
             audio = model.reverse_windowed(z.cuda(), c, window, batch=int(args.batch))[0, :, 0]
-        with wave.open(os.path.join(args.output_dir, name[:-4] + ".wav"), "wb") as w:
+        pieces = [(a, min(b, frames * hop)) for _, _, a, b in plan_windows(own * hop, window, hparams)]
+        if out.resampler is not None:
+            audio = out.resampler(audio[:frames * hop].contiguous())
+            pieces = [(a, min(a + window, len(audio))) for a in range(0, len(audio), window)]
+        with wave.open(out.path(name), "wb") as w:
             w.setnchannels(1)
             w.setsampwidth(2)
-            w.setframerate(int(hparams.sample_rate))
-            for _, _, a, b in plan_windows(own * hop, window, hparams):
-                part = audio[a:min(b, frames * hop)].cpu().numpy()
+            w.setframerate(out.rate)
+            for a, b in pieces:
+                part = audio[a:b].cpu().numpy()
                 if not device_rng:                   # write_wav's arithmetic
                     part = (np.clip(part.astype(np.float64), -1.0, 1.0) * 32767.0).round()
                 w.writeframes(np.ascontiguousarray(part, dtype="<i2").tobytes())
@@ -326,7 +364,15 @@ def main(argv=None):
     parser.add_argument("--window", type=int, default=argparse.SUPPRESS, metavar="SAMPLES",
                         help="synthesize clips longer than SAMPLES (rounded up to lcm(hop_size, 2^n_block)) window by window, each "
                              "with the network's receptive field of real context on both sides: no length limit, same audio")
+    parser.add_argument("--out_rate", type=int, default=argparse.SUPPRESS, metavar="HZ",
+                        help="resample the audio on the device to HZ before it is written (default: hparams.sample_rate, no "
+                             "resampling); the float paths only - not with --device_rng")
     args = parser.parse_args(argv)
+    if getattr(args, "out_rate", None) is not None:
+        if args.device_rng:
+            parser.error("--out_rate cannot be combined with --device_rng (the device path holds 16-bit PCM, not float audio)")
+        if args.out_rate < 1:
+            parser.error("--out_rate must be a positive rate in Hz")
     synthesize(args, hparams)
 
 
