@@ -906,6 +906,44 @@ int fwn_resample(const void* x, int x_pcm16, int64_t B, int64_t x_stride, int64_
                  int64_t len_host, const float* table_dev, int up, int down, int zeros, float* y, int64_t y_stride, int64_t m0,
                  int64_t n_out, void* stream);
 
+/* ---- spectral denoiser (additive; FWN_VERSION unchanged): STFT, bias-spectrum subtraction and inverse STFT on the device, so
+ * that synthesize --denoise keeps "only the mel goes up, only int16 comes down".  DESIGN.md 6b has the definition;
+ * tests/denoise_ref.py restates it in fp64.
+ *
+ * n_fft a power of two in 32..4096, 1 <= hop <= n_fft / 2, w[n] = 0.5 - 0.5 cos(2 pi n / n_fft), nb = n_fft / 2 + 1.  A clip of
+ * N samples has F = 1 + N div hop centred frames v_f[n] = w[n] x[j], j = f hop + n - n_fft / 2 reflected (j < 0 -> -j,
+ * j >= N -> 2 (N - 1) - j) - fwn_mel_spectrogram's framing; X[f][k] = sum_n v_f[n] e^(-2 pi i k n / n_fft), k < nb;
+ *     Y[f][k] = X[f][k] (1 - s b[k] / |X[f][k]|) where |X[f][k]| > s b[k], else 0          (s = strength, b = bias)
+ *     out[n] = sum_f w[p - f hop] irfft(Y[f])[p - f hop] / sum_f w[p - f hop]^2,  p = n + n_fft / 2
+ * both sums over the frames f <= F - 1 that cover p, in ascending f.  A clip of N < n_fft / 2 + 1 samples cannot be reflect-
+ * padded and is returned unchanged.
+ *
+ * fwn_denoise: one launch for B clips, no workspace (fwn_denoise_workspace_bytes is 0; workspace may be NULL).  x: row b at
+ * x + b * x_stride floats; clip b has N_b = len_dev[b] samples (DEVICE int64 [B], read on the device and clamped to
+ * [0, len_host]) or len_host when len_dev is NULL.  y (float, may be NULL) and pcm (int16, may be NULL; not both): rows at
+ * y + b * y_stride / pcm + b * pcm_stride; elements [0, len_host) of each row are written and nothing else: the result for
+ * i < N_b, exact +0 / PCM 0 from N_b on.  pcm = fwn_pcm16's arithmetic on the float result, bit for bit.  No sample at or past
+ * N_b is loaded.  A workgroup owns fwn_denoise_tile(n_fft, hop) consecutive samples and transforms the frames that cover them in
+ * LDS; a frame is computed by the same instructions whichever tile computes it, so an output's bits depend on the clip's samples
+ * within n_fft of it, on N_b, bias and strength only - not on B, the row, len_host or the tiling.  strength = 0 returns x to
+ * rounding ((16 log2 n_fft + 16) 2^-24 relative to the frames' norms: DESIGN.md 6b).  Refusals (FWN_ERR_ARG, before any launch):
+ * n_fft not a power of two in 32..4096; hop outside 1..n_fft/2; a null x, bias_dev or both outputs null; a pointer off its
+ * element's alignment (len_dev: 8); B outside 1..65535; len_host outside 1..2^40; a stride shorter than len_host (or above 2^44); a negative,
+ * infinite or NaN strength; a workspace smaller than fwn_denoise_workspace_bytes (or bytes at a null pointer); an output that
+ * overlaps the input.
+ *
+ * fwn_stft_mean_mag: mag_out[k] (DEVICE float [nb]) = the mean over the interior frames - those whose n_fft samples lie inside
+ * the clip: ceil(n_fft / 2 / hop) <= f <= (len_host - n_fft / 2) div hop - of the B rows (each len_host long) of |X[f][k]|,
+ * summed per bin in fp64 in frame order by one workgroup: the model's bias from a clip synthesized from nothing.  Refuses what
+ * fwn_denoise refuses of these arguments, a clip with no interior frame, and more than 2^20 interior frames in all.
+ * Speed: tools/bench_denoise.py. */
+int fwn_denoise_tile(int n_fft, int hop);
+size_t fwn_denoise_workspace_bytes(int64_t B, int64_t len_host, int n_fft, int hop);
+int fwn_stft_mean_mag(const float* x, int64_t B, int64_t x_stride, int64_t len_host, int n_fft, int hop, float* mag_out, void* stream);
+int fwn_denoise(const float* x, int64_t B, int64_t x_stride, const int64_t* len_dev, int64_t len_host, const float* bias_dev,
+                float strength, int n_fft, int hop, float* y, int64_t y_stride, int16_t* pcm, int64_t pcm_stride, void* workspace,
+                size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

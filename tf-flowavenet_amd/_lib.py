@@ -271,6 +271,10 @@ SIGNATURES = {
     "fwn_resample_taps": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "fwn_resample_design": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, vp]),
     "fwn_resample": (C.c_int, [vp, C.c_int, i64, i64, i64, i64, vp, i64, vp, C.c_int, C.c_int, C.c_int, vp, i64, i64, i64, vp]),
+    "fwn_denoise_tile": (C.c_int, [C.c_int, C.c_int]),
+    "fwn_denoise_workspace_bytes": (C.c_size_t, [i64, i64, C.c_int, C.c_int]),
+    "fwn_stft_mean_mag": (C.c_int, [vp, i64, i64, i64, C.c_int, C.c_int, vp, vp]),
+    "fwn_denoise": (C.c_int, [vp, i64, i64, vp, i64, vp, C.c_float, C.c_int, C.c_int, vp, i64, vp, i64, vp, C.c_size_t, vp]),
 }
 
 _lib = None

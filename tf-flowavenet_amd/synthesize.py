@@ -19,6 +19,10 @@ any more - and writes its wav core by core; the other clips take the paths above
 float audio on the device before it is written (``resample.Resampler``: a clip's true samples, ``frames * hop`` of them, not its
 padding -> ``ceil(frames * hop * HZ / sample_rate)`` samples, ``write_wav``'s arithmetic, ``HZ`` in the header) on the default
 path, with ``--ragged`` and with ``--window``; with ``--device_rng`` - which holds 16-bit PCM, not float audio - it is an error.
+``--denoise STRENGTH`` (opt-in) subtracts the model's bias spectrum from every clip on the device (``denoise.Denoiser``: STFT,
+soft threshold of the magnitudes by ``STRENGTH`` times the spectrum of what the model synthesizes from nothing, inverse STFT) -
+a clip's true samples, before ``--out_rate`` resamples them; with ``--device_rng`` the float waveform stays on the device and
+still only int16 comes down; with ``--window`` the stitched clip is denoised whole.
 """
 from __future__ import annotations
 
@@ -129,8 +133,8 @@ class _Output:
     device (``resample.Resampler``), ``n_out(length)`` samples per clip come down, and ``write_wav`` writes them with ``HZ`` in
     the header."""
 
-    def __init__(self, args, hparams):
-        self.dir, self.rate, self.resampler = args.output_dir, int(hparams.sample_rate), None
+    def __init__(self, args, hparams, denoiser=None):
+        self.dir, self.rate, self.resampler, self.denoiser = args.output_dir, int(hparams.sample_rate), None, denoiser
         out_rate = getattr(args, "out_rate", None)
         if out_rate is not None:
             if int(out_rate) < 1:
@@ -143,12 +147,23 @@ class _Output:
 
     def write(self, names, wav, lengths):
         """``wav``: device float32 [B, T]; clip b is ``names[b]`` with ``lengths[b]`` true samples."""
+        if self.denoiser is not None:                # --denoise: at the model's rate, the true samples only
+            wav = self.denoiser(wav, lengths=lengths)
         if self.resampler is not None:
             wav = self.resampler(wav, lengths=lengths)
             lengths = [self.resampler.out_length(n) for n in lengths]
         wav = wav.cpu().numpy()
         for n, w, length in zip(names, wav, lengths):
             write_wav(self.path(n), w[:length], self.rate)
+
+
+def _denoiser(args, model):
+    """``--denoise STRENGTH`` -> the model's ``Denoiser`` (its bias is computed here, once per run); None without the flag."""
+    strength = getattr(args, "denoise", None)
+    if strength is None:
+        return None
+    from .denoise import Denoiser
+    return Denoiser(model, strength=strength)
 
 
 def synthesize(args, hparams, model=None):
@@ -158,22 +173,23 @@ def synthesize(args, hparams, model=None):
         raise ValueError("--out_rate applies to the float paths: it cannot be combined with --device_rng")
     if model is None:
         model = FloWaveNet(hparams).load_params(load_checkpoint(args.saved_dir))
+    denoiser = _denoiser(args, model)
     os.makedirs(args.output_dir, exist_ok=True)
     names = sorted(f for f in os.listdir(args.mels_dir) if f.endswith(".npy"))
     mels = {n: np.load(os.path.join(args.mels_dir, n)).astype(np.float32) for n in names}
     done = set()                                     # --window: the clips longer than it, written window by window
     if getattr(args, "window", None) is not None:
-        done = _synthesize_windowed(args, hparams, model, names, mels, window_samples(args.window, hparams))
+        done = _synthesize_windowed(args, hparams, model, names, mels, window_samples(args.window, hparams), denoiser)
     if getattr(args, "device_rng", False):
-        return _synthesize_device(args, hparams, model, names, mels, done)
+        return _synthesize_device(args, hparams, model, names, mels, done, denoiser)
     if getattr(args, "ragged", False):
-        return _synthesize_ragged(args, hparams, model, names, mels, done)
+        return _synthesize_ragged(args, hparams, model, names, mels, done, denoiser)
     by_len = {}
     for n in names:
         if n not in done:
             by_len.setdefault(mels[n].shape[0], []).append(n)
     gen = torch.Generator(device="cpu").manual_seed(int(args.seed))
-    out = _Output(args, hparams)
+    out = _Output(args, hparams, denoiser)
     hop = hparams.hop_size
     align = max(1, (1 << hparams.n_block) // np.gcd(1 << hparams.n_block, hop))
     for frames, group in sorted(by_len.items()):
@@ -192,7 +208,7 @@ def synthesize(args, hparams, model=None):
     return names
 
 
-def _synthesize_ragged(args, hparams, model, names, mels, done=()):
+def _synthesize_ragged(args, hparams, model, names, mels, done=(), denoiser=None):
     """``--ragged``: clips of similar length share a call (``plan_batches``).  Each clip is edge-padded to the model's
     alignment as without the flag - that is its ``length`` - and zero-padded from there to the group's T; clip k (in sorted
     file-name order) draws its z from ``torch.Generator().manual_seed(seed + k)``.  ``done``: names ``--window`` has written."""
@@ -200,7 +216,7 @@ def _synthesize_ragged(args, hparams, model, names, mels, done=()):
     hop = hparams.hop_size
     frames = [mels[n].shape[0] for n in names]
     keep = [k for k, n in enumerate(names) if n not in done]
-    out = _Output(args, hparams)
+    out = _Output(args, hparams, denoiser)
     for group in plan_batches([frames[k] for k in keep], int(args.batch), float(getattr(args, "max_pad_frac", 0.25)), hparams):
         group = [keep[j] for j in group]
         own = [_aligned_frames(frames[k], hparams) for k in group]        # frames of each clip after its own edge padding
@@ -236,13 +252,15 @@ def device_batches(frame_counts, args, hparams):
     return groups
 
 
-def synthesize_device(model, hparams, mel_list, groups, seed, ragged, emit):
+def synthesize_device(model, hparams, mel_list, groups, seed, ragged, emit, denoiser=None):
     """The device path over ``groups`` (lists of indices into ``mel_list``, arrays [F, num_mels]): per group one upload of the
     padded mels, one ``FloWaveNet.synthesize`` - clip k draws the z of (seed, clip id k) - and one non-blocking copy of the int16
     result into one of two pinned host buffers.  ``emit(k, pcm)`` gets clip k's samples (a view of the pinned buffer, valid
     during the call) once the group's copy has landed - and that is after the NEXT group has been enqueued, so the device
     works while the host writes files.  One event orders it: recorded behind each copy and waited for before that copy's buffer
-    is read; the buffers alternate, so the copy enqueued next never lands in the one being read."""
+    is read; the buffers alternate, so the copy enqueued next never lands in the one being read.  ``denoiser`` (``--denoise``):
+    the call also returns its float waveform, which stays on the device; the denoiser turns each clip's true samples into the
+    int16 that comes down, on the same stream."""
     import torch
     hop = hparams.hop_size
     frames = [int(m.shape[0]) for m in mel_list]
@@ -265,8 +283,13 @@ def synthesize_device(model, hparams, mel_list, groups, seed, ragged, emit):
             c[row, :f] = np.pad(mel_list[k], ((0, f - frames[k]), (0, 0)), mode="edge")
         if not ragged and min(own) != top:
             raise ValueError("clips of different lengths share a call only with ragged=True")
-        pcm = model.synthesize(torch.from_numpy(c).cuda(), seed, clip_ids=list(group),
-                               lengths=[f * hop for f in own] if ragged else None)
+        if denoiser is None:
+            pcm = model.synthesize(torch.from_numpy(c).cuda(), seed, clip_ids=list(group),
+                                   lengths=[f * hop for f in own] if ragged else None)
+        else:
+            wav = model.synthesize(torch.from_numpy(c).cuda(), seed, clip_ids=list(group),
+                                   lengths=[f * hop for f in own] if ragged else None, return_wav=True)[1]
+            pcm = denoiser(wav[:, :, 0], lengths=[frames[k] * hop for k in group], pcm=True)
         if pending is not None:
             flush()                                  # the previous group: its buffer is the OTHER one
         need = len(group) * top * hop
@@ -279,7 +302,7 @@ def synthesize_device(model, hparams, mel_list, groups, seed, ragged, emit):
         flush()
 
 
-def _synthesize_device(args, hparams, model, names, mels, done=()):
+def _synthesize_device(args, hparams, model, names, mels, done=(), denoiser=None):
     """``--device_rng``: clip k (in sorted file-name order) has clip id k under ``--seed``, with and without ``--ragged`` - the
     same seed gives a clip the same z in either mode; the padding rules are those of the host paths.  ``done``: names
     ``--window`` has written (they keep their index: the other clips' ids do not move)."""
@@ -290,7 +313,7 @@ def _synthesize_device(args, hparams, model, names, mels, done=()):
     def emit(k, pcm):
         write_wav_pcm(os.path.join(args.output_dir, names[k][:-4] + ".wav"), pcm, hparams.sample_rate)
 
-    synthesize_device(model, hparams, mel_list, groups, int(args.seed), bool(getattr(args, "ragged", False)), emit)
+    synthesize_device(model, hparams, mel_list, groups, int(args.seed), bool(getattr(args, "ragged", False)), emit, denoiser)
     return names
 
 
@@ -302,13 +325,15 @@ def window_samples(window, hparams):
     return round_up_to_unit(window, hparams)
 
 
-def _synthesize_windowed(args, hparams, model, names, mels, window):
+def _synthesize_windowed(args, hparams, model, names, mels, window, denoiser=None):
     """``--window``: every clip longer than ``window`` samples (after its edge padding), one at a time, through
     ``FloWaveNet.synthesize_windowed`` (``--device_rng``: clip id = the clip's index in sorted file-name order, as without the
     flag) or ``FloWaveNet.reverse_windowed`` (z drawn on the host from ``torch.Generator().manual_seed(seed + index)``, the
     per-clip generator of ``--ragged``), ``--batch`` windows per call.  The result stays on the device and comes down core by
     core into ``wave``'s incremental ``writeframes``: the host never holds more than one window of audio, and no clip is too
-    long for one call.  -> the set of names written."""
+    long for one call.  ``denoiser`` (``--denoise``): the stitched clip is whole on the device - its true samples are denoised
+    whole there (with ``--device_rng`` from the float waveform to int16), before ``--out_rate`` resamples them.  -> the set of
+    names written."""
     import torch
     from .windowing import plan_windows
     hop = hparams.hop_size
@@ -322,11 +347,17 @@ def _synthesize_windowed(args, hparams, model, names, mels, window):
             continue
         c = torch.from_numpy(np.pad(mels[name], ((0, own - frames), (0, 0)), mode="edge")[None]).cuda()
         if device_rng:
-            audio = model.synthesize_windowed(c, int(args.seed), clip_ids=[k], window=window, batch=int(args.batch))[0]
+            if denoiser is None:
+                audio = model.synthesize_windowed(c, int(args.seed), clip_ids=[k], window=window, batch=int(args.batch))[0]
+            else:
+                wav = model.synthesize_windowed(c, int(args.seed), clip_ids=[k], window=window, batch=int(args.batch), return_wav=True)[1]
+                audio = denoiser(wav[0, :frames * hop, 0], pcm=True)
         else:
             gen = torch.Generator(device="cpu").manual_seed(int(args.seed) + k)
             z = torch.randn(1, own * hop, 1, generator=gen) * hparams.temp
             audio = model.reverse_windowed(z.cuda(), c, window, batch=int(args.batch))[0, :, 0]
+            if denoiser is not None:
+                audio = denoiser(audio[:frames * hop])
         pieces = [(a, min(b, frames * hop)) for _, _, a, b in plan_windows(own * hop, window, hparams)]
         if out.resampler is not None:
             audio = out.resampler(audio[:frames * hop].contiguous())
@@ -367,6 +398,10 @@ def main(argv=None):
     parser.add_argument("--out_rate", type=int, default=argparse.SUPPRESS, metavar="HZ",
                         help="resample the audio on the device to HZ before it is written (default: hparams.sample_rate, no "
                              "resampling); the float paths only - not with --device_rng")
+    from .denoise import strength_arg
+    parser.add_argument("--denoise", type=strength_arg, default=argparse.SUPPRESS, metavar="STRENGTH",
+                        help="subtract STRENGTH times the model's bias spectrum (what it synthesizes from nothing) from every "
+                             "clip's STFT magnitudes on the device; a finite number >= 0, typically 0.01 - 0.1")
     args = parser.parse_args(argv)
     if getattr(args, "out_rate", None) is not None:
         if args.device_rng:
