@@ -944,6 +944,43 @@ int fwn_denoise(const float* x, int64_t B, int64_t x_stride, const int64_t* len_
                 float strength, int n_fft, int hop, float* y, int64_t y_stride, int16_t* pcm, int64_t pcm_stride, void* workspace,
                 size_t workspace_bytes, void* stream);
 
+/* ---- ragged mel front-end (additive; FWN_VERSION unchanged): peak normalisation, the log-mel spectrogram through the denoiser's
+ * LDS FFT and the reference's centre-padded audio for B clips of different lengths, in two launches.  DESIGN.md 6c has the
+ * definition; tests/mel_front_ref.py restates it.  fwn_mel_spectrogram (one rectangle, direct DFT) is untouched.
+ *
+ * Framing as above: n_fft a power of two in 32..4096, 1 <= hop <= n_fft / 2, nb = n_fft / 2 + 1, a clip of N samples has
+ * F = 1 + N div hop centred, reflect-padded frames under the periodic Hann window.  x: row b at x + b * x_stride floats; clip b
+ * has N_b = len_dev[b] samples (DEVICE int64 [B], read on the device and clamped to [0, len_host]) or len_host when len_dev is
+ * NULL; no sample at or past N_b is loaded.  F_host = 1 + len_host div hop.
+ *
+ * fwn_clip_peak: peak_out[b] (DEVICE float [B]) = max_{i < N_b} |x[i]|: +0 for an empty clip, NaN if any sample is NaN, else
+ * exact (an integer maximum over the bit patterns: the result does not depend on B, the row, the stride or the order).  A clip
+ * is split over workgroups of 16384 samples; the output need not be cleared (a memset node precedes the one launch).
+ *
+ * fwn_mel_front: one launch, no workspace.  xn[i] = (x[i] / peak_dev[b]) * rmax - two separately rounded fp32 operations, the
+ * division IEEE: the float32 arithmetic of the reference's wav / max|wav| * rescaling_max - or xn = x when peak_dev is NULL.
+ *     P[f][m] = sum_k fb[m][k] |X_f[k]|^2 (ascending k, fmaf), X_f the transform of frame f of xn,
+ *     mel[f][m] = clip((20 log10(max(1e-4, P[f][m])) - ref_level_db - min_level_db) / -min_level_db, 0, 1)
+ * fb: DEVICE float [n_mels][nb], dense.  bands (DEVICE int32 [n_mels][2], may be NULL): first and one-past-last non-zero bin of
+ * each row of fb; it restricts the k loop and, for finite input, changes no bit (a skipped term is fmaf(0, p, acc) = acc).
+ * mel: row b at mel + b * mel_stride floats, [F_host][n_mels]: rows f < F_b hold the result, rows F_b <= f < F_host exact +0.
+ * audio (may be NULL): row b at audio + b * audio_stride floats, F_host * hop samples: audio[i] = xn[i - pad_l] for
+ * pad_l <= i < pad_l + N_b, pad_l = (F_b hop - N_b) div 2, and +0 elsewhere - the reference's padded, trimmed clip.  Nothing else
+ * is written.  A clip whose peak is not > 0 (silent, NaN) or with N_b < n_fft / 2 + 1 (cannot be reflected) gets all-zero mel
+ * and audio rows.  A workgroup owns fwn_mel_front_frames(n_fft, hop) consecutive frames of one clip; a frame is computed by the
+ * same instructions wherever it lands, so mel[f]'s bits depend on the clip's samples in the frame's support, on N_b, peak[b],
+ * rmax and fb only - not on B, the row, len_host or the grid.  Error against fp64: tests/mel_front_ref.py bound().
+ * Refusals (FWN_ERR_ARG, before any launch): n_fft not a power of two in 32..4096; hop outside 1..n_fft/2; a null x, fb, mel or
+ * peak_out; a pointer off its element's alignment (len_dev: 8); B outside 1..65535; len_host outside 1..2^40; a stride shorter
+ * than the row it holds (or above 2^44); min_level_db >= 0; a non-finite rmax, or rmax <= 0 with peak_dev; n_mels outside
+ * 1..1024; more than 2^31 - 1 workgroups per row; an output that overlaps the input.
+ * Speed: tools/bench_mel.py. */
+int fwn_mel_front_frames(int n_fft, int hop);
+int fwn_clip_peak(const float* x, int64_t B, int64_t x_stride, const int64_t* len_dev, int64_t len_host, float* peak_out, void* stream);
+int fwn_mel_front(const float* x, int64_t B, int64_t x_stride, const int64_t* len_dev, int64_t len_host, const float* peak_dev, float rmax,
+                  const float* fb, const int32_t* bands, int n_fft, int hop, int n_mels, float ref_level_db, float min_level_db, float* mel,
+                  int64_t mel_stride, float* audio, int64_t audio_stride, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

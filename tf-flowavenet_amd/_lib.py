@@ -275,6 +275,10 @@ SIGNATURES = {
     "fwn_denoise_workspace_bytes": (C.c_size_t, [i64, i64, C.c_int, C.c_int]),
     "fwn_stft_mean_mag": (C.c_int, [vp, i64, i64, i64, C.c_int, C.c_int, vp, vp]),
     "fwn_denoise": (C.c_int, [vp, i64, i64, vp, i64, vp, C.c_float, C.c_int, C.c_int, vp, i64, vp, i64, vp, C.c_size_t, vp]),
+    "fwn_mel_front_frames": (C.c_int, [C.c_int, C.c_int]),
+    "fwn_clip_peak": (C.c_int, [vp, i64, i64, vp, i64, vp, vp]),
+    "fwn_mel_front": (C.c_int, [vp, i64, i64, vp, i64, vp, C.c_float, vp, vp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, vp, i64,
+                                vp, i64, vp]),
 }
 
 _lib = None

@@ -23,6 +23,10 @@ path, with ``--ragged`` and with ``--window``; with ``--device_rng`` - which hol
 soft threshold of the magnitudes by ``STRENGTH`` times the spectrum of what the model synthesizes from nothing, inverse STFT) -
 a clip's true samples, before ``--out_rate`` resamples them; with ``--device_rng`` the float waveform stays on the device and
 still only int16 comes down; with ``--window`` the stitched clip is denoised whole.
+``--wavs_dir DIR`` (opt-in, instead of ``--mels_dir``) is copy-synthesis: every ``DIR/*.wav`` (any PCM rate: ``load_wav``'s reader
+and resampler) goes through ``preprocessing.MelFrontEnd`` in ragged batches of ``--batch``, normalised as ``preprocess``
+normalises, and its mel enters the paths above as the ``.npy`` of the same name would; the mel comes down to the host and goes
+up again with its batch - keeping it on the device between front-end and model is the cut not made.
 """
 from __future__ import annotations
 
@@ -166,6 +170,24 @@ def _denoiser(args, model):
     return Denoiser(model, strength=strength)
 
 
+def mels_from_wavs(wavs_dir, hparams, batch):
+    """``--wavs_dir``: every ``*.wav`` in sorted order -> (names, name -> mel float32 [F, num_mels]), ``batch`` files per
+    ``MelFrontEnd`` call (any PCM rate: resampled on the device; peak-normalised as ``preprocess`` normalises)."""
+    from .preprocessing import MelFrontEnd, load_wavs
+    names = sorted(f for f in os.listdir(wavs_dir) if f.endswith(".wav"))
+    front, resamplers, mels = MelFrontEnd(hparams), {}, {}
+    for i in range(0, len(names), batch):
+        group = names[i:i + batch]
+        x, lengths = load_wavs([os.path.join(wavs_dir, n) for n in group], hparams.sample_rate, resamplers)
+        _, mel, peak = front(x, lengths=lengths, audio=False)
+        mel, peak = mel.cpu().numpy(), peak.cpu().numpy()
+        for row, n in enumerate(group):
+            if not peak[row] > 0.0:
+                raise ValueError("%s: silent clip: normalisation divides by max|wav|" % os.path.join(wavs_dir, n))
+            mels[n] = mel[row, :1 + lengths[row] // hparams.hop_size].copy()
+    return names, mels
+
+
 def synthesize(args, hparams, model=None):
     import torch
     from .model import FloWaveNet
@@ -175,8 +197,11 @@ def synthesize(args, hparams, model=None):
         model = FloWaveNet(hparams).load_params(load_checkpoint(args.saved_dir))
     denoiser = _denoiser(args, model)
     os.makedirs(args.output_dir, exist_ok=True)
-    names = sorted(f for f in os.listdir(args.mels_dir) if f.endswith(".npy"))
-    mels = {n: np.load(os.path.join(args.mels_dir, n)).astype(np.float32) for n in names}
+    if getattr(args, "wavs_dir", None) is not None:
+        names, mels = mels_from_wavs(args.wavs_dir, hparams, int(args.batch))
+    else:
+        names = sorted(f for f in os.listdir(args.mels_dir) if f.endswith(".npy"))
+        mels = {n: np.load(os.path.join(args.mels_dir, n)).astype(np.float32) for n in names}
     done = set()                                     # --window: the clips longer than it, written window by window
     if getattr(args, "window", None) is not None:
         done = _synthesize_windowed(args, hparams, model, names, mels, window_samples(args.window, hparams), denoiser)
@@ -375,11 +400,19 @@ def _synthesize_windowed(args, hparams, model, names, mels, window, denoiser=Non
     return done
 
 
+class _Given(argparse.Action):
+    """Stores the value and notes that the option was given explicitly (``--wavs_dir`` refuses an explicit ``--mels_dir``)."""
+
+    def __call__(self, parser, namespace, values, option_string=None):
+        setattr(namespace, self.dest, values)
+        namespace._given = getattr(namespace, "_given", ()) + (self.dest,)
+
+
 def main(argv=None):
     from .hparams import hparams
     parser = argparse.ArgumentParser()
     parser.add_argument("--saved_dir", default="logs/pretrained/", help="Folder with model checkpoint")
-    parser.add_argument("--mels_dir", default="mels/", help="folder to contain mels to synthesize audio from using the model")
+    parser.add_argument("--mels_dir", default="mels/", action=_Given, help="folder to contain mels to synthesize audio from using the model")
     parser.add_argument("--output_dir", default="output/", help="folder to contain synthesized audio files")
     parser.add_argument("--seed", type=int, default=hparams.tf_random_seed, help="seed of the latent z")
     parser.add_argument("--batch", type=int, default=8, help="mels per launch (of equal length; of similar length with --ragged)")
@@ -402,7 +435,13 @@ def main(argv=None):
     parser.add_argument("--denoise", type=strength_arg, default=argparse.SUPPRESS, metavar="STRENGTH",
                         help="subtract STRENGTH times the model's bias spectrum (what it synthesizes from nothing) from every "
                              "clip's STFT magnitudes on the device; a finite number >= 0, typically 0.01 - 0.1")
+    parser.add_argument("--wavs_dir", default=argparse.SUPPRESS, metavar="DIR",
+                        help="copy-synthesis: take the mels from DIR/*.wav (any PCM rate; normalised as preprocess normalises) "
+                             "through the device front-end instead of --mels_dir/*.npy")
     args = parser.parse_args(argv)
+    given = vars(args).pop("_given", ())             # not part of the namespace the paths see
+    if getattr(args, "wavs_dir", None) is not None and "mels_dir" in given:
+        parser.error("--wavs_dir cannot be combined with --mels_dir: the mels come from one or the other")
     if getattr(args, "out_rate", None) is not None:
         if args.device_rng:
             parser.error("--out_rate cannot be combined with --device_rng (the device path holds 16-bit PCM, not float audio)")
