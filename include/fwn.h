@@ -981,6 +981,46 @@ int fwn_mel_front(const float* x, int64_t B, int64_t x_stride, const int64_t* le
                   const float* fb, const int32_t* bands, int n_fft, int hop, int n_mels, float ref_level_db, float min_level_db, float* mel,
                   int64_t mel_stride, float* audio, int64_t audio_stride, void* stream);
 
+/* ---- spectral distances (additive; FWN_VERSION unchanged): how close a test clip is to its target - mel L1, log-spectral
+ * distance and spectral convergence of B pairs of clips of different lengths, through the same LDS FFT, in two launches; no
+ * spectrogram is written to memory and four doubles per pair come out.  DESIGN.md 6d has the definition; tests/specdist_ref.py
+ * restates it in fp64.
+ *
+ * Framing as above: n_fft a power of two in 32..4096, 1 <= hop <= n_fft / 2, nb = n_fft / 2 + 1.  Pair b is x (the target), row b
+ * at x + b * x_stride floats, and y (the test), row b at y + b * y_stride floats, both of N_b = len_dev[b] samples (DEVICE int64
+ * [B], read on the device and clamped to [0, len_host]) or len_host when len_dev is NULL; no sample at or past N_b is loaded; x
+ * and y are only read and may overlap each other.  F_b = 1 + N_b div hop frames; X_f, Y_f the transforms of frame f; Px = |X|^2,
+ * Py = |Y|^2 in fp32 as fwn_mel_front forms them.
+ *     mel_l1 = mean_{f < F_b, m < n_mels} |mel_x[f][m] - mel_y[f][m]|, mel_* being fwn_mel_front's mel with peak_dev NULL - the
+ *              same filter loop over fb (and bands), dB and clip: the distance in the space the model is conditioned on, in
+ *              fractions of -min_level_db.  NaN when fb is NULL (n_mels, bands and the dB constants are then unused).
+ *     lsd_db = mean_f sqrt( mean_{k < nb} (10 log10 max(floor, Px) - 10 log10 max(floor, Py))^2 )
+ *     sc     = sqrt( sum_{f,k} (sqrt Px - sqrt Py)^2 ) / sqrt( sum_{f,k} Px );  the IEEE quotient when the target's spectrum is
+ *              all zero: NaN for 0 / 0, +inf otherwise
+ * The terms are fp32, every sum fp64.  out: DEVICE double [B][4] = mel_l1, lsd_db, sc, F_b.  A pair with N_b < n_fft / 2 + 1
+ * cannot be reflected: NaN, NaN, NaN, 0.  Nothing else is written but the workspace.
+ *
+ * First launch: a workgroup owns fwn_spectral_distance_frames(n_fft, hop) consecutive frames of one pair, transforms frame f of
+ * x and of y (side by side; one after the other at n_fft 2048 and 4096), adds the terms with lanes on fixed bins through a fixed
+ * shuffle-and-LDS tree, and stores four partials (sum |dmel|, sum_f lsd_f, sum (|X| - |Y|)^2, sum |X|^2) at [b][workgroup] of
+ * the workspace (fwn_spectral_distance_workspace_bytes: B * ceil(F_host / frames) * 32, F_host = 1 + len_host div hop; 0 for
+ * arguments fwn_spectral_distance refuses; need not be cleared).  Second launch: one wave per pair adds the partials
+ * 0 .. ceil(F_b / frames) - 1 in an order that F_b alone decides, divides and takes the roots.  No atomics, no synchronisation
+ * with the host.  A pair's four doubles depend on its two sets of samples, N_b, fb, the dB constants and floor only - not on B,
+ * the row, the strides, len_host, the grid or bands (for finite input a skipped term is fmaf(0, p, acc) = acc).
+ * Error against fp64: tests/specdist_ref.py bound().
+ * Refusals (FWN_ERR_ARG, before any launch): n_fft not a power of two in 32..4096; hop outside 1..n_fft/2; a null x, y or out; a
+ * pointer off its element's alignment (len_dev, out, workspace: 8); B outside 1..65535; len_host outside 1..2^40; a stride
+ * shorter than len_host (or above 2^44); with fb: n_mels outside 1..1024, min_level_db >= 0; bands without fb; a floor that is
+ * not finite or not > 0; a null workspace or one smaller than fwn_spectral_distance_workspace_bytes; out or the workspace
+ * overlapping an input or each other; more than 2^31 - 1 workgroups per row.
+ * Speed: tools/bench_specdist.py. */
+int fwn_spectral_distance_frames(int n_fft, int hop);
+size_t fwn_spectral_distance_workspace_bytes(int64_t B, int64_t len_host, int n_fft, int hop);
+int fwn_spectral_distance(const float* x, int64_t x_stride, const float* y, int64_t y_stride, int64_t B, const int64_t* len_dev,
+                          int64_t len_host, const float* fb, const int32_t* bands, int n_fft, int hop, int n_mels, float ref_level_db,
+                          float min_level_db, float floor, double* out, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

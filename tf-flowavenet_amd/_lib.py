@@ -279,6 +279,10 @@ SIGNATURES = {
     "fwn_clip_peak": (C.c_int, [vp, i64, i64, vp, i64, vp, vp]),
     "fwn_mel_front": (C.c_int, [vp, i64, i64, vp, i64, vp, C.c_float, vp, vp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, vp, i64,
                                 vp, i64, vp]),
+    "fwn_spectral_distance_frames": (C.c_int, [C.c_int, C.c_int]),
+    "fwn_spectral_distance_workspace_bytes": (C.c_size_t, [i64, i64, C.c_int, C.c_int]),
+    "fwn_spectral_distance": (C.c_int, [vp, i64, vp, i64, i64, vp, i64, vp, vp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
+                                        C.c_float, vp, vp, C.c_size_t, vp]),
 }
 
 _lib = None

@@ -369,6 +369,7 @@ def train(log_dir, args, hparams, input_path, device="cuda", params=None):
     # this very loop, so all of them accumulate the same number of times per update.  Steps, the rate schedule and every
     # interval below count updates, and a checkpoint is only ever written between two updates: no pending state to save.
     accum_steps = int(getattr(args, "accum_steps", 1))
+    eval_metric = None                                                       # --eval_metrics: built at the first evaluation
     while step < args.train_steps:
         start_time = time.time()
         clip_lengths = []
@@ -427,9 +428,19 @@ def train(log_dir, args, hparams, input_path, device="cuda", params=None):
             model = FloWaveNet(hparams, device=device, cond_mode=1).load_params(trainer.opt.master_views())
             g = torch.Generator().manual_seed(step)
             z = torch.randn(1, len(wav), 1, generator=g) * hparams.temp
-            pred = model.reverse(z, torch.from_numpy(mel[None])).reshape(-1).cpu().numpy()
+            pred_dev = model.reverse(z, torch.from_numpy(mel[None])).reshape(-1)
+            pred = pred_dev.cpu().numpy()
             write_wav(os.path.join(train_logdir, "predictions-%d.wav" % step), pred, hparams.sample_rate)
             write_wav(os.path.join(train_logdir, "targets-%d.wav" % step), wav, hparams.sample_rate)
+            if bool(getattr(args, "eval_metrics", False)):                   # the same prediction against its target, on the device
+                from .evaluate import eval_record
+                from .metrics import SpectralDistance
+                if eval_metric is None:
+                    eval_metric = SpectralDistance(hparams, device=device)
+                target = torch.from_numpy(np.ascontiguousarray(wav, dtype=np.float32).reshape(-1)).to(pred_dev.device)
+                eval_logdir = os.path.join(log_dir, "eval")
+                os.makedirs(eval_logdir, exist_ok=True)
+                log(eval_logdir, eval_record(step, eval_metric.dist(target, pred_dev)))
     return save_dir
 
 
@@ -467,6 +478,10 @@ def main(argv=None):
                              "keyed by seed, rank and a draw counter on the device: not the host draws of a run without the flag); "
                              "checkpoints then carry the counter and a restored run continues the data stream; every rank holds the "
                              "whole corpus; combines with --ragged and --accum_steps")
+    parser.add_argument("--eval_metrics", action="store_true",
+                        help="at --eval_interval also measure the evaluation sample's prediction against its target on the device "
+                             "(metrics.SpectralDistance: mel L1, log-spectral distance, spectral convergence) and append the "
+                             "record to <log_dir>/eval/summary.jsonl; the two wavs are written as without the flag")
     args = parser.parse_args(argv)
     import torch
     import torch.distributed as dist
