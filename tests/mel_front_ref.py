@@ -6,6 +6,7 @@ the mel's bound; and that bound, per element, from the transform's error constan
 """
 import numpy as np
 
+from denoise_ref import frame_index
 from oracle import mel_np as onp
 from tf_flowavenet_amd.hparams import default_hparams
 
@@ -51,11 +52,7 @@ def padded_audio(xn, hop):
 def frames64(xn, n_fft, hop):
     """v_f[n] = w[n] xn[j], j = f hop + n - n_fft / 2 reflected, in fp64: [F, n_fft]."""
     xn = np.asarray(xn, dtype=np.float64)
-    n = len(xn)
-    j = np.arange(frames_of(n, hop))[:, None] * hop + np.arange(n_fft)[None, :] - n_fft // 2
-    j = np.where(j < 0, -j, j)
-    j = np.where(j >= n, 2 * (n - 1) - j, j)
-    return xn[j] * onp.hann_periodic(n_fft)[None, :]
+    return xn[frame_index(len(xn), n_fft, hop)] * onp.hann_periodic(n_fft)[None, :]
 
 
 def db(power, hp):
@@ -82,15 +79,22 @@ def front(x, hp, normalize=True):
     return padded_audio(xn, hp.hop_size), onp.melspectrogram(xn.astype(np.float64), hp), pk, xn
 
 
+def frame_terms(xn, n_fft, hop):
+    """The per-frame terms of ``bound`` (and of ``specdist_ref.bound``) for one clip: |X| [F, nb]; e [F, 1], e_f = (16 L + 16) u
+    ||v_f||_2, which bounds every bin's error after the transform (DESIGN.md 6b's constant); and dpw [F, nb] = 2 |X| e + e^2 +
+    4 u |X|^2, that of the power."""
+    v = frames64(xn, n_fft, hop)
+    X = np.abs(np.fft.rfft(v, axis=1))
+    e = ((16 * np.log2(n_fft) + 16) * U * np.linalg.norm(v, axis=1))[:, None]
+    return X, e, 2 * X * e + e ** 2 + 4 * U * X ** 2
+
+
 def bound(xn, hp, fb):
     """The per-element bound of a float32 evaluation of the mel of the float32 samples ``xn``: [F, num_mels].
-    e_f = (16 L + 16) u ||v_f||_2 bounds every bin's error after the transform (DESIGN.md 6b's constant);
-    dpw = 2 |X| e + e^2 + 4 u |X|^2 that of the power; dP = fb dpw + (nb + 2) u P that of the filter sum; and the log carries it as
+    ``frame_terms`` gives e_f and dpw, the error of a bin after the transform and of its power; dP = fb dpw + (nb + 2) u P is that
+    of the filter sum; and the log carries it as
     c dP / max(1e-4, P - dP), c = (20 / ln 10) / |min_level_db|, plus 32 u for the log, the affine map and the clip."""
-    v = frames64(xn, hp.n_fft, hp.hop_size)
-    X = np.abs(np.fft.rfft(v, axis=1))
-    e = ((16 * np.log2(hp.n_fft) + 16) * U * np.linalg.norm(v, axis=1))[:, None]
-    dpw = 2 * X * e + e ** 2 + 4 * U * X ** 2
+    X, _, dpw = frame_terms(xn, hp.n_fft, hp.hop_size)
     fb = np.asarray(fb, dtype=np.float64)
     P = (X ** 2) @ fb.T
     dP = dpw @ fb.T + (hp.n_fft // 2 + 3) * U * P

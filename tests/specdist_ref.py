@@ -89,14 +89,6 @@ def dist32(x, y, n_fft, hop, hp=None, fb=None, floor=FLOOR):
     return mel, lsd, sc, MR.frames_of(len(x), hop)
 
 
-def _frame_terms(c, n_fft, hop):
-    """mel_front_ref.bound's per-frame terms of one clip: |X| [F, nb], e [F, 1], dpw [F, nb]."""
-    v = MR.frames64(c, n_fft, hop)
-    X = np.abs(np.fft.rfft(v, axis=1))
-    e = ((16 * np.log2(n_fft) + 16) * U * np.linalg.norm(v, axis=1))[:, None]
-    return X, e, 2 * X * e + e ** 2 + 4 * U * X ** 2
-
-
 def bound(x, y, n_fft, hop, hp=None, fb=None, floor=FLOOR):
     """-> (b_mel, b_lsd, b_sc): what a float32 evaluation of ``dist`` may differ from it by.
 
@@ -111,8 +103,8 @@ def bound(x, y, n_fft, hop, hp=None, fb=None, floor=FLOOR):
             denominator D = ||X|| by Ex + u D, and the quotient by (dn + sc dD) / (D - dD)."""
     x, y = np.asarray(x, dtype=np.float32), np.asarray(y, dtype=np.float32)
     nb = n_fft // 2 + 1
-    X, ex, dpx = _frame_terms(x, n_fft, hop)
-    Y, ey, dpy = _frame_terms(y, n_fft, hop)
+    X, ex, dpx = MR.frame_terms(x, n_fft, hop)
+    Y, ey, dpy = MR.frame_terms(y, n_fft, hop)
     b_mel = float("nan")
     if fb is not None:
         b_mel = float((MR.bound(x, hp, fb) + MR.bound(y, hp, fb)).mean() + U)

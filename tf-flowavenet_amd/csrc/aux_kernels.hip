@@ -5,6 +5,7 @@
 //   prior / log-det finalisation (model.py:342-343).
 #include "common.h"
 #include "fwn_internal.h"
+#include "row_steps.h"
 #include "../../include/fwn.h"
 
 // ---- weight-norm scale: scale[n] = g[n] / sqrt(max(sum_k V[k][n]^2, 1e-12)) ----------------
@@ -473,8 +474,8 @@ static inline dim3 row_grid(long bytes_per_row, long nrows) {
     return dim3((unsigned)(want < 1 ? 1 : (want > cap ? cap : want)), (unsigned)nrows);
 }
 // Every length and every core comes from a table in device memory and is clamped where it is read, so no value of it loads
-// or stores outside the buffer: a length to [0, T]; a core's offset to [0, L] and its count to what is left of L.
-__device__ __forceinline__ long clamp_len(long len, long T) { return len < 0 ? 0 : (len > T ? T : len); }
+// or stores outside the buffer: a length to [0, T] (row_steps.h's clamp_len); a core's offset to [0, L] and its count to what
+// is left of L.
 __device__ __forceinline__ void clamp_core(long& off, long& n, long L) {
     off = clamp_len(off, L);
     n = clamp_len(n, L - off);
@@ -645,13 +646,8 @@ __global__ void corpus_advance_kernel(unsigned long long* counter) {
 }
 
 // ---- synthesis: fp32 waveform -> 16-bit PCM ------------------------------------------------------------------
-// x [B][T] fp32 -> pcm [B][T] int16 = rint((double)clamp(x, -1, 1) * 32767.0), NaN -> 0: synthesize.write_wav's float64 NumPy
-// arithmetic bit for bit (the fp64 product of an fp32 value and 32767 is exact, so the one rounding is rint's half-to-even;
-// the fp32 product would round twice at near-ties).  Samples at i >= len[b] (clamped) are 0.
-__device__ __forceinline__ short pcm16_of(float v) {
-    v = (v != v) ? 0.0f : fminf(fmaxf(v, -1.0f), 1.0f);
-    return (short)(int)rint((double)v * 32767.0);
-}
+// x [B][T] fp32 -> pcm [B][T] int16 = pcm16_of(x) (row_steps.h: synthesize.write_wav's float64 NumPy arithmetic bit for bit).
+// Samples at i >= len[b] (clamped) are 0.
 // One row: pr[0, n) = pcm16_of(xr[i]) for i < keep, 0 from keep on - and nothing of xr from keep on is loaded.  Between the
 // first and the last 16-byte boundary of pr, one lane turns eight samples (two 16-byte loads) into one 16-byte store - where
 // xr is 16-byte aligned at that first boundary too; the up to seven samples on either side go one by one, and so does the

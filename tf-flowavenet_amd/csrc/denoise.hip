@@ -12,25 +12,19 @@
 // bits depend on the clip's samples within n_fft of it, the clip's length, bias and strength only.  Twiddles come from
 // sincospif once per workgroup; the window is 0.5 - 0.5 cos from the same table.  mean_mag_kernel is the bias: the forward
 // half over the interior frames of B equal rows, |X[k]| summed per bin in fp64 in frame order by one workgroup.
-// The load, the passes and the split are stft_lds.h's (shared with melfront.hip); its header has the LDS bank notes.
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdint.h>
-
-#include "../../include/fwn.h"
+// The load, the passes and the split are stft_lds.h's (shared with melfront.hip and specdist.hip); its header has the LDS bank
+// notes.  The PCM sample is row_steps.h's pcm16_of, fwn_pcm16's own; the argument checks are audio_args.h's.
+#include "audio_args.h"
+#include "row_steps.h"
 #include "stft_lds.h"
-
-int fwn_set_error(int code, const char* fmt, ...);      // api.hip: thread-local message of fwn_last_error()
-#define DREQUIRE(cond, ...) do { if (!(cond)) return fwn_set_error(FWN_ERR_ARG, __VA_ARGS__); } while (0)
 
 namespace {
 
 using namespace stft_lds;                   // NT, batch_of, lds_floats: [n_fft / 2 + 1] thresholds (or, for the bias, fp64 sums) in the tail
+using namespace audio_args;
 
 constexpr int TILE = 2048;                  // output samples per workgroup
 constexpr int PER = TILE / NT;              // samples a lane owns: tile samples lane, lane + NT, ...
-constexpr int64_t MAX_LEN = (int64_t)1 << 40;
-constexpr int64_t MAX_STRIDE = (int64_t)1 << 44;            // keeps B * stride * 4 inside int64
 constexpr int64_t MAX_BIAS_FRAMES = 1 << 20;
 
 // soft threshold of the magnitude, the phase kept: X (1 - t / |X|) where |X| > t, else 0.  t = 0 returns X's own bits.
@@ -73,11 +67,6 @@ __device__ __forceinline__ void threshold_in_place(float2* z, const float2* tw, 
     }
 }
 
-// fwn_pcm16's arithmetic (aux_kernels.hip pcm16_of), restated here so that the unit stands alone; tests hold the two equal
-__device__ __forceinline__ short pcm16_of(float v) {
-    v = (v != v) ? 0.0f : fminf(fmaxf(v, -1.0f), 1.0f);
-    return (short)(int)rint((double)v * 32767.0);
-}
 __device__ __forceinline__ void put(float* yrow, short* prow, long i, float v) {
     if (yrow) yrow[i] = v;
     if (prow) prow[i] = pcm16_of(v);
@@ -198,16 +187,6 @@ __global__ __launch_bounds__(NT) void mean_mag_kernel(const float* __restrict__ 
     for (int k = tid; k <= nc; k += NT) mag_out[k] = (float)(sum[k] / (double)total);
 }
 
-int check_shape(const char* fn, int n_fft, int hop) {
-    DREQUIRE(n_fft >= 32 && n_fft <= 4096 && (n_fft & (n_fft - 1)) == 0, "%s: n_fft %d is not a power of two in 32..4096", fn, n_fft);
-    DREQUIRE(hop >= 1 && hop <= n_fft / 2, "%s: hop %d outside 1..n_fft/2 = %d", fn, hop, n_fft / 2);
-    return FWN_OK;
-}
-bool overlap(const void* p, int64_t pbytes, const void* q, int64_t qbytes) {
-    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-    return a < b + (uintptr_t)qbytes && b < a + (uintptr_t)pbytes;
-}
-
 }  // namespace
 
 extern "C" {
@@ -223,56 +202,48 @@ size_t fwn_denoise_workspace_bytes(int64_t B, int64_t len_host, int n_fft, int h
 }
 
 int fwn_stft_mean_mag(const float* x, int64_t B, int64_t x_stride, int64_t len_host, int n_fft, int hop, float* mag_out, void* stream) {
-    if (int rc = check_shape("fwn_stft_mean_mag", n_fft, hop)) return rc;
-    DREQUIRE(x && mag_out, "fwn_stft_mean_mag: null pointer");
-    DREQUIRE((((uintptr_t)x) & 3) == 0 && (((uintptr_t)mag_out) & 3) == 0, "fwn_stft_mean_mag: a pointer is off its element's alignment");
-    DREQUIRE(B >= 1 && B < 65536, "fwn_stft_mean_mag: B %lld outside 1..65535", (long long)B);
-    DREQUIRE(len_host >= 1 && len_host <= MAX_LEN, "fwn_stft_mean_mag: clip length %lld outside 1..2^40", (long long)len_host);
-    DREQUIRE(x_stride >= len_host && x_stride <= MAX_STRIDE, "fwn_stft_mean_mag: row stride %lld shorter than the row %lld, or above 2^44",
-             (long long)x_stride, (long long)len_host);
+    const char* fn = "fwn_stft_mean_mag";
+    if (int rc = check_shape(fn, n_fft, hop)) return rc;
+    if (int rc = check_clips(fn, B, nullptr, len_host)) return rc;
+    if (int rc = check_rows(fn, "x", x, 4, x_stride, len_host)) return rc;
+    if (int rc = check_ptr(fn, "mag_out", mag_out, 4)) return rc;
     // interior: the frame's n_fft samples [f hop - n_fft / 2, f hop + n_fft / 2) lie inside [0, len_host)
     const int64_t h = n_fft / 2, f_min = (h + hop - 1) / hop, f_max = (len_host - h) / hop;
-    DREQUIRE(len_host >= n_fft && f_max >= f_min, "fwn_stft_mean_mag: a clip of %lld samples has no interior frame at n_fft %d, hop %d",
+    AREQUIRE(len_host >= n_fft && f_max >= f_min, "%s: a clip of %lld samples has no interior frame at n_fft %d, hop %d", fn,
              (long long)len_host, n_fft, hop);
     const int64_t n_int = f_max - f_min + 1;
-    DREQUIRE(B * n_int <= MAX_BIAS_FRAMES, "fwn_stft_mean_mag: %lld interior frames, more than the %lld one workgroup is given",
+    AREQUIRE(B * n_int <= MAX_BIAS_FRAMES, "%s: %lld interior frames, more than the %lld one workgroup is given", fn,
              (long long)(B * n_int), (long long)MAX_BIAS_FRAMES);
     const int G = batch_of(n_fft);
     hipLaunchKernelGGL(mean_mag_kernel, dim3(1), dim3(NT), lds_floats(n_fft, 2) * sizeof(float), (hipStream_t)stream, x, (long)B,
                        (long)x_stride, (long)len_host, n_fft, log2_of(n_fft / 2), hop, G, (long)f_min, (long)n_int, mag_out);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fwn_set_error(FWN_ERR_HIP, "fwn_stft_mean_mag: %s", hipGetErrorString(e));
-    return FWN_OK;
+    return launched(fn);
 }
 
 int fwn_denoise(const float* x, int64_t B, int64_t x_stride, const int64_t* len_dev, int64_t len_host, const float* bias_dev,
                 float strength, int n_fft, int hop, float* y, int64_t y_stride, int16_t* pcm, int64_t pcm_stride, void* workspace,
                 size_t workspace_bytes, void* stream) {
-    if (int rc = check_shape("fwn_denoise", n_fft, hop)) return rc;
-    DREQUIRE(x && bias_dev && (y || pcm), "fwn_denoise: null pointer (x, bias_dev, or both outputs)");
-    DREQUIRE((((uintptr_t)x) & 3) == 0 && (((uintptr_t)bias_dev) & 3) == 0 && (((uintptr_t)y) & 3) == 0 && (((uintptr_t)pcm) & 1) == 0 &&
-             (((uintptr_t)len_dev) & 7) == 0, "fwn_denoise: a pointer is off its element's alignment");
-    DREQUIRE(B >= 1 && B < 65536, "fwn_denoise: B %lld outside 1..65535", (long long)B);
-    DREQUIRE(len_host >= 1 && len_host <= MAX_LEN, "fwn_denoise: clip length %lld outside 1..2^40", (long long)len_host);
-    DREQUIRE(x_stride >= len_host && x_stride <= MAX_STRIDE && (!y || (y_stride >= len_host && y_stride <= MAX_STRIDE)) &&
-             (!pcm || (pcm_stride >= len_host && pcm_stride <= MAX_STRIDE)),
-             "fwn_denoise: a row stride (%lld / %lld / %lld) is shorter than the row %lld, or above 2^44", (long long)x_stride,
-             (long long)y_stride, (long long)pcm_stride, (long long)len_host);
-    DREQUIRE(strength >= 0.0f && strength <= 3.0e38f, "fwn_denoise: strength %g is negative, infinite or NaN", (double)strength);
-    DREQUIRE(workspace_bytes >= fwn_denoise_workspace_bytes(B, len_host, n_fft, hop) && (workspace || workspace_bytes == 0),
-             "fwn_denoise: workspace of %zu bytes at a null pointer, or smaller than fwn_denoise_workspace_bytes", workspace_bytes);
+    const char* fn = "fwn_denoise";
+    if (int rc = check_shape(fn, n_fft, hop)) return rc;
+    if (int rc = check_clips(fn, B, len_dev, len_host)) return rc;
+    if (int rc = check_rows(fn, "x", x, 4, x_stride, len_host)) return rc;
+    if (int rc = check_ptr(fn, "bias_dev", bias_dev, 4)) return rc;
+    AREQUIRE(y || pcm, "%s: null pointer (both outputs)", fn);
+    if (y) if (int rc = check_rows(fn, "y", y, 4, y_stride, len_host)) return rc;
+    if (pcm) if (int rc = check_rows(fn, "pcm", pcm, 2, pcm_stride, len_host)) return rc;
+    AREQUIRE(strength >= 0.0f && strength <= 3.0e38f, "%s: strength %g is negative, infinite or NaN", fn, (double)strength);
+    AREQUIRE(workspace_bytes >= fwn_denoise_workspace_bytes(B, len_host, n_fft, hop) && (workspace || workspace_bytes == 0),
+             "%s: workspace of %zu bytes at a null pointer, or smaller than fwn_denoise_workspace_bytes", fn, workspace_bytes);
     const int64_t xb = ((B - 1) * x_stride + len_host) * 4;
-    DREQUIRE(!(y && overlap(x, xb, y, ((B - 1) * y_stride + len_host) * 4)) && !(pcm && overlap(x, xb, pcm, ((B - 1) * pcm_stride + len_host) * 2)),
-             "fwn_denoise: an output overlaps the input (a tile reads its neighbours' samples)");
+    AREQUIRE(!(y && overlap(x, xb, y, ((B - 1) * y_stride + len_host) * 4)) && !(pcm && overlap(x, xb, pcm, ((B - 1) * pcm_stride + len_host) * 2)),
+             "%s: an output overlaps the input (a tile reads its neighbours' samples)", fn);
     const int64_t tiles = (len_host + TILE - 1) / TILE;
-    DREQUIRE(tiles < ((int64_t)1 << 31), "fwn_denoise: %lld tiles per row", (long long)tiles);
+    AREQUIRE(tiles < ((int64_t)1 << 31), "%s: %lld tiles per row", fn, (long long)tiles);
     const int G = batch_of(n_fft);
     hipLaunchKernelGGL(denoise_kernel, dim3((unsigned)tiles, (unsigned)B), dim3(NT), lds_floats(n_fft, 1) * sizeof(float),
                        (hipStream_t)stream, x, (long)x_stride, (const long long*)len_dev, (long)len_host, bias_dev, strength, n_fft,
                        log2_of(n_fft / 2), hop, G, y, (long)y_stride, (short*)pcm, (long)pcm_stride);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fwn_set_error(FWN_ERR_HIP, "fwn_denoise: %s", hipGetErrorString(e));
-    return FWN_OK;
+    return launched(fn);
 }
 
 }  // extern "C"

@@ -8,30 +8,24 @@
 //   mel_front_kernel  a workgroup owns FRAMES consecutive frames of one clip and transforms them G = batch_of(n_fft) at a time:
 //     load     v_f[n] = w[n] xn[reflect(f hop + n - n_fft / 2)], xn = (x / peak) * rmax, as n_fft / 2 complex points
 //     forward  the radix-2 Stockham passes, ping-pong between two LDS buffers
-//     power    |X[k]|^2, |X[nc - k]|^2 from Z[k], Z[nc - k] (split_pair) into LDS [G][nb], one lane per pair
-//     mel      one lane per (frame, mel): fmaf over the filter's bins [bands[m][0], bands[m][1]) in ascending k, 20 log10, clip
+//     power    stft_lds.h's power_rows: |X[k]|^2, |X[nc - k]|^2 from Z[k], Z[nc - k] (split_pair) into LDS [G][nb], one lane per pair
+//     mel      one lane per (frame, mel), stft_lds.h's mel_of: fmaf over the filter's bins [bands[m][0], bands[m][1]) in
+//              ascending k, 20 log10, clip
 //   and stores the hop-sample stretches of `audio` that belong to its frames.  Frames at or past the clip's own count, and every
 //   frame of a clip that is silent, NaN or too short to reflect, are written as +0.  A frame is computed by the same
 //   instructions whichever slot, workgroup, row or batch it lands in: its bits depend on the clip's samples in its support, on
-//   N_b, peak[b], rmax and fb only.
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdint.h>
-
-#include "../../include/fwn.h"
+//   N_b, peak[b], rmax and fb only.  The argument checks are audio_args.h's.
+#include "audio_args.h"
+#include "row_steps.h"
 #include "stft_lds.h"
-
-int fwn_set_error(int code, const char* fmt, ...);      // api.hip: thread-local message of fwn_last_error()
-#define MREQUIRE(cond, ...) do { if (!(cond)) return fwn_set_error(FWN_ERR_ARG, __VA_ARGS__); } while (0)
 
 namespace {
 
 using namespace stft_lds;
+using namespace audio_args;
 
 constexpr int FRAMES = 8;                   // frames a workgroup owns (fwn_mel_front_frames)
 constexpr int CHUNK = 16384;                // samples of one clip a peak workgroup reads: 64 per lane
-constexpr int64_t MAX_LEN = (int64_t)1 << 40;
-constexpr int64_t MAX_STRIDE = (int64_t)1 << 44;            // keeps B * stride * 4 inside int64
 
 // |v| as bits: +0 for both zeros, 0x7f800000 for the infinities, anything above that for a NaN
 __device__ __forceinline__ unsigned abs_bits(float v) { return __float_as_uint(v) & 0x7fffffffu; }
@@ -76,7 +70,7 @@ __global__ __launch_bounds__(NT) void mel_front_kernel(const float* __restrict__
                                                        int hop, int n_mels, int G, float ref_db, float min_db, float* __restrict__ mel,
                                                        long mel_stride, float* __restrict__ audio, long audio_stride) {
     extern __shared__ float sm[];
-    const int tid = threadIdx.x, h = n_fft / 2, nc = h, half = nc >> 1, per = half + 1, nb = h + 1;
+    const int tid = threadIdx.x, h = n_fft / 2, nc = h, nb = h + 1;
     const long b = blockIdx.y;
     const long N = clamp_len(len_dev, b, len_host);
     const long F = 1 + N / hop, F_host = 1 + len_host / hop;
@@ -115,59 +109,14 @@ __global__ __launch_bounds__(NT) void mel_front_kernel(const float* __restrict__
         __syncthreads();
         float2 *a = l.a, *bb = l.b;
         fft_passes(a, bb, l.tw, nc, lognc, frames, -1.0f);
-        for (int i = tid; i < frames * per; i += NT) {         // lane owns bins k and nc - k of frame g
-            const int g = i / per, k = i - g * per;
-            const float2* zf = a + (size_t)g * nc;
-            float* pf = pw + (size_t)g * nb;
-            if (k == 0) {                                      // X[0] and X[nc] are real
-                const float x0 = zf[0].x + zf[0].y, xn = zf[0].x - zf[0].y;
-                pf[0] = x0 * x0;
-                pf[nc] = xn * xn;
-            } else if (k == half) {                            // its own partner: X = conj Z
-                pf[half] = zf[half].x * zf[half].x + zf[half].y * zf[half].y;
-            } else {
-                float2 Xk, Xm;
-                split_pair(zf[k], zf[nc - k], l.tw[k], Xk, Xm);
-                pf[k] = Xk.x * Xk.x + Xk.y * Xk.y;
-                pf[nc - k] = Xm.x * Xm.x + Xm.y * Xm.y;
-            }
-        }
+        power_rows(a, l.tw, frames, nc, pw, nb);
         __syncthreads();
         for (int i = tid; i < frames * n_mels; i += NT) {      // lane owns (frame g, mel m)
             const int g = i / n_mels, m = i - g * n_mels;
-            int lo = 0, hi = nb;
-            if (bands) {
-                lo = bands[2 * m] < 0 ? 0 : bands[2 * m];
-                hi = bands[2 * m + 1] > nb ? nb : bands[2 * m + 1];
-            }
-            const float* w = fb + (long)m * nb;
-            const float* pf = pw + (size_t)g * nb;
-            float acc = 0.0f;
-            for (int k = lo; k < hi; ++k) acc = fmaf(w[k], pf[k], acc);
-            const float db = 20.0f * log10f(fmaxf(1e-4f, acc)) - ref_db;
-            mrow[g0 * n_mels + i] = fminf(fmaxf((db - min_db) / (-min_db), 0.0f), 1.0f);
+            mrow[g0 * n_mels + i] = mel_of(fb, bands, m, nb, pw + (size_t)g * nb, ref_db, min_db);
         }
         __syncthreads();                                       // before the next batch is loaded over l.a and pw
     }
-}
-
-int check_shape(const char* fn, int n_fft, int hop) {
-    MREQUIRE(n_fft >= 32 && n_fft <= 4096 && (n_fft & (n_fft - 1)) == 0, "%s: n_fft %d is not a power of two in 32..4096", fn, n_fft);
-    MREQUIRE(hop >= 1 && hop <= n_fft / 2, "%s: hop %d outside 1..n_fft/2 = %d", fn, hop, n_fft / 2);
-    return FWN_OK;
-}
-int check_rows(const char* fn, const float* x, int64_t B, int64_t x_stride, const int64_t* len_dev, int64_t len_host) {
-    MREQUIRE(x, "%s: null pointer (x)", fn);
-    MREQUIRE((((uintptr_t)x) & 3) == 0 && (((uintptr_t)len_dev) & 7) == 0, "%s: a pointer is off its element's alignment", fn);
-    MREQUIRE(B >= 1 && B < 65536, "%s: B %lld outside 1..65535", fn, (long long)B);
-    MREQUIRE(len_host >= 1 && len_host <= MAX_LEN, "%s: clip length %lld outside 1..2^40", fn, (long long)len_host);
-    MREQUIRE(x_stride >= len_host && x_stride <= MAX_STRIDE, "%s: row stride %lld shorter than the row %lld, or above 2^44", fn,
-             (long long)x_stride, (long long)len_host);
-    return FWN_OK;
-}
-bool overlap(const void* p, int64_t pbytes, const void* q, int64_t qbytes) {
-    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-    return a < b + (uintptr_t)qbytes && b < a + (uintptr_t)pbytes;
 }
 
 }  // namespace
@@ -180,41 +129,41 @@ int fwn_mel_front_frames(int n_fft, int hop) {
 }
 
 int fwn_clip_peak(const float* x, int64_t B, int64_t x_stride, const int64_t* len_dev, int64_t len_host, float* peak_out, void* stream) {
-    if (int rc = check_rows("fwn_clip_peak", x, B, x_stride, len_dev, len_host)) return rc;
-    MREQUIRE(peak_out, "fwn_clip_peak: null pointer (peak_out)");
-    MREQUIRE((((uintptr_t)peak_out) & 3) == 0, "fwn_clip_peak: a pointer is off its element's alignment");
-    MREQUIRE(!overlap(x, ((B - 1) * x_stride + len_host) * 4, peak_out, B * 4), "fwn_clip_peak: the output overlaps the input");
+    const char* fn = "fwn_clip_peak";
+    if (int rc = check_clips(fn, B, len_dev, len_host)) return rc;
+    if (int rc = check_rows(fn, "x", x, 4, x_stride, len_host)) return rc;
+    if (int rc = check_ptr(fn, "peak_out", peak_out, 4)) return rc;
+    AREQUIRE(!overlap(x, ((B - 1) * x_stride + len_host) * 4, peak_out, B * 4), "%s: the output overlaps the input", fn);
     const int64_t chunks = (len_host + CHUNK - 1) / CHUNK;     // <= 2^26
-    hipError_t e = hipMemsetAsync(peak_out, 0, (size_t)B * 4, (hipStream_t)stream);     // +0: an empty clip's peak, and the maximum's start
-    if (e != hipSuccess) return fwn_set_error(FWN_ERR_HIP, "fwn_clip_peak: %s", hipGetErrorString(e));
+    // +0: an empty clip's peak, and the maximum's start
+    if (int rc = launched(fn, hipMemsetAsync(peak_out, 0, (size_t)B * 4, (hipStream_t)stream))) return rc;
     hipLaunchKernelGGL(peak_abs_kernel, dim3((unsigned)chunks, (unsigned)B), dim3(NT), 0, (hipStream_t)stream, x, (long)x_stride,
                        (const long long*)len_dev, (long)len_host, (unsigned*)peak_out);
-    e = hipGetLastError();
-    if (e != hipSuccess) return fwn_set_error(FWN_ERR_HIP, "fwn_clip_peak: %s", hipGetErrorString(e));
-    return FWN_OK;
+    return launched(fn);
 }
 
 int fwn_mel_front(const float* x, int64_t B, int64_t x_stride, const int64_t* len_dev, int64_t len_host, const float* peak_dev, float rmax,
                   const float* fb, const int32_t* bands, int n_fft, int hop, int n_mels, float ref_level_db, float min_level_db, float* mel,
                   int64_t mel_stride, float* audio, int64_t audio_stride, void* stream) {
-    if (int rc = check_shape("fwn_mel_front", n_fft, hop)) return rc;
-    if (int rc = check_rows("fwn_mel_front", x, B, x_stride, len_dev, len_host)) return rc;
-    MREQUIRE(fb && mel, "fwn_mel_front: null pointer (fb or mel)");
-    MREQUIRE((((uintptr_t)peak_dev) & 3) == 0 && (((uintptr_t)fb) & 3) == 0 && (((uintptr_t)bands) & 3) == 0 && (((uintptr_t)mel) & 3) == 0 &&
-             (((uintptr_t)audio) & 3) == 0, "fwn_mel_front: a pointer is off its element's alignment");
-    MREQUIRE(n_mels >= 1 && n_mels <= 1024, "fwn_mel_front: n_mels %d outside 1..1024", n_mels);
-    MREQUIRE(min_level_db < 0.0f, "fwn_mel_front: min_level_db %g must be negative", (double)min_level_db);
-    MREQUIRE(rmax >= -3.0e38f && rmax <= 3.0e38f, "fwn_mel_front: rmax %g is infinite or NaN", (double)rmax);
-    MREQUIRE(!peak_dev || rmax > 0.0f, "fwn_mel_front: rmax %g must be positive when clips are normalised (peak_dev given)", (double)rmax);
+    const char* fn = "fwn_mel_front";
+    if (int rc = check_shape(fn, n_fft, hop)) return rc;
+    if (int rc = check_clips(fn, B, len_dev, len_host)) return rc;
+    if (int rc = check_rows(fn, "x", x, 4, x_stride, len_host)) return rc;
+    if (int rc = check_ptr(fn, "peak_dev", peak_dev, 4, true)) return rc;
+    if (int rc = check_ptr(fn, "fb", fb, 4)) return rc;
+    if (int rc = check_ptr(fn, "bands", bands, 4, true)) return rc;
+    AREQUIRE(n_mels >= 1 && n_mels <= 1024, "%s: n_mels %d outside 1..1024", fn, n_mels);
+    AREQUIRE(min_level_db < 0.0f, "%s: min_level_db %g must be negative", fn, (double)min_level_db);
+    AREQUIRE(rmax >= -3.0e38f && rmax <= 3.0e38f, "%s: rmax %g is infinite or NaN", fn, (double)rmax);
+    AREQUIRE(!peak_dev || rmax > 0.0f, "%s: rmax %g must be positive when clips are normalised (peak_dev given)", fn, (double)rmax);
     const int64_t F_host = 1 + len_host / hop, mel_row = F_host * n_mels, audio_row = F_host * hop;
-    MREQUIRE(mel_stride >= mel_row && mel_stride <= MAX_STRIDE && (!audio || (audio_stride >= audio_row && audio_stride <= MAX_STRIDE)),
-             "fwn_mel_front: a row stride (mel %lld / audio %lld) is shorter than the row it holds (%lld / %lld), or above 2^44",
-             (long long)mel_stride, (long long)audio_stride, (long long)mel_row, (long long)audio_row);
+    if (int rc = check_rows(fn, "mel", mel, 4, mel_stride, mel_row)) return rc;
+    if (audio) if (int rc = check_rows(fn, "audio", audio, 4, audio_stride, audio_row)) return rc;
     const int64_t groups = (F_host + FRAMES - 1) / FRAMES;
-    MREQUIRE(groups < ((int64_t)1 << 31), "fwn_mel_front: %lld workgroups per row, past 2^31 - 1", (long long)groups);
+    AREQUIRE(groups < ((int64_t)1 << 31), "%s: %lld workgroups per row, past 2^31 - 1", fn, (long long)groups);
     const int64_t xb = ((B - 1) * x_stride + len_host) * 4;
-    MREQUIRE(!overlap(x, xb, mel, ((B - 1) * mel_stride + mel_row) * 4) && !(audio && overlap(x, xb, audio, ((B - 1) * audio_stride + audio_row) * 4)),
-             "fwn_mel_front: an output overlaps the input (a frame reads its neighbours' samples)");
+    AREQUIRE(!overlap(x, xb, mel, ((B - 1) * mel_stride + mel_row) * 4) && !(audio && overlap(x, xb, audio, ((B - 1) * audio_stride + audio_row) * 4)),
+             "%s: an output overlaps the input (a frame reads its neighbours' samples)", fn);
     const int G = batch_of(n_fft);
     const dim3 grid((unsigned)groups, (unsigned)B);
     const size_t lds = lds_floats(n_fft, G) * sizeof(float);
@@ -226,9 +175,7 @@ int fwn_mel_front(const float* x, int64_t B, int64_t x_stride, const int64_t* le
         hipLaunchKernelGGL(mel_front_kernel<false>, grid, dim3(NT), lds, (hipStream_t)stream, x, (long)x_stride, (const long long*)len_dev,
                            (long)len_host, peak_dev, rmax, fb, (const int*)bands, n_fft, log2_of(n_fft / 2), hop, n_mels, G, ref_level_db,
                            min_level_db, mel, (long)mel_stride, audio, (long)audio_stride);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fwn_set_error(FWN_ERR_HIP, "fwn_mel_front: %s", hipGetErrorString(e));
-    return FWN_OK;
+    return launched(fn);
 }
 
 }  // extern "C"

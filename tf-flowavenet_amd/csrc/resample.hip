@@ -5,22 +5,20 @@
 // TILE consecutive outputs of one clip, stages the input span they read in LDS (converted to fp32, zeros outside the clip and
 // outside the provided span - nothing out there is loaded) and each lane walks its phase row through L2.  A lane's sum is four
 // fmaf chains over k = 0, 1, 2, 3 (mod 4), added as (a0 + a1) + (a2 + a3): the order is a function of k alone, so an output's
-// bits do not depend on the tile, the row, in_start or m0.
-#include <hip/hip_runtime.h>
+// bits do not depend on the tile, the row, in_start or m0.  A clip's length comes through row_steps.h's clamp_len; the argument
+// checks the audio units share are audio_args.h's.
 #include <math.h>
-#include <stdint.h>
 
-#include "../../include/fwn.h"
-
-int fwn_set_error(int code, const char* fmt, ...);      // api.hip: thread-local message of fwn_last_error()
-#define RREQUIRE(cond, ...) do { if (!(cond)) return fwn_set_error(FWN_ERR_ARG, __VA_ARGS__); } while (0)
+#include "audio_args.h"
+#include "row_steps.h"
 
 namespace {
+
+using namespace audio_args;
 
 constexpr int TILE = 256;                   // outputs per workgroup, one per lane
 constexpr long LDS_FLOATS = 16384;          // 64 KiB of dynamic LDS: the largest staged span a launch may ask for
 constexpr int64_t MAX_RATE = 1 << 20;       // up, down: keeps m * down and N * up inside int64 for N <= 2^40
-constexpr int64_t MAX_LEN = (int64_t)1 << 40;
 
 int64_t gcd64(int64_t a, int64_t b) { while (b) { int64_t t = a % b; a = b; b = t; } return a; }
 // floor / ceil of a / b for b > 0 and any sign of a
@@ -50,8 +48,7 @@ __global__ __launch_bounds__(TILE) void resample_kernel(const XT* __restrict__ x
     extern __shared__ float xs[];
     const int tid = threadIdx.x;
     const long b = blockIdx.y;
-    long N = len_dev ? (long)len_dev[b] : len_host;            // read and clamped here: the host never sees it
-    N = N < 0 ? 0 : (N > len_host ? len_host : N);
+    const long N = clamp_len(len_dev, b, len_host);
     const long clip_out = (N * up + down - 1) / down;          // n_out(N)
     const long i0 = (long)blockIdx.x * TILE;                   // first requested output of this tile
     const long left = n_req - i0;
@@ -98,9 +95,9 @@ __global__ __launch_bounds__(TILE) void resample_kernel(const XT* __restrict__ x
 }
 
 int check_ratio(const char* fn, int up, int down, int zeros) {
-    RREQUIRE(up >= 1 && down >= 1 && up <= MAX_RATE && down <= MAX_RATE, "%s: up %d / down %d outside 1..%d", fn, up, down, (int)MAX_RATE);
-    RREQUIRE(gcd64(up, down) == 1, "%s: up %d / down %d is not in lowest terms (gcd %d)", fn, up, down, (int)gcd64(up, down));
-    RREQUIRE(zeros >= 1 && zeros <= 64, "%s: zeros %d outside 1..64", fn, zeros);
+    AREQUIRE(up >= 1 && down >= 1 && up <= MAX_RATE && down <= MAX_RATE, "%s: up %d / down %d outside 1..%d", fn, up, down, (int)MAX_RATE);
+    AREQUIRE(gcd64(up, down) == 1, "%s: up %d / down %d is not in lowest terms (gcd %d)", fn, up, down, (int)gcd64(up, down));
+    AREQUIRE(zeros >= 1 && zeros <= 64, "%s: zeros %d outside 1..64", fn, zeros);
     return FWN_OK;
 }
 
@@ -116,9 +113,9 @@ int fwn_resample_taps(int up, int down, int zeros) {
 
 int fwn_resample_design(int up, int down, int zeros, double beta, double rolloff, float* table_host) {
     if (int rc = check_ratio("fwn_resample_design", up, down, zeros)) return rc;
-    RREQUIRE(rolloff > 0.0 && rolloff <= 1.0, "fwn_resample_design: rolloff %g outside (0, 1]", rolloff);
-    RREQUIRE(beta >= 0.0 && beta <= 100.0, "fwn_resample_design: beta %g outside [0, 100]", beta);   // (a NaN fails both)
-    RREQUIRE(table_host, "fwn_resample_design: null table");
+    AREQUIRE(rolloff > 0.0 && rolloff <= 1.0, "fwn_resample_design: rolloff %g outside (0, 1]", rolloff);
+    AREQUIRE(beta >= 0.0 && beta <= 100.0, "fwn_resample_design: beta %g outside [0, 100]", beta);   // (a NaN fails both)
+    AREQUIRE(table_host, "fwn_resample_design: null table");
     const int64_t q = up > down ? up : down, Hh = (int64_t)zeros * q;
     const int64_t K = 2 * Hh / up + 1;
     const double i0b = bessel_i0(beta), gain = (double)up * rolloff / (double)q;
@@ -141,20 +138,19 @@ int fwn_resample(const void* x, int x_pcm16, int64_t B, int64_t x_stride, int64_
                  int64_t len_host, const float* table_dev, int up, int down, int zeros, float* y, int64_t y_stride, int64_t m0,
                  int64_t n_out, void* stream) {
     if (int rc = check_ratio("fwn_resample", up, down, zeros)) return rc;
-    RREQUIRE(x && table_dev && y, "fwn_resample: null pointer");
-    RREQUIRE(x_pcm16 == 0 || x_pcm16 == 1, "fwn_resample: x_pcm16 must be 0 (float32) or 1 (16-bit PCM), got %d", x_pcm16);
-    RREQUIRE((((uintptr_t)x) & (x_pcm16 ? 1 : 3)) == 0 && (((uintptr_t)y) & 3) == 0 && (((uintptr_t)table_dev) & 3) == 0 &&
-             (((uintptr_t)len_dev) & 7) == 0, "fwn_resample: a pointer is off its element's alignment");
-    RREQUIRE(B >= 1 && B < 65536, "fwn_resample: B %lld outside 1..65535", (long long)B);
-    RREQUIRE(len_host >= 0 && len_host <= MAX_LEN, "fwn_resample: clip length %lld outside 0..2^40", (long long)len_host);
-    RREQUIRE(in_start >= 0 && n_in >= 0 && in_start <= MAX_LEN && n_in <= MAX_LEN && m0 >= 0 && m0 <= MAX_LEN * MAX_RATE && n_out >= 1 &&
+    AREQUIRE(x_pcm16 == 0 || x_pcm16 == 1, "fwn_resample: x_pcm16 must be 0 (float32) or 1 (16-bit PCM), got %d", x_pcm16);
+    if (int rc = check_ptr("fwn_resample", "x", x, x_pcm16 ? 2 : 4)) return rc;
+    if (int rc = check_ptr("fwn_resample", "table_dev", table_dev, 4)) return rc;
+    if (int rc = check_ptr("fwn_resample", "y", y, 4)) return rc;
+    if (int rc = check_clips("fwn_resample", B, len_dev, len_host, 0)) return rc;      // an empty clip is a clip
+    AREQUIRE(in_start >= 0 && n_in >= 0 && in_start <= MAX_LEN && n_in <= MAX_LEN && m0 >= 0 && m0 <= MAX_LEN * MAX_RATE && n_out >= 1 &&
              n_out < ((int64_t)1 << 31) * TILE, "fwn_resample: bad span (in_start %lld, n_in %lld) or range (m0 %lld, n_out %lld)",
              (long long)in_start, (long long)n_in, (long long)m0, (long long)n_out);
-    RREQUIRE(x_stride >= n_in && y_stride >= n_out, "fwn_resample: row strides %lld / %lld shorter than the rows %lld / %lld",
+    AREQUIRE(x_stride >= n_in && y_stride >= n_out, "fwn_resample: row strides %lld / %lld shorter than the rows %lld / %lld",
              (long long)x_stride, (long long)y_stride, (long long)n_in, (long long)n_out);
     const int64_t q = up > down ? up : down, Hh = (int64_t)zeros * q, K = 2 * Hh / up + 1;
     const int64_t span_cap = ((int64_t)(TILE - 1) * down) / up + K + 2;
-    RREQUIRE(span_cap <= LDS_FLOATS, "fwn_resample: %d / %d with %d zeros stages %lld floats per tile, more than the %ld that fit",
+    AREQUIRE(span_cap <= LDS_FLOATS, "fwn_resample: %d / %d with %d zeros stages %lld floats per tile, more than the %ld that fit",
              up, down, zeros, (long long)span_cap, LDS_FLOATS);
     // every requested output's support within [0, N) must lie in the provided span; N = len_host is the widest case (a device
     // length is clamped to it, and a shorter clip only drops samples from the top of a support)
@@ -164,7 +160,7 @@ int fwn_resample(const void* x, int x_pcm16, int64_t B, int64_t x_stride, int64_
         int64_t lo = ceildiv(m0 * down - Hh, up), hi = floordiv(mlast * down + Hh, up);
         if (lo < 0) lo = 0;
         if (hi > len_host - 1) hi = len_host - 1;
-        RREQUIRE(lo > hi || (lo >= in_start && hi < in_start + n_in),
+        AREQUIRE(lo > hi || (lo >= in_start && hi < in_start + n_in),
                  "fwn_resample: outputs [%lld, %lld] read clip samples [%lld, %lld], the provided span is [%lld, %lld)",
                  (long long)m0, (long long)mlast, (long long)lo, (long long)hi, (long long)in_start, (long long)(in_start + n_in));
     }
@@ -179,9 +175,7 @@ int fwn_resample(const void* x, int x_pcm16, int64_t B, int64_t x_stride, int64_
         hipLaunchKernelGGL(resample_kernel<float>, grid, dim3(TILE), lds, st, (const float*)x, (long)x_stride, (long)in_start, (long)n_in,
                            (const long long*)len_dev, (long)len_host, table_dev, up, down, (long)Hh, (int)K, y, (long)y_stride, (long)m0,
                            (long)n_out, (int)span_cap);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fwn_set_error(FWN_ERR_HIP, "fwn_resample: %s", hipGetErrorString(e));
-    return FWN_OK;
+    return launched("fwn_resample");
 }
 
 }  // extern "C"

@@ -4,10 +4,11 @@
 //   specdist_kernel        a workgroup owns FRAMES consecutive frames of one pair and transforms frame f of x and of y: side by side
 //                          in slots 2p, 2p + 1 where batch_of(n_fft) >= 2, one after the other at n_fft 2048 and 4096 (one slot:
 //                          x's power row waits in the tail, y's goes to the ping-pong buffer the passes left free).
-//     load, forward, power   melfront.hip's own steps (peak NULL), so a frame's power row has the front-end's bits
+//     load, forward, power   stft_lds.h's load_frame, fft_passes and power_rows, the ones melfront.hip calls (peak NULL), so a
+//                            frame's power row has the front-end's bits
 //     per bin  (10 log10 max(floor, Px) - 10 log10 max(floor, Py))^2, (sqrt Px - sqrt Py)^2 and Px in fp32, added in fp64 by the
 //              lane that owns bins tid, tid + NT, ...
-//     per mel  melfront.hip's filter loop, dB and clip for x and for y, |difference| in fp32, added in fp64 by the lane that owns
+//     per mel  stft_lds.h's mel_of, the front-end's, for x and for y, |difference| in fp32, added in fp64 by the lane that owns
 //              (pair, mel)
 //     sums     a butterfly over the wave, the four waves' values through LDS and added in order by lane 0; a frame's lsd is rooted
 //              there and added to the workgroup's in frame order
@@ -15,26 +16,19 @@
 //   specdist_final_kernel  one wave per clip adds the partials 0 .. ceil(F_b / FRAMES) - 1 - lane l takes l, l + 64, ... in order,
 //                          then the butterfly -, divides, takes the roots and writes out[b].
 // Which lane adds what, and in which order, follows from n_fft, n_mels and F_b alone: a clip's four doubles depend on its two
-// sets of samples, N_b, fb, the dB constants and floor only.
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdint.h>
-
-#include "../../include/fwn.h"
+// sets of samples, N_b, fb, the dB constants and floor only.  The argument checks are audio_args.h's.
+#include "audio_args.h"
+#include "row_steps.h"
 #include "stft_lds.h"
-
-int fwn_set_error(int code, const char* fmt, ...);      // api.hip: thread-local message of fwn_last_error()
-#define SREQUIRE(cond, ...) do { if (!(cond)) return fwn_set_error(FWN_ERR_ARG, __VA_ARGS__); } while (0)
 
 namespace {
 
 using namespace stft_lds;
+using namespace audio_args;
 
 constexpr int FRAMES = 8;                   // frames of a pair a workgroup owns (fwn_spectral_distance_frames): a multiple of every G / 2
 constexpr int MAXP = 4;                     // pairs side by side at most: batch_of() / 2
 constexpr int NW = NT / 64;
-constexpr int64_t MAX_LEN = (int64_t)1 << 40;
-constexpr int64_t MAX_STRIDE = (int64_t)1 << 44;            // keeps B * stride * 4 inside int64
 
 // v[i] summed over the workgroup, in lane 0 of wave 0 (every lane of a wave holds its wave's sum): the same tree every time
 template <int n>
@@ -55,36 +49,6 @@ __device__ __forceinline__ void block_sum(double (&v)[n], double (*red)[MAXP]) {
         }
     }
     __syncthreads();                                           // red, and whatever LDS the caller read, may be written again
-}
-
-// |X[k]|^2 of `frames` slots of Z = FFT(z) into rows pw + g * row: mel_front_kernel's power step, term for term
-__device__ __forceinline__ void power_rows(const float2* a, const float2* tw, int frames, int nc, float* pw, int row) {
-    const int half = nc >> 1, per = half + 1;
-    for (int i = threadIdx.x; i < frames * per; i += NT) {     // lane owns bins k and nc - k of slot g
-        const int g = i / per, k = i - g * per;
-        const float2* zf = a + (size_t)g * nc;
-        float* pf = pw + (size_t)g * row;
-        if (k == 0) {                                          // X[0] and X[nc] are real
-            const float x0 = zf[0].x + zf[0].y, xn = zf[0].x - zf[0].y;
-            pf[0] = x0 * x0;
-            pf[nc] = xn * xn;
-        } else if (k == half) {                                // its own partner: X = conj Z
-            pf[half] = zf[half].x * zf[half].x + zf[half].y * zf[half].y;
-        } else {
-            float2 Xk, Xm;
-            split_pair(zf[k], zf[nc - k], tw[k], Xk, Xm);
-            pf[k] = Xk.x * Xk.x + Xk.y * Xk.y;
-            pf[nc - k] = Xm.x * Xm.x + Xm.y * Xm.y;
-        }
-    }
-}
-
-// mel_front_kernel's filter sum, dB and clip of one power row
-__device__ __forceinline__ float mel_of(const float* __restrict__ w, const float* pf, int lo, int hi, float ref_db, float min_db) {
-    float acc = 0.0f;
-    for (int k = lo; k < hi; ++k) acc = fmaf(w[k], pf[k], acc);
-    const float db = 20.0f * log10f(fmaxf(1e-4f, acc)) - ref_db;
-    return fminf(fmaxf((db - min_db) / (-min_db), 0.0f), 1.0f);
 }
 
 __global__ __launch_bounds__(NT) void specdist_kernel(const float* x, long x_stride, const float* y, long y_stride,
@@ -158,14 +122,8 @@ __global__ __launch_bounds__(NT) void specdist_kernel(const float* x, long x_str
         if (fb) {
             for (int i = tid; i < pairs * n_mels; i += NT) {   // lane owns (pair p, mel m)
                 const int p = i / n_mels, m = i - p * n_mels;
-                int lo = 0, hi = nb;
-                if (bands) {
-                    lo = bands[2 * m] < 0 ? 0 : bands[2 * m];
-                    hi = bands[2 * m + 1] > nb ? nb : bands[2 * m + 1];
-                }
-                const float* w = fb + (long)m * nb;
-                const float mx = mel_of(w, pw + (size_t)p * 2 * nb, lo, hi, ref_db, min_db);
-                const float my = mel_of(w, py_rows + (size_t)p * 2 * nb, lo, hi, ref_db, min_db);
+                const float mx = mel_of(fb, bands, m, nb, pw + (size_t)p * 2 * nb, ref_db, min_db);
+                const float my = mel_of(fb, bands, m, nb, py_rows + (size_t)p * 2 * nb, ref_db, min_db);
                 acc[0] += (double)fabsf(mx - my);
             }
         }
@@ -210,15 +168,6 @@ __global__ __launch_bounds__(64) void specdist_final_kernel(const double* __rest
     }
 }
 
-int check_shape(const char* fn, int n_fft, int hop) {
-    SREQUIRE(n_fft >= 32 && n_fft <= 4096 && (n_fft & (n_fft - 1)) == 0, "%s: n_fft %d is not a power of two in 32..4096", fn, n_fft);
-    SREQUIRE(hop >= 1 && hop <= n_fft / 2, "%s: hop %d outside 1..n_fft/2 = %d", fn, hop, n_fft / 2);
-    return FWN_OK;
-}
-bool overlap(const void* p, int64_t pbytes, const void* q, int64_t qbytes) {
-    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-    return a < b + (uintptr_t)qbytes && b < a + (uintptr_t)pbytes;
-}
 int64_t groups_of(int64_t len_host, int hop) { return (1 + len_host / hop + FRAMES - 1) / FRAMES; }
 
 }  // namespace
@@ -240,26 +189,24 @@ int fwn_spectral_distance(const float* x, int64_t x_stride, const float* y, int6
                           float min_level_db, float floor, double* out, void* workspace, size_t workspace_bytes, void* stream) {
     const char* fn = "fwn_spectral_distance";
     if (int rc = check_shape(fn, n_fft, hop)) return rc;
-    SREQUIRE(x && y && out, "%s: null pointer (x, y or out)", fn);
-    SREQUIRE((((uintptr_t)x) & 3) == 0 && (((uintptr_t)y) & 3) == 0 && (((uintptr_t)fb) & 3) == 0 && (((uintptr_t)bands) & 3) == 0 &&
-             (((uintptr_t)len_dev) & 7) == 0 && (((uintptr_t)out) & 7) == 0 && (((uintptr_t)workspace) & 7) == 0,
-             "%s: a pointer is off its element's alignment", fn);
-    SREQUIRE(B >= 1 && B < 65536, "%s: B %lld outside 1..65535", fn, (long long)B);
-    SREQUIRE(len_host >= 1 && len_host <= MAX_LEN, "%s: clip length %lld outside 1..2^40", fn, (long long)len_host);
-    SREQUIRE(x_stride >= len_host && x_stride <= MAX_STRIDE && y_stride >= len_host && y_stride <= MAX_STRIDE,
-             "%s: a row stride (%lld / %lld) is shorter than the row %lld, or above 2^44", fn, (long long)x_stride, (long long)y_stride,
-             (long long)len_host);
-    SREQUIRE(fb || !bands, "%s: bands without fb", fn);
-    SREQUIRE(!fb || (n_mels >= 1 && n_mels <= 1024), "%s: n_mels %d outside 1..1024", fn, n_mels);
-    SREQUIRE(!fb || min_level_db < 0.0f, "%s: min_level_db %g must be negative", fn, (double)min_level_db);
-    SREQUIRE(floor > 0.0f && floor <= 3.0e38f, "%s: floor %g is not a finite positive power", fn, (double)floor);
+    if (int rc = check_clips(fn, B, len_dev, len_host)) return rc;
+    if (int rc = check_rows(fn, "x", x, 4, x_stride, len_host)) return rc;
+    if (int rc = check_rows(fn, "y", y, 4, y_stride, len_host)) return rc;
+    if (int rc = check_ptr(fn, "out", out, 8)) return rc;
+    if (int rc = check_ptr(fn, "fb", fb, 4, true)) return rc;
+    if (int rc = check_ptr(fn, "bands", bands, 4, true)) return rc;
+    if (int rc = check_ptr(fn, "workspace", workspace, 8, true)) return rc;
+    AREQUIRE(fb || !bands, "%s: bands without fb", fn);
+    AREQUIRE(!fb || (n_mels >= 1 && n_mels <= 1024), "%s: n_mels %d outside 1..1024", fn, n_mels);
+    AREQUIRE(!fb || min_level_db < 0.0f, "%s: min_level_db %g must be negative", fn, (double)min_level_db);
+    AREQUIRE(floor > 0.0f && floor <= 3.0e38f, "%s: floor %g is not a finite positive power", fn, (double)floor);
     const int64_t groups = groups_of(len_host, hop);
-    SREQUIRE(groups < ((int64_t)1 << 31), "%s: %lld workgroups per row, past 2^31 - 1", fn, (long long)groups);
+    AREQUIRE(groups < ((int64_t)1 << 31), "%s: %lld workgroups per row, past 2^31 - 1", fn, (long long)groups);
     const size_t need = (size_t)B * (size_t)groups * 4 * sizeof(double);
-    SREQUIRE(workspace && workspace_bytes >= need, "%s: workspace of %zu bytes is null or smaller than the %zu of fwn_spectral_distance_workspace_bytes",
+    AREQUIRE(workspace && workspace_bytes >= need, "%s: workspace of %zu bytes is null or smaller than the %zu of fwn_spectral_distance_workspace_bytes",
              fn, workspace_bytes, need);
     const int64_t xb = ((B - 1) * x_stride + len_host) * 4, yb = ((B - 1) * y_stride + len_host) * 4, ob = B * 4 * (int64_t)sizeof(double);
-    SREQUIRE(!overlap(x, xb, out, ob) && !overlap(y, yb, out, ob) && !overlap(x, xb, workspace, (int64_t)need) &&
+    AREQUIRE(!overlap(x, xb, out, ob) && !overlap(y, yb, out, ob) && !overlap(x, xb, workspace, (int64_t)need) &&
              !overlap(y, yb, workspace, (int64_t)need) && !overlap(out, ob, workspace, (int64_t)need),
              "%s: out or the workspace overlaps an input, or each other", fn);
     const int G = batch_of(n_fft);
@@ -267,13 +214,10 @@ int fwn_spectral_distance(const float* x, int64_t x_stride, const float* y, int6
     hipLaunchKernelGGL(specdist_kernel, dim3((unsigned)groups, (unsigned)B), dim3(NT), lds, (hipStream_t)stream, x, (long)x_stride, y,
                        (long)y_stride, (const long long*)len_dev, (long)len_host, fb, (const int*)bands, n_fft, log2_of(n_fft / 2), hop,
                        n_mels, G, ref_level_db, min_level_db, floor, (double*)workspace, (long)groups);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fwn_set_error(FWN_ERR_HIP, "%s: %s", fn, hipGetErrorString(e));
+    if (int rc = launched(fn)) return rc;
     hipLaunchKernelGGL(specdist_final_kernel, dim3((unsigned)B), dim3(64), 0, (hipStream_t)stream, (const double*)workspace, (long)groups,
                        (const long long*)len_dev, (long)len_host, n_fft, hop, n_mels, fb ? 1 : 0, out);
-    e = hipGetLastError();
-    if (e != hipSuccess) return fwn_set_error(FWN_ERR_HIP, "%s: %s", fn, hipGetErrorString(e));
-    return FWN_OK;
+    return launched(fn);
 }
 
 }  // extern "C"

@@ -1,8 +1,12 @@
-// The LDS transform the STFT units share (denoise.hip, melfront.hip): centred reflect-padded frames under the periodic Hann
-// window, taken as n_fft / 2 complex points z[m] = v[2m] + i v[2m + 1], radix-2 Stockham passes that ping-pong between two LDS
-// buffers, and the split that turns Z = FFT(z) into the bins of the real transform.  Twiddles come from sincospif once per
-// workgroup; the window is 0.5 - 0.5 cos from the same table.  Every function is a workgroup-wide step over NT lanes; a frame is
-// computed by the same instructions whichever slot, workgroup or unit computes it (the locality rule).
+// The LDS short-time transform and the steps on its result that the STFT units share (denoise.hip, melfront.hip, specdist.hip):
+//   carve, fill_twiddles, hann, load_frame, fft_passes, split_pair   all three: centred reflect-padded frames under the periodic
+//       Hann window, taken as n_fft / 2 complex points z[m] = v[2m] + i v[2m + 1], radix-2 Stockham passes that ping-pong between
+//       two LDS buffers, and the split that turns Z = FFT(z) into the bins of the real transform
+//   power_rows, mel_of                                               melfront.hip and specdist.hip: |X[k]|^2 per slot, and one
+//       mel of one power row (band clamp, filter sum, dB, clip) - one copy, so the two units' mels have the same bits
+// Twiddles come from sincospif once per workgroup; the window is 0.5 - 0.5 cos from the same table.  Every function is a
+// workgroup-wide step over NT lanes (mel_of: one lane's); a frame is computed by the same instructions whichever slot, workgroup
+// or unit computes it (the locality rule).  A clip's length comes through row_steps.h's clamp_len.
 //
 // LDS banks: a pass reads src[j] and src[j + nc / 2] as 8-byte pairs at consecutive lanes (conflict-free) and writes dst at
 // 2 (j - k) + k, k = j mod Ns: runs of Ns consecutive pairs, so the first passes (Ns = 1, 2) write at a 16-byte lane stride,
@@ -99,10 +103,43 @@ __device__ __forceinline__ void split_pair(float2 A, float2 B, float2 w, float2&
     Xm = make_float2(zer - tr, -(zei - ti));
 }
 
-// a clip's length: the device's own value clamped to [0, len_host], read here so that the host never sees it
-__device__ __forceinline__ long clamp_len(const long long* len_dev, long b, long len_host) {
-    const long N = len_dev ? (long)len_dev[b] : len_host;
-    return N < 0 ? 0 : (N > len_host ? len_host : N);
+// |X[k]|^2 of `frames` slots of Z = FFT(z) into rows pw + g * row, one lane per pair (k, nc - k), k = 0 .. nc / 2
+__device__ __forceinline__ void power_rows(const float2* a, const float2* tw, int frames, int nc, float* pw, int row) {
+    const int half = nc >> 1, per = half + 1;
+    for (int i = threadIdx.x; i < frames * per; i += NT) {     // lane owns bins k and nc - k of slot g
+        const int g = i / per, k = i - g * per;
+        const float2* zf = a + (size_t)g * nc;
+        float* pf = pw + (size_t)g * row;
+        if (k == 0) {                                          // X[0] and X[nc] are real
+            const float x0 = zf[0].x + zf[0].y, xn = zf[0].x - zf[0].y;
+            pf[0] = x0 * x0;
+            pf[nc] = xn * xn;
+        } else if (k == half) {                                // its own partner: X = conj Z
+            pf[half] = zf[half].x * zf[half].x + zf[half].y * zf[half].y;
+        } else {
+            float2 Xk, Xm;
+            split_pair(zf[k], zf[nc - k], tw[k], Xk, Xm);
+            pf[k] = Xk.x * Xk.x + Xk.y * Xk.y;
+            pf[nc - k] = Xm.x * Xm.x + Xm.y * Xm.y;
+        }
+    }
+}
+
+// mel m of the power row pf[nb]: the filter fb[m][nb] summed by fmaf in ascending k over the bins [bands[m][0], bands[m][1])
+// clamped to [0, nb) (all of them without `bands`), 20 log10 over the 1e-4 floor less ref_db, mapped from [min_db, 0] and
+// clipped to [0, 1]
+__device__ __forceinline__ float mel_of(const float* __restrict__ fb, const int* __restrict__ bands, int m, int nb, const float* pf,
+                                        float ref_db, float min_db) {
+    int lo = 0, hi = nb;
+    if (bands) {
+        lo = bands[2 * m] < 0 ? 0 : bands[2 * m];
+        hi = bands[2 * m + 1] > nb ? nb : bands[2 * m + 1];
+    }
+    const float* w = fb + (long)m * nb;
+    float acc = 0.0f;
+    for (int k = lo; k < hi; ++k) acc = fmaf(w[k], pf[k], acc);
+    const float db = 20.0f * log10f(fmaxf(1e-4f, acc)) - ref_db;
+    return fminf(fmaxf((db - min_db) / (-min_db), 0.0f), 1.0f);
 }
 
 }  // namespace stft_lds

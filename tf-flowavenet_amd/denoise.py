@@ -12,15 +12,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import _lib
-
-
-def check_shape(n_fft, hop):
-    n_fft, hop = int(n_fft), int(hop)
-    if n_fft < 32 or n_fft > 4096 or n_fft & (n_fft - 1):
-        raise ValueError("n_fft must be a power of two in 32..4096, got %r" % (n_fft,))
-    if not 1 <= hop <= n_fft // 2:
-        raise ValueError("hop must be in 1..n_fft/2 = %d, got %r" % (n_fft // 2, hop))
-    return n_fft, hop
+from .rows import as_lengths, as_rows, check_shape      # noqa: F401  (check_shape is part of this module's interface)
 
 
 def check_strength(strength):
@@ -94,7 +86,7 @@ class Denoiser:
     def mean_mag(self, x):
         """float32 ``[B, T]`` (or ``[T]``) on the device -> ``[nb]``: the mean magnitude over the rows' interior frames."""
         import torch
-        x = self._rows(x)
+        x = as_rows(x, "x", self._device, strict=True)
         out = torch.empty(self.nb, dtype=torch.float32, device=self._device)
         rc = self._lib.fwn_stft_mean_mag(x.data_ptr(), int(x.shape[0]), int(x.stride(0)) if x.shape[0] > 1 else int(x.shape[1]),
                                          int(x.shape[1]), self.n_fft, self.hop, out.data_ptr(),
@@ -102,27 +94,13 @@ class Denoiser:
         _lib.check(rc, "fwn_stft_mean_mag")
         return out
 
-    def _rows(self, x):
-        import torch
-        x = torch.as_tensor(x)
-        if x.dim() == 1:
-            x = x[None]
-        if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1:
-            raise ValueError("x must have shape [T] or [B, T] with B, T >= 1, got %r" % (tuple(x.shape),))
-        if x.dtype != torch.float32:
-            raise TypeError("x must be float32, got %s" % x.dtype)
-        return x.to(self._device).contiguous()
-
     def __call__(self, x, lengths=None, pcm=False, strength=None):
         import torch
         squeeze = torch.as_tensor(x).dim() == 1
-        x = self._rows(x)
+        x = as_rows(x, "x", self._device, strict=True)
         b, t = int(x.shape[0]), int(x.shape[1])
         s = self.strength if strength is None else check_strength(strength)
-        if lengths is not None:
-            lengths = torch.as_tensor(lengths).to(device=self._device, dtype=torch.int64).contiguous()
-            if tuple(lengths.shape) != (b,):
-                raise ValueError("lengths must have shape [%d], got %r" % (b, tuple(lengths.shape)))
+        lengths = as_lengths(lengths, b, self._device)
         out = torch.empty(b, t, dtype=torch.int16 if pcm else torch.float32, device=self._device)
         rc = self._lib.fwn_denoise(x.data_ptr(), b, t, None if lengths is None else lengths.data_ptr(), t, self.bias.data_ptr(), s,
                                    self.n_fft, self.hop, None if pcm else out.data_ptr(), t, out.data_ptr() if pcm else None, t,

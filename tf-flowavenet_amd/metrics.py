@@ -14,8 +14,8 @@ than ``n_fft / 2 + 1`` samples at some resolution gets NaN there.  There is no C
 from __future__ import annotations
 
 from . import _lib
-from .denoise import check_shape
 from .preprocessing import mel_bands, mel_filterbank
+from .rows import as_lengths, as_rows, check_shape
 
 MEASURES = ("mel_l1", "lsd_db", "sc")
 
@@ -72,17 +72,6 @@ class SpectralDistance:
         self._bands = torch.from_numpy(mel_bands(fb)).to(self._device)
         self._ws = {}                    # (B, T, n_fft, hop, stream) -> workspace
 
-    def _rows(self, x, name):
-        import torch
-        x = torch.as_tensor(x)
-        if x.dim() == 1:
-            x = x[None]
-        if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1:
-            raise ValueError("%s must have shape [T] or [B, T] with B, T >= 1, got %r" % (name, tuple(x.shape)))
-        if x.dtype != torch.float32:
-            raise TypeError("%s must be float32, got %s" % (name, x.dtype))
-        return x.to(self._device).contiguous()
-
     def _workspace(self, b, t, n_fft, hop, stream):
         import torch
         key = (b, t, n_fft, hop, stream)
@@ -94,7 +83,7 @@ class SpectralDistance:
         return self._ws[key]
 
     def one(self, x, y, lengths, n_fft, hop, mel):
-        """One resolution: device float64 ``[B, 4]`` = mel_l1 (NaN unless ``mel``), lsd_db, sc, frames.  x, y: ``_rows``."""
+        """One resolution: device float64 ``[B, 4]`` = mel_l1 (NaN unless ``mel``), lsd_db, sc, frames.  x, y: ``as_rows``."""
         import torch
         hp = self._hp
         b, t = int(x.shape[0]), int(x.shape[1])
@@ -109,15 +98,10 @@ class SpectralDistance:
         return out
 
     def dist(self, ref, test, lengths=None):
-        import torch
-        x, y = self._rows(ref, "ref"), self._rows(test, "test")
+        x, y = as_rows(ref, "ref", self._device, strict=True), as_rows(test, "test", self._device, strict=True)
         if x.shape != y.shape:
             raise ValueError("ref %r and test %r differ in shape" % (tuple(x.shape), tuple(y.shape)))
-        b = int(x.shape[0])
-        if lengths is not None:
-            lengths = torch.as_tensor(lengths).to(device=self._device, dtype=torch.int64).contiguous()
-            if tuple(lengths.shape) != (b,):
-                raise ValueError("lengths must have shape [%d], got %r" % (b, tuple(lengths.shape)))
+        lengths = as_lengths(lengths, int(x.shape[0]), self._device)
         own = self.one(x, y, lengths, self.own[0], self.own[1], True)
         per_res = [own if r == self.own else self.one(x, y, lengths, r[0], r[1], False) for r in self.resolutions]
         return combine(per_res, own, self.resolutions)

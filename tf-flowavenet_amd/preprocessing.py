@@ -32,6 +32,7 @@ import wave
 import numpy as np
 
 from . import _lib
+from .rows import as_lengths, as_rows
 
 
 def _mel_points(fmin, fmax, n):
@@ -147,17 +148,9 @@ class MelFrontEnd:
     def __call__(self, wav, lengths=None, normalize=True, audio=True, bands=True):
         import torch
         hp = self._hp
-        w = torch.as_tensor(wav)
-        if w.dim() == 1:
-            w = w[None]
-        if w.dim() != 2:
-            raise ValueError("wav must have shape [T] or [B, T], got %r" % (tuple(w.shape),))
-        w = w.to(device=self._device, dtype=torch.float32).contiguous()
+        w = as_rows(wav, "wav", self._device)
         b, t = int(w.shape[0]), int(w.shape[1])
-        if lengths is not None:
-            lengths = torch.as_tensor(lengths).to(device=self._device, dtype=torch.int64).contiguous()
-            if tuple(lengths.shape) != (b,):
-                raise ValueError("lengths must have shape [%d], got %r" % (b, tuple(lengths.shape)))
+        lengths = as_lengths(lengths, b, self._device)
         frames = 1 + t // hp.hop_size
         peak = torch.empty(b, dtype=torch.float32, device=self._device)
         mel = torch.empty(b, frames, hp.num_mels, dtype=torch.float32, device=self._device)

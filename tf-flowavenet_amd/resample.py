@@ -18,6 +18,7 @@ from math import gcd
 import numpy as np
 
 from . import _lib
+from .rows import as_lengths, as_rows
 
 ZEROS, BETA, ROLLOFF = 32, 10.0, 0.90
 
@@ -146,20 +147,10 @@ class Resampler:
 
     def __call__(self, x, lengths=None):
         import torch
-        x = torch.as_tensor(x)
-        squeeze = x.dim() == 1
-        if squeeze:
-            x = x[None]
-        if x.dim() != 2:
-            raise ValueError("x must have shape [T] or [B, T], got %r" % (tuple(x.shape),))
-        if x.dtype != torch.int16:
-            x = x.to(torch.float32)
-        x = x.to(self._device).contiguous()
+        squeeze = torch.as_tensor(x).dim() == 1
+        x = as_rows(x, "x", self._device, pcm16=True)
         b, t = int(x.shape[0]), int(x.shape[1])
-        if lengths is not None:
-            lengths = torch.as_tensor(lengths).to(device=self._device, dtype=torch.int64).contiguous()
-            if tuple(lengths.shape) != (b,):
-                raise ValueError("lengths must have shape [%d], got %r" % (b, tuple(lengths.shape)))
+        lengths = as_lengths(lengths, b, self._device)
         if self.identity:
             y = x.to(torch.float32) / 32768.0 if x.dtype == torch.int16 else x
             if lengths is not None:
